@@ -24,6 +24,14 @@ x faces the ring is a chain (no exchange between rank 0 and rank N-1).
 Protocol (mirrors mlups_3d.py:225-242): W warm-up steps, device sync + barrier, K timed steps,
 device sync + barrier; the time is the MAX over ranks; MLUPS = cells_total * K / t / 1e6.
 Inputs are resident in HBM before the timed region.  One JSON line is printed by rank 0.
+
+A plain run does only that: set-up, warm-up, the K timed steps, the outputs (--dump-outputs) and the line.
+--full adds what takes runs of its own: the two copy yardsticks (roofline.copy_yardstick_gbs, pattern_copy_ms,
+frac_of_pattern_copy; null without --full) and the CPU baseline legs (cpu_baseline).
+--dump-outputs DIR writes the populations f_0 of the last timed step, i.e. what stepper.run hands back as the current
+state, as DIR/f_0.npy ((cells, q), float32, or float64 for fp64 storage) with their linear cell indices
+(x * ny + y) * nz + z in DIR/f_0_cells.npy (float64): every cell when the field fits in DUMP_BYTES, else a fixed
+sample (default_rng(0)).  Ranks of a multi-GPU run write f_0_rank<r>.npy / f_0_cells_rank<r>.npy, global indices.
 """
 
 import argparse
@@ -54,10 +62,12 @@ def parse(argv=None):
     p.add_argument("--collision", default="BGK", choices=["BGK", "KBC"])
     p.add_argument("--policy", default="FP32FP32")
     p.add_argument("--omega", type=float, default=1.0)  # mlups_3d.py:222
-    p.add_argument("--cpu-baseline-seconds", type=float, default=14.0, help="budget of the CPU baseline legs; 0 disables them")
+    p.add_argument("--cpu-baseline-seconds", type=float, default=14.0, help="budget of the CPU baseline legs (--full); 0 disables them")
     p.add_argument("--cpu-baseline-size", type=int, default=256)
     p.add_argument("--opt", action="append", default=[], help="backend option key=value (e.g. vec=4, nt_store=0)")
     p.add_argument("--dry-run", action="store_true", help="launcher / rendezvous self-test: join the job, barrier, print a line marked dry_run; no GPU work")
+    p.add_argument("--full", action="store_true", help="also the copy yardsticks and the CPU baseline legs (runs of their own)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR", help="write f_0 of the last timed step (or a fixed sample of it) to DIR/*.npy")
     return p.parse_args(argv)
 
 
@@ -307,6 +317,38 @@ def measured_traffic(args, world, n, kernel):
     return entry[kernel], f"profiles/traffic.json (offline rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, {entry.get('profile', 'profiles/')})"
 
 
+DUMP_BYTES = 60_000_000  # what --dump-outputs writes at the most (the .npy headers included, it stays under 64 MB)
+
+
+def dump_cells(shape, row_bytes, budget=DUMP_BYTES):
+    """Sorted linear cell indices ((x * ny + y) * nz + z of the global domain) whose rows --dump-outputs writes: every cell when
+    they fit in `budget` at `row_bytes` per cell, else a fixed sample drawn by default_rng(0) — the same for every run of one shape."""
+    import numpy as np
+
+    cells = int(np.prod(shape))
+    n = min(cells, budget // row_bytes)
+    if n == cells:
+        return np.arange(cells, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(cells, size=n, replace=False))
+
+
+def dump_outputs(out_dir, f_0, grid, shape, rank, world):
+    """f_0 (the current populations a caller of stepper.run receives) at dump_cells(), from this rank's slab."""
+    import numpy as np
+
+    out_t = np.float64 if f_0.dtype.itemsize == 8 else np.float32
+    q = f_0.shape[0]
+    cells = dump_cells(shape, q * np.dtype(out_t).itemsize + 8)
+    plane = int(np.prod(shape[1:]))
+    lo, hi = grid.x_offset * plane, (grid.x_offset + grid.local_shape[0]) * plane
+    mine = cells[(cells >= lo) & (cells < hi)]
+    rows = f_0.gather(mine - lo).astype(out_t)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"f_0{sfx}.npy"), rows)
+    np.save(os.path.join(out_dir, f"f_0_cells{sfx}.npy"), mine.astype(np.float64))
+
+
 def main():
     argv = sys.argv[1:]
     args = parse(argv)
@@ -424,7 +466,8 @@ def main():
     # (after the timed region by default; XLB_BENCH_YARDSTICK=before was an experiment — does a device that has just streamed 100 GB enter a
     # short timed region faster? no: the run-to-run spread, 2.35 / 2.50 ms per step on one box, is bimodal either way and moves with
     # time inside one process on unchanged allocations: tools/alloc_modes.py, profiles/r03/run_to_run_spread.md)
-    yardstick_first = os.environ.get("XLB_BENCH_YARDSTICK", "after") == "before"
+    # (the yardsticks and the CPU baseline are --full only: a plain run does what its headline figure needs)
+    yardstick_first = args.full and os.environ.get("XLB_BENCH_YARDSTICK", "after") == "before"
     copy_gbs = copy_yardstick() if (world == 1 and yardstick_first) else None
     xdist.barrier()  # (set-up takes the ranks unevenly long; the first exchange's bounded waits should not have to cover that)
     f_0, f_1 = stepper.run(f_0, f_1, bc_mask, missing_mask, omega, args.warmup)
@@ -435,6 +478,8 @@ def main():
     ctx.sync()
     xdist.barrier()
     elapsed = xdist.all_reduce_max(time.perf_counter() - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, f_0, grid, shape, rank, world)
     per_rank_ms = [round(v / args.steps, 4) for v in xdist.all_gather(float(dev_ms))]
     dev_ms = max(xdist.all_gather(float(dev_ms)))
     # slab runs: how long each rank's compute stream sat waiting for its halo exchange after the interior launch (a lost
@@ -442,9 +487,9 @@ def main():
     stats = ctx.comm_stats() if world > 1 else {"halo_wait_ms": 0.0, "halo_waits": 0}
     halo_wait = xdist.all_gather([round(stats["halo_wait_ms"], 3), int(stats["halo_waits"])])
 
-    if world == 1 and not yardstick_first:
+    if args.full and world == 1 and not yardstick_first:
         copy_gbs = copy_yardstick()
-    tiles_ms = pattern_copy_ms() if world == 1 and pp.store_precision.np_dtype(0).itemsize == 4 else None
+    tiles_ms = pattern_copy_ms() if args.full and world == 1 and pp.store_precision.np_dtype(0).itemsize == 4 else None
 
     cells_total = float(np.prod(shape))
     local_cells = float(max(slab_bounds(shape[0], r, world)[1] for r in range(world))) * shape[1] * shape[2]
@@ -524,7 +569,7 @@ def main():
             "kernel_source_hash": kernel_source_hash(),
         },
     }
-    if world == 1 and args.cpu_baseline_seconds > 0:
+    if args.full and world == 1 and args.cpu_baseline_seconds > 0:
         out["cpu_baseline"] = cpu_baseline(args)
     sys.stdout.flush()
     os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -42,7 +42,7 @@ def main():
     print("| configuration | kernel | ms / step | MLUPS | GB/s (algorithmic) | of 8 TB/s | of the fused ideal | copy yardstick GB/s |")
     print("|---|---|---:|---:|---:|---:|---:|---:|")
     for label, extra in ROWS:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", "10", "--cpu-baseline-seconds", "0"] + extra.split()
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", "10", "--full", "--cpu-baseline-seconds", "0"] + extra.split()
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if out.returncode != 0 or not line:
