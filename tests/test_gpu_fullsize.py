@@ -69,8 +69,8 @@ def test_cavity_512_symmetry(walls_cls):
 
 @pytest.mark.parametrize("walls_cls", [HalfwayBounceBackBC, FullwayBounceBackBC])
 def test_cavity_512_two_step_kernel_equals_single_step_kernel(walls_cls):
-    """BASELINE configs[2] at full size: 120 steps through the two-steps-per-pass kernel (hand-counted vmcnt, inline-asm
-    fix-up loads, 4096 work items) and through the single-step kernel give the SAME BITS in all 19 x 512^3 populations.
+    """BASELINE configs[2] at full size: 120 steps through the two-steps-per-pass kernel (pulls of halfway walls redirected
+    inside the pull instructions, 4096 work items) and through the single-step kernel give the SAME BITS in all 19 x 512^3 populations.
     (The small-size tests compare both kernels with the oracle; this one exercises the full-size schedule.)"""
     from xlb_amd.default_config import get_context
 

@@ -157,12 +157,7 @@ int xlbhip_create(int device, xlbhip_ctx** out) {
   c->opts["smagorinsky_coef_e6"] = 170000;  // Smagorinsky constant x 1e6 for the STAND-ALONE collision operator (0.17)
   c->opts["fuse2"] = 1;            // xlbhip_run: two steps per pass (step2_kernel.hpp): 0 never, 1 where eligible and the grid fills the chip, 2 wherever eligible
   c->opts["fuse2_xseg"] = 0;       // x segments per tile column in the two-step kernel (0 = auto: 4, fewer for short domains)
-  c->opts["fuse2_lpt"] = 1;        // two-step kernel with BCs: hull tiles first (longest-processing-time-first dispatch)
-  c->opts["fuse2_xcd"] = 1;        // compact tile patch per XCD in the two-step kernel
-  c->opts["fuse2_shift"] = 1;      // two-step kernel with BCs: tiling shifted by half a tile (both walls of an axis in ONE wrapping tile row)
-  c->opts["fuse2_xcap"] = 8;       // with fuse2_clean: planes of the thin first / last x-segment (0 = uniform cuts)
   c->opts["fuse2_clean"] = 1;      // two-step kernel with BCs: work items without boundary cells run the BC-free body (same launch)
-  c->opts["fuse2_tile"] = 0;       // tile of the two-step kernel: 0 = 8 x 64, 2 = 16 x 32 (D3Q19)
   c->opts["fuse2_cus"] = 0;        // CUs the chip-filling rule of fuse2 = 1 assumes (0 = the device's; tests of the rule)
   c->opts["fuse2_strips"] = 1;     // two-step kernel (D3Q19): halo columns of phase A from the fields' strip buffers (step2_kernel.hpp): 0 never,
                                    // 1 = for steppers with boundary conditions (where they pay), 2 = always
@@ -1027,19 +1022,19 @@ struct xlbhip_stepper {
   const xlbhip_field* scan_field = nullptr;
   uint64_t scan_version = 0;
   int scan_flag = 1;
-  uint32_t* tile_order = nullptr;  // two-step kernel: block -> (8 x 64) tile, hull tiles first
-  int order_ty = 0, order_tz = 0, order_mode = -1;
+  uint32_t* tile_order = nullptr;  // two-step kernel: block -> tile, hull tiles first (step2_tile_order)
+  int order_ty = 0, order_tz = 0;
   uint32_t* meta = nullptr;  // two-step kernel: id | missing << 8, rebuilt by every xlbhip_run that fuses
   size_t meta_cells = 0;
-  // two-step kernel: per launch geometry (x_begin, x_count, segments, tile order?, swizzle) the per-block "no boundary
-  // cell" flags; dropped whenever the meta words are rebuilt
-  std::map<std::array<int, 8>, uint8_t*> clean_cache;
+  // two-step kernel: per launch geometry (x_begin, x_count, segments) the per-block "no boundary cell" flags; dropped
+  // whenever the meta words or the tile order are rebuilt
+  std::map<std::array<int, 3>, uint8_t*> clean_cache;
   // the masks (address + contents version) the meta words were built from: xlbhip_step2 called per pair (the Python
   // stepper pairing reference-style calls) must not rebuild them every time
   const xlbhip_field* meta_bc = nullptr;
   const xlbhip_field* meta_miss = nullptr;
   uint64_t meta_bc_version = 0, meta_miss_version = 0;
-  unsigned long long meta_opts = 0;
+  bool meta_external_halo = false;
   bool forced = false;
   double force[3] = {0, 0, 0};
   double smag_cs = 0.17;
@@ -1097,23 +1092,6 @@ static int check_step_fields(const xlbhip_stepper* s, const xlbhip_field* a, con
   return 0;
 }
 
-// tile of the two-step kernel: (8 x 64); the (16 x 32) form (fuse2_tile = 2) exists in -DXLB_TUNE_VARIANTS builds only
-static int fuse2_tile_ty(const xlbhip_ctx* c) {
-#ifdef XLB_TUNE_VARIANTS
-  if (opt(c, "fuse2_tile", 0) == 2) return 16;
-  if (opt(c, "fuse2_tile", 0) == 4) return 4;
-#endif
-  (void)c;
-  return 8;
-}
-static int fuse2_tile_tz(const xlbhip_ctx* c) {
-#ifdef XLB_TUNE_VARIANTS
-  if (opt(c, "fuse2_tile", 0) == 2 || opt(c, "fuse2_tile", 0) == 3) return 32;
-#endif
-  (void)c;
-  return 64;
-}
-
 static StepLaunch make_launch(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
                               double omega) {
   xlbhip_ctx* c = s->ctx;
@@ -1131,12 +1109,9 @@ static StepLaunch make_launch(xlbhip_stepper* s, const xlbhip_field* src, xlbhip
   p.x_segments = 1;
   p.x_cap = 0;
   p.tile_oy = p.tile_oz = 0;
-  p.tile_ty = fuse2_tile_ty(c);
-  p.tile_tz = fuse2_tile_tz(c);
-  // D3Q27 KBC: (8 x 48) tiles — 8 waves per block, i.e. 2 per SIMD and 256 VGPRs for the collision (the (8 x 64) tile's 11 waves
-  // leave 168: 3.8 KB of scratch in fp64); the grown tile is 500 cells for 384 outputs, the same ratio as (8 x 64)
-  // D3Q27 BGK with boundary conditions (round 3): the BC ring — 63 population-planes — fits the LDS on the same (8 x 48) tile: 126 KB
-  if (s->lattice == XLBHIP_D3Q27 && (s->collision == XLBHIP_KBC || (s->n_bc > 0 && bcm))) p.tile_tz = 48;
+  const Step2Tile tile = step2_tile(s->lattice, s->collision, p.bc != nullptr);
+  p.tile_ty = tile.ty;
+  p.tile_tz = tile.tz;
   p.tab_kind = s->tab_kind;
   p.ids_packed = s->ids_packed;
   p.kinds_packed = s->kinds_packed;
@@ -1175,39 +1150,20 @@ static StepLaunch make_launch(xlbhip_stepper* s, const xlbhip_field* src, xlbhip
   return p;
 }
 
-// x segments per tile column of the two-step kernel.  One block per CU marches a segment, so the launch runs in
-// ceil(tiles * n / CUs) rounds of (planes per segment + 3 warm-up planes): pick the n that minimises that product
-// (320^3: 4 -> 8 segments = 3.1 -> 6.25 rounds, -9 %; 256^3: 2 segments = exactly one round).  With halfway walls the
-// hull tiles are the expensive ones and finer items balance them better: take the most segments of >= 32 planes
-// (measured at 256^3 ... 512^3: profiles/r01/sweeps.md).
+// the inputs of the two-step plan (step2_plan.hpp)
+static Step2Case plan_case(const xlbhip_stepper* s, const StepLaunch& p) {
+  return {s->lattice, s->collision, p.compute_dtype, p.store_dtype, p.fast_math, p.nx, p.ny, p.nz, p.halo,
+          p.has_bc, p.edge_ext, p.n_bc, p.kinds_packed, s->needs_missing ? 1 : 0};
+}
+
+// CUs the work items of the two-step kernel are to fill
 static long fill_cus(const xlbhip_ctx* c) {
   const int64_t o = opt(c, "fuse2_cus", 0);
   return o > 0 ? (long)o : (c->compute_units > 0 ? c->compute_units : 256);
 }
 
 static int fuse2_segments(const xlbhip_stepper* s, const StepLaunch& p) {
-  const int64_t xseg = opt(s->ctx, "fuse2_xseg", 0);
-  if (xseg > 0) {
-    int n = (int)xseg;
-    while (n > 1 && p.x_count / n < 8) n /= 2;
-    return n;
-  }
-  const long tiles = (long)(p.ny / p.tile_ty) * (p.nz / p.tile_tz), cus = fill_cus(s->ctx);
-  // with boundary conditions finer items win twice: the expensive hull tiles balance better (halfway walls), and work
-  // items free of boundary cells — most segments of an interior tile column — run the BC-free body (fuse2_clean):
-  // take the most segments of >= 32 planes (measured at 256^3 ... 512^3: profiles/r01/sweeps.md, profiles/r02/step2_sweeps.txt)
-  const bool finest = s->needs_missing || (p.has_bc && opt(s->ctx, "fuse2_clean", 1));
-  int best = 1;
-  long best_cost = -1;
-  for (int n = 1; n <= 8; n *= 2) {
-    if (n > 1 && p.x_count / n < 32) break;
-    const long cost = ((tiles * n + cus - 1) / cus) * (p.x_count / n + 3);
-    if (best_cost < 0 || cost < best_cost || finest) {
-      best = n;
-      best_cost = cost;
-    }
-  }
-  return best;
+  return step2_segments(plan_case(s, p), p.x_count, fill_cus(s->ctx), (int)opt(s->ctx, "fuse2_xseg", 0), opt(s->ctx, "fuse2_clean", 1) != 0);
 }
 
 // assemble_auxiliary_data of the ExtrapolationOutflowBC cells after a step src -> dst (nse_stepper.py:270-272)
@@ -1238,9 +1194,9 @@ static int launch_step2(xlbhip_stepper* s, StepLaunch p) {
   if (s->lattice == XLBHIP_D3Q27 && s->collision == XLBHIP_KBC) return launch_step2_d3q27_kbc(p);
   p.clean = nullptr;
   if (p.has_bc && p.meta && opt(s->ctx, "fuse2_clean", 1)) {
-    // everything the block -> (tile, x-segment) mapping depends on: the flags say "no boundary cell in THIS block's item"
-    const std::array<int, 8> key = {p.x_begin, p.x_count, p.x_segments * 64 + p.x_cap, (p.tile_order ? 1 : 0) + 2 * p.tile_oy + 1024 * p.tile_oz,
-                                    p.xcd_swizzle, p.tile_order ? s->order_mode : -1, p.tile_ty, p.tile_tz};
+    // what the block -> (tile, x-segment) mapping depends on and may differ between the launches of one stepper (tile, shift and
+    // order are the stepper's; x_cap follows fuse2_clean): the flags say "no boundary cell in THIS block's item"
+    const std::array<int, 3> key = {p.x_begin, p.x_count, p.x_segments};
     auto it = s->clean_cache.find(key);
     if (it == s->clean_cache.end()) {
       uint8_t* flags = nullptr;
@@ -1337,18 +1293,17 @@ static int step_twice(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* 
                       double omega) {
   StepLaunch p = make_launch(s, src, dst, bcm, miss, omega);
   p.meta = s->meta;
-  // hull tiles first only pays when they are much more expensive than fluid tiles (halfway walls: redirected
-  // loads); with fullway / equilibrium boundaries the XCD-compact order is faster (fuse2_lpt: 0 never, 1 auto, 2 always)
-  const int64_t lpt = opt(s->ctx, "fuse2_lpt", 1);
+  // hull tiles first pays when they are much more expensive than fluid tiles (halfway walls: redirected loads) and
+  // with clean work items; otherwise (fullway / equilibrium boundaries alone) the XCD-compact patch is faster
   const bool clean_on = p.has_bc && opt(s->ctx, "fuse2_clean", 1) != 0;
-  p.tile_order = (p.has_bc && (lpt >= 2 || (lpt == 1 && (s->needs_missing || clean_on)))) ? s->tile_order : nullptr;
+  p.tile_order = (p.has_bc && (s->needs_missing || clean_on)) ? s->tile_order : nullptr;
   p.x_segments = fuse2_segments(s, p);
-  p.x_cap = clean_on ? (int)opt(s->ctx, "fuse2_xcap", 8) : 0;
-  if (p.has_bc && opt(s->ctx, "fuse2_shift", 1)) {  // half-tile shift: both walls of an axis in one (wrapping) tile row
+  p.x_cap = clean_on ? 8 : 0;  // thin first / last x-segments: with walls on the x faces the inner segments are free of them
+  if (p.has_bc) {  // half-tile shift: both walls of an axis in one (wrapping) tile row
     p.tile_oy = p.tile_ty / 2;
     p.tile_oz = p.tile_tz / 2;
   }
-  p.xcd_swizzle = (int)opt(s->ctx, "fuse2_xcd", 1);
+  p.xcd_swizzle = 1;
   xlbhip_ctx* c = s->ctx;
   p.strips = 0;
   p.strips_src = nullptr;
@@ -1469,35 +1424,8 @@ static bool can_fuse2(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* 
     }
     s->edge_ext_ok = true;
   }
-  StepLaunch p = make_launch(s, src, dst, bcm, miss, 1.0);
-  if (!step2_eligible(p, s->lattice, s->collision)) return false;
-  if (mode == 1) {
-    // D3Q27 KBC pairs on request only (fuse2 = 2): ~1100 (fp32) / 810 (fast fp64) VALU instructions per cell and 8 waves per CU make
-    // the two-step form issue-bound — 384^3: 2.41 (FP64FP32) / 2.52 (FP32FP32) ms per step against 2.21 / 2.16 of the HBM-bound
-    // single-step kernel (profiles/r02/d3q27_kbc_two_step.txt)
-    // Round 3: the gamma reduction in fp32 (cell.hpp COLL_G32) speeds the fp64 / fp32-store pairs up by 5.6 % — and single steps by 3.1 % —
-    // on a non-trivial state: pairs 2.28 against 2.23 ms per step at 384^3, still behind (profiles/r03/kbc_gamma32.md; on a uniform
-    // f = w the pairs look 3 % FASTER than single steps: identical operands in every lane, higher clocks — not a state to time on).
-    if (s->lattice == XLBHIP_D3Q27 && s->collision == XLBHIP_KBC) return false;
-    // D3Q27 BGK with boundary conditions (round 3, (8 x 48) tiles, 192 VGPRs): bit-exact, but 2.59-3.16 against 2.15-2.19 ms per step on
-    // the 384^3 cavity (0.48-0.59 against 0.70-0.71 of the roofline, profiles/r03/d3q27_walls_two_step.md): on request only
-    if (s->lattice == XLBHIP_D3Q27 && s->collision == XLBHIP_BGK && p.has_bc) return false;
-    // one block per CU marches an (8 x 64) tile column segment: the work items must fill the chip in whole
-    // rounds (128^3 = 32 tiles x 4 segments would leave half of the 256 CUs idle)
-    const long items = (long)(p.ny / p.tile_ty) * (p.nz / p.tile_tz) * fuse2_segments(s, p), cus = fill_cus(s->ctx);
-    const long rounds = (items + cus - 1) / cus;
-    if (items * 100 < rounds * cus * 85) return false;
-    // halfway walls make the hull tiles ~1.5x as expensive as fluid tiles; when most tiles are hull tiles two single
-    // steps are faster (256^3, 53 % hull tiles: fused 41.7 vs 38.2 GLUPS; thinner domains lose)
-    if (s->needs_missing) {
-      const long tys = p.ny / p.tile_ty, tzs = p.nz / p.tile_tz;
-      // (with the half-tile shift both walls of an axis share one tile row: tys + tzs - 1 hull tiles)
-      const long hull = opt(s->ctx, "fuse2_shift", 1) ? std::min(tys * tzs, tys + tzs - 1)
-                                                      : tys * tzs - (tys > 2 ? tys - 2 : 0) * (tzs > 2 ? tzs - 2 : 0);
-      if (hull * 100 > tys * tzs * 60) return false;
-    }
-  }
-  return true;
+  const StepLaunch p = make_launch(s, src, dst, bcm, miss, 1.0);
+  return step2_fuse(plan_case(s, p), (int)mode, fill_cus(s->ctx), (int)opt(s->ctx, "fuse2_xseg", 0), opt(s->ctx, "fuse2_clean", 1) != 0);
 }
 
 // per-run tables of the two-step kernel: the meta words (bc kind | slot | missing bits per cell, ghost planes
@@ -1516,64 +1444,10 @@ static int prepare_fuse2(xlbhip_stepper* s, const xlbhip_field* bcm, const xlbhi
     s->meta_cells = cells;
     s->meta_bc = nullptr;  // (contents gone: rebuild below)
   }
-  // (the tile of THIS stepper: make_launch — D3Q27 with boundary conditions marches (8 x 48) tiles)
-  const int tile_tz = s->lattice == XLBHIP_D3Q27 ? 48 : fuse2_tile_tz(c);
-  const int tys = bcm->ny / fuse2_tile_ty(c), tzs = bcm->nz / tile_tz;
-  const bool shifted = opt(c, "fuse2_shift", 1) != 0;
-  const int order_mode = (opt(c, "fuse2_lpt", 1) == 3 ? 3 : 0) + (shifted ? 8 : 0);
-  if (s->order_ty != tys || s->order_tz != tzs || s->order_mode != order_mode) {
-    s->order_mode = order_mode;
-    // hull tiles first (the expensive ones when there are walls), then the interior; both lists are dealt so that every
-    // XCD (block i runs on XCD i % 8) works on a CONTIGUOUS run of tiles — neighbours share their halo rows / lines
-    // through that XCD's L2 (fuse2_lpt = 3: the hull in row-major order as in round 1, for A/B)
-    std::vector<uint32_t> hull, inner;
-    if (shifted) {
-      // half-tile shift: the walls of the y / z faces sit in the LAST tile row / column (the ones that wrap around)
-      for (int tz = 0; tz < tzs; ++tz) hull.push_back((uint32_t)((tys - 1) * tzs + tz));
-      for (int ty = tys - 2; ty >= 0; --ty) hull.push_back((uint32_t)(ty * tzs + tzs - 1));
-      for (int ty = 0; ty < tys - 1; ++ty)
-        for (int tz = 0; tz < tzs - 1; ++tz) inner.push_back((uint32_t)(ty * tzs + tz));
-    } else if (opt(c, "fuse2_lpt", 1) == 3) {
-      for (int ty = 0; ty < tys; ++ty)
-        for (int tz = 0; tz < tzs; ++tz)
-          if (ty == 0 || ty == tys - 1 || tz == 0 || tz == tzs - 1) hull.push_back((uint32_t)(ty * tzs + tz));
-    } else {
-      // walk around the perimeter: consecutive entries are adjacent tiles
-      for (int tz = 0; tz < tzs; ++tz) hull.push_back((uint32_t)tz);
-      for (int ty = 1; ty < tys - 1; ++ty)
-        if (tzs > 1) hull.push_back((uint32_t)(ty * tzs + tzs - 1));
-      if (tys > 1)
-        for (int tz = tzs - 1; tz >= 0; --tz) hull.push_back((uint32_t)((tys - 1) * tzs + tz));
-      for (int ty = tys - 2; ty >= 1; --ty) hull.push_back((uint32_t)(ty * tzs));
-    }
-    if (!shifted)
-      for (int ty = 1; ty < tys - 1; ++ty)
-        for (int tz = 1; tz < tzs - 1; ++tz) inner.push_back((uint32_t)(ty * tzs + tz));
-    std::vector<uint32_t> order;
-    order.reserve((size_t)tys * tzs);
-    auto deal = [&](const std::vector<uint32_t>& list, bool chunked) {
-      const size_t n = list.size(), per = (n + 7) / 8;
-      if (!chunked) {
-        order.insert(order.end(), list.begin(), list.end());
-        return;
-      }
-      // chunk k = list[k * per ...]; the slot being filled decides the XCD (slot % 8) and takes the next tile of that
-      // XCD's chunk (of the fullest chunk once its own is used up)
-      size_t cur[8], end[8];
-      for (size_t k = 0; k < 8; ++k) {
-        cur[k] = std::min(n, k * per);
-        end[k] = std::min(n, (k + 1) * per);
-      }
-      for (size_t done = 0; done < n; ++done) {
-        size_t k = order.size() % 8;
-        if (cur[k] == end[k])
-          for (size_t m = 0; m < 8; ++m)
-            if (end[m] - cur[m] > end[k] - cur[k]) k = m;
-        order.push_back(list[cur[k]++]);
-      }
-    };
-    deal(hull, opt(c, "fuse2_lpt", 1) != 3);
-    deal(inner, true);
+  const Step2Tile tile = step2_tile(s->lattice, s->collision, true);
+  const int tys = bcm->ny / tile.ty, tzs = bcm->nz / tile.tz;
+  if (s->order_ty != tys || s->order_tz != tzs) {
+    const std::vector<uint32_t> order = step2_tile_order(tys, tzs);
     drop_clean_cache(s);  // the flags were computed for the old block -> tile mapping
     if (s->tile_order) XLB_HIP(hipFree(s->tile_order));
     s->tile_order = nullptr;
@@ -1582,15 +1456,15 @@ static int prepare_fuse2(xlbhip_stepper* s, const xlbhip_field* bcm, const xlbhi
     s->order_ty = tys;
     s->order_tz = tzs;
   }
-  const unsigned long long opts_key = (unsigned long long)opt(c, "fuse2_shift", 1) | ((unsigned long long)opt(c, "external_halo", 0) << 1);
+  const bool external_halo = opt(c, "external_halo", 0) != 0;
   if (s->meta_bc == bcm && s->meta_miss == miss && s->meta_bc_version == bcm->version && s->meta_miss_version == (miss ? miss->version : 0) &&
-      s->meta_opts == opts_key)
+      s->meta_external_halo == external_halo)
     return 0;  // meta words, tile order and clean flags are those of these very masks
   s->meta_bc = bcm;
   s->meta_miss = miss;
   s->meta_bc_version = bcm->version;
   s->meta_miss_version = miss ? miss->version : 0;
-  s->meta_opts = opts_key;
+  s->meta_external_halo = external_halo;
   drop_clean_cache(s);  // (stream-ordered: the flags' last readers were enqueued before this point and hipFree synchronises)
   hipLaunchKernelGGL(k_build_meta, blocks_for(cells), 256, 0, c->stream, static_cast<const uint8_t*>(bcm->data),
                      miss ? static_cast<const uint32_t*>(miss->data) : nullptr, s->meta, cells, s->ids_packed, s->kinds_packed,

@@ -12,7 +12,7 @@
 // 2 + 2.  Arithmetic is the same per-cell code (cell.hpp) in the same order, so the result is
 // bit-identical to two single steps (tests/test_gpu_stepper.py::test_two_step_fusion_*).
 //
-// Restrictions (the launcher falls back to the single-step kernel otherwise — step2_eligible): fp32 store (f(t+1) sits in LDS in the
+// Restrictions (the launcher falls back to the single-step kernel otherwise — step2_plan.hpp: step2_eligible): fp32 store (f(t+1) sits in LDS in the
 // store type); D3Q19 BGK fp32 with basic boundary conditions, D3Q27 BGK fp32 and (on request) KBC fp32 / fast fp64 without them;
 // ny % TY == 0, nz % TZ == 0; fields without ghost planes (x wraps here) or — D3Q19 — with
 // TWO ghost planes per side (slab decomposition: phase A also computes f(t+1) on the ghost planes -1 and nx from
@@ -20,53 +20,14 @@
 #pragma once
 #include "step_kernel.hpp"
 
-#ifndef XLB_STEP2_ALIGN
-#define XLB_STEP2_ALIGN 256
-#endif
-#ifndef XLB_PIN_CLEAN
-#define XLB_PIN_CLEAN true
-#endif
-#ifndef XLB_PIN_BC
-#define XLB_PIN_BC true
-#endif
-#ifndef XLB_STEP2_SLACK
-#define XLB_STEP2_SLACK 1  // the clean work items of a BC kernel run on the slack ring (one barrier per plane): cavity 512^3 -3.5 %
-#endif
-#ifndef XLB_STEP2_SLACK_PLAIN
-#define XLB_STEP2_SLACK_PLAIN 0  // ... the kernel without boundary conditions does not: periodic 512^3 +3.5 % with it (profiles/r02/step2_sweeps.txt)
-#endif
-#ifndef XLB_STEP2_ROWMAP
-#define XLB_STEP2_ROWMAP 0
-#endif
-#ifndef XLB_STEP2_ROWMAP_PLAIN
-#define XLB_STEP2_ROWMAP_PLAIN 1
-#endif
-#ifndef XLB_STEP2_ROWMAP_CLEAN
-#define XLB_STEP2_ROWMAP_CLEAN 0  // the BC-free body of the clean work items inside a BC kernel (slack ring): measurement builds
-#endif
-#ifndef XLB_STEP2_STAGE
-#define XLB_STEP2_STAGE 0
-#endif
-#ifndef XLB_STEP2_MAX_BLOCKS
-#define XLB_STEP2_MAX_BLOCKS 2
-#endif
-#ifndef XLB_STEP2_PLAIN_GMAX
-#define XLB_STEP2_PLAIN_GMAX 1  // pair-group width of the kernel without boundary conditions
-#endif
-#ifndef XLB_STEP2_CLEAN_GMAX
-#define XLB_STEP2_CLEAN_GMAX 3  // pair-group width of the BC-free body inside the BC kernel (1 makes hipcc park the pairs in scratch there)
-#endif
-
 namespace xlb {
 
 // -DXLB_STEP2_TRACE=1|2 (tools/step2_phase_trace.py, never in the shipped build): shader-clock stamps of the steady-state loop's phases,
 // per wave, for one block and a few planes.  2 additionally drains vmcnt at the top of finish_a, which separates "waiting for the pulls"
 // from the collision (and perturbs the pipeline: the stores drain too).
 #ifdef XLB_STEP2_TRACE
-#ifndef XLB_STEP2_TRACE_BLOCK
-#define XLB_STEP2_TRACE_BLOCK 300  // (cavity 512^3, 8 x-segments of 512 tile columns, hull tiles first: 522 = a hull tile's second segment, 812 = a clean item)
-#endif
-constexpr int TRACE_PLANES = 6, TRACE_EVENTS = 8, TRACE_WAVES = 11, TRACE_FIRST = 40, TRACE_BLOCK = XLB_STEP2_TRACE_BLOCK;
+// TRACE_BLOCK: the block stamped (cavity 512^3, 8 x-segments of 512 tile columns, hull tiles first: 522 = a hull tile's second segment, 812 = a clean item)
+constexpr int TRACE_PLANES = 6, TRACE_EVENTS = 8, TRACE_WAVES = 11, TRACE_FIRST = 40, TRACE_BLOCK = 300;
 static __device__ unsigned long long g_step2_trace[TRACE_PLANES * TRACE_WAVES * TRACE_EVENTS];
 __device__ __forceinline__ void trace_stamp(int d, int e) {
   __builtin_amdgcn_sched_barrier(0);
@@ -104,16 +65,14 @@ constexpr int nth_cz(int cz, int k) {  // k-th population (index order) with c_z
 // populations of plane x — every group must still be there then, so the c_x = -1 group gets a second buffer (43 / 63).
 // (Serving those reads by letting phase A pre-write the value into the entry phase B pulls from was built and dropped:
 // two adjacent solid cells need two different values in the same entry.)
-// PACKED = false keeps three whole planes ([plane % 3][population][cell], round 1's layout).  With pointer-per-buffer addressing the two
-// forms run alike for D3Q19 (periodic 512^3 2.28 vs 2.29-2.32 ms/step, cavity 2.40-2.42 vs 2.41-2.44: profiles/r02/step2_sweeps.txt); the
-// packed one is the default because D3Q27 needs it and the room it leaves pays for the slack ring of the clean work items.
+// (Round 1's three whole planes per population: measured and removed, profiles/r02/step2_sweeps.txt.)
 // SLACK: one more buffer per population, so that phase A of plane x + 2 may WRITE while phase B of plane x still READS (no buffer
 // phase B(x) reads — planes x - 1 / x / x + 1 of the c_x = +1 / 0 / -1 groups — is the one that receives plane x + 2): the barrier
 // between the two phases goes away, every wave runs its phase B and its phase A back to back and the waves without output cells
 // (3 of 11) start phase A at once.  2 + 3 + 4 buffers: D3Q19 5 x 2 + 9 x 3 + 5 x 4 = 57 population-planes again.
-template <class L, int HASBC, bool PACKED, bool SLACK = false>
+template <class L, int HASBC, bool SLACK = false>
 struct S2Ring {
-  static_assert(!SLACK || (PACKED && HASBC == 0), "the slack ring is the lifetime-packed one, BC-free body");
+  static_assert(!SLACK || HASBC == 0, "the slack ring is the BC-free body's");
   // layout: group-major — [c_x = -1 group: life x n_m planes][c_x = 0: 2 x n_z][c_x = +1: 3 x n_p], a plane buffer of a
   // group is contiguous, so that one VGPR base per group + an immediate offset per population addresses everything
   static constexpr int group(int l) { return L::c(0, l) + 1; }  // 0: c_x = -1, 1: c_x = 0, 2: c_x = +1
@@ -127,7 +86,7 @@ struct S2Ring {
     for (int m = 0; m < l; ++m) n += group(m) == group(l) ? 1 : 0;
     return n;
   }
-  static constexpr int glife(int g) { return !PACKED ? 3 : (g == 0 ? (HASBC != 0 ? 2 : 1) : (g == 1 ? 2 : 3)) + (SLACK ? 1 : 0); }
+  static constexpr int glife(int g) { return (g == 0 ? (HASBC != 0 ? 2 : 1) : (g == 1 ? 2 : 3)) + (SLACK ? 1 : 0); }
   // buffer of plane q (counted from x_lo - 1) in a group of `life` buffers
   template <int life>
   static __device__ __forceinline__ int buf(int q) {
@@ -143,32 +102,24 @@ struct S2Ring {
 };
 
 // tile geometry of one instantiation
-template <class L, int HASBC, int TY, int TZ, bool PACKED>
+template <class L, int HASBC, int TY, int TZ>
 struct S2Geom {
   static constexpr int EY = TY + 2, EZ = TZ + 2;
   static constexpr int NE = EY * EZ;                     // cells of f(t+1) per plane slot (grown tile)
   static constexpr int NB = TY * TZ;                     // output cells per plane
   static constexpr int THREADS = (NE + 63) / 64 * 64;    // whole waves covering the grown tile
-  // STAGE: phase B hands its results to the memory pipeline as 16-byte stores — each wave writes the 19 values of its 64 cells (one z
-  // row of the tile) to a wave-private LDS area and reads them back four cells of one population per lane: 5 store instructions per
-  // wave and plane instead of 19 (the vector-memory pipeline is paid per instruction).  Needs the packed ring's room: 19 x 64 x 4 B per wave.
   static constexpr int EXTRA_BYTES = HASBC != 0 ? 3 * NE * 4 + 1024 : 8;  // meta words + BC constants
-  // the BC-free body (the whole kernel, or the clean work items of a BC kernel) runs on the slack ring where that fits the LDS
-  static constexpr int PLANES_BC = S2Ring<L, HASBC, PACKED>::PLANES;
-  static constexpr int PLANES_SLACK = S2Ring<L, 0, true, true>::PLANES;
-  static constexpr bool SLACK = XLB_STEP2_SLACK != 0 && PACKED && PLANES_SLACK * NE * 4 + EXTRA_BYTES <= 160 * 1024;
-  static constexpr bool SLACK_USED = SLACK && (HASBC != 0 || XLB_STEP2_SLACK_PLAIN != 0);
-  static constexpr int RING_PLANES = SLACK_USED && PLANES_SLACK > PLANES_BC ? PLANES_SLACK : PLANES_BC;
-  static constexpr bool STAGE = XLB_STEP2_STAGE != 0 && PACKED && TZ == 64 &&
-                                RING_PLANES * NE * 4 + NB * L::Q * 4 + EXTRA_BYTES <= 160 * 1024;  // (D3Q27: no room)
-  static constexpr int STAGE_ELEMS = STAGE ? (NB / 64) * L::Q * 64 : 0;
-  static constexpr int N_STORES = STAGE ? (L::Q + 3) / 4 : L::Q;  // vector-memory stores per phase-B thread and plane
-  static constexpr int LDS_BYTES = RING_PLANES * NE * 4 + STAGE_ELEMS * 4 + EXTRA_BYTES;  // ring + staging + meta words + BC constants
+  // The clean work items of a BC kernel run on the slack ring (one barrier per plane: cavity 512^3 -3.5 %) where that fits the LDS;
+  // the kernel without boundary conditions keeps two barriers (the slack ring there: periodic 512^3 +3.5 %, measured and removed:
+  // profiles/r02/step2_sweeps.txt)
+  static constexpr int PLANES_BC = S2Ring<L, HASBC>::PLANES;
+  static constexpr int PLANES_SLACK = S2Ring<L, 0, true>::PLANES;
+  static constexpr bool SLACK = PLANES_SLACK * NE * 4 + EXTRA_BYTES <= 160 * 1024;
+  static constexpr int RING_PLANES = SLACK && HASBC != 0 && PLANES_SLACK > PLANES_BC ? PLANES_SLACK : PLANES_BC;
+  static constexpr int LDS_BYTES = RING_PLANES * NE * 4 + EXTRA_BYTES;  // ring + meta words + BC constants
   static_assert(LDS_BYTES <= 160 * 1024, "tile does not fit the LDS");
-  // blocks per CU the LDS admits (one for every tile built by default; XLB_STEP2_MAX_BLOCKS bounds the tuning variants)
-  // -> waves per SIMD the register allocation must admit
-  static constexpr int BLOCKS_PER_CU = (160 * 1024) / LDS_BYTES < XLB_STEP2_MAX_BLOCKS ? (160 * 1024) / LDS_BYTES : XLB_STEP2_MAX_BLOCKS;
-  static constexpr int WAVES_PER_SIMD = (BLOCKS_PER_CU * (THREADS / 64) + 3) / 4;
+  static_assert(2 * LDS_BYTES > 160 * 1024, "the launch bounds assume one block per CU");
+  static constexpr int WAVES_PER_SIMD = (THREADS / 64 + 3) / 4;  // waves per SIMD the register allocation must admit
 };
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt(0), i.e. every
@@ -241,20 +192,14 @@ __device__ __forceinline__ void step2_seg_range(int x_begin, int x_count, int n_
 // run either boundary-condition form of the body in the same allocation).
 // STRIPS (D3Q19 / (TY x 64) tiles): bit 0 = phase A reads the halo columns of its grown tile from the source field's STRIP buffer,
 // bit 1 = phase B also writes the destination field's strips.  See "Strip buffers" below.
-template <class L, class T, class S, int COLL, int HASBC, int TY, int TZ, bool SLAB, bool PACKED, int GMAX, bool PIN, bool FAST, bool SLACK = false, int STRIPS = 0>
+template <class L, class T, class S, int COLL, int HASBC, int TY, int TZ, bool SLAB, int GMAX, bool PIN, bool FAST, bool SLACK = false, int STRIPS = 0>
 __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsigned* ldsmeta, T* bcval, S* strip_stage = nullptr) {
-  using G = S2Geom<L, HASBC, TY, TZ, PACKED>;
-  using R = S2Ring<L, HASBC, PACKED, SLACK>;
+  using G = S2Geom<L, HASBC, TY, TZ>;
+  using R = S2Ring<L, HASBC, SLACK>;
   using M = S2Meta<L>;
   constexpr int Q = L::Q, NE = G::NE, EZ = G::EZ;
   constexpr unsigned ES = sizeof(S);
-#if defined(XLB_STRIPS_NOREAD)  // measurement builds (tools/r03_call4.sh): one half of the mechanism at a time
-  constexpr bool SR = false, SW = (STRIPS & 2) != 0;
-#elif defined(XLB_STRIPS_NOWRITE)
-  constexpr bool SR = (STRIPS & 1) != 0, SW = false;
-#else
   constexpr bool SR = (STRIPS & 1) != 0, SW = (STRIPS & 2) != 0;
-#endif
   static_assert(STRIPS == 0 || STRIPS == 2 || STRIPS == 3 || STRIPS == 4, "STRIPS: 0, 2 (write), 3 (read + write) or 4 (row-aligned lanes only)");
   static_assert(STRIPS == 0 || (TZ == 64 && sizeof(S) == 4), "strip buffers: (TY x 64) tiles, 4-byte store type");
   // f(t+1) lives in LDS in the STORE type: the single-step kernel rounds it to that type on its way through memory, so the
@@ -263,12 +208,8 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
   // first cell of the buffer that holds population l of plane q (q counted from x_lo - 1; uniform)
   auto ring = [&](auto lc, int q) __attribute__((always_inline)) -> int {
     constexpr int l = decltype(lc)::value;
-    if constexpr (!PACKED) {
-      return (q % 3) * (Q * NE) + l * NE;
-    } else {
-      constexpr int g = R::group(l), life = R::glife(g);
-      return (R::gbase(g) + R::template buf<life>(q) * R::gcount(g)) * NE + R::gidx(l) * NE;
-    }
+    constexpr int g = R::group(l), life = R::glife(g);
+    return (R::gbase(g) + R::template buf<life>(q) * R::gcount(g)) * NE + R::gidx(l) * NE;
   };
 
   // tile of this block: from the launch's order table when there is one (hull tiles first — with boundary
@@ -315,11 +256,10 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
   const int ta = act_a ? t : NE - 1;
   // row-aligned lanes ((TY x 64) tiles): wave j < EY pulls the 64 interior cells of grown row j (for c_z = 0 one aligned 256-byte
   // piece per pull instead of the tail of one row + the head of the next), the last wave the two halo columns of all rows
-  // Row-aligned lanes are the default of the stand-alone BC-free kernel (two barriers per plane): periodic 512^3 2.28 -> 2.11-2.16
+  // Row-aligned lanes are the mapping of the stand-alone BC-free kernel (two barriers per plane): periodic 512^3 2.28 -> 2.11-2.16
   // ms/step in round 3's A/B (round 2 measured -2...3 %); the bodies of the BC kernel lose 0-3 % with it and keep the dense mapping.
   // (STRIPS & 4: row-aligned lanes for this body WITHOUT strip buffers — the run-time A/B of api.hip's "fuse2_rowmap" option)
-  constexpr bool ROWMAP = (XLB_STEP2_ROWMAP != 0 || SR || (STRIPS & 4) != 0 || (XLB_STEP2_ROWMAP_PLAIN != 0 && HASBC == 0 && !SLACK) ||
-                           (XLB_STEP2_ROWMAP_CLEAN != 0 && HASBC == 0 && SLACK)) && TZ == 64;
+  constexpr bool ROWMAP = (SR || (STRIPS & 4) != 0 || (HASBC == 0 && !SLACK)) && TZ == 64;
   // strip buffers: the last wave holds the 2 x EY halo-column cells of the grown tile (ROWMAP) and pulls for them from the
   // strips — the same instructions as every other wave, with the strip buffer's geometry in place of the field's
   const bool halo_wave = SR && __builtin_amdgcn_readfirstlane(t) >= G::EY * 64;
@@ -349,32 +289,6 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
       Zb[0] = Zb[1] = Zb[2] = zoff;
     }
   }
-#if defined(XLB_STEP2_WHATIF) && XLB_STEP2_WHATIF != 0
-  // MEASUREMENT ONLY (wrong results; never in the shipped build — tools/r03_whatif.sh): what would phase A's pulls cost if the
-  // halo columns (bit 0) / halo rows (bit 1) of the grown tile came for free?  Sources outside the tile proper are clamped onto
-  // its edge cells, so a block touches no sector that belongs to a neighbouring tile: the upper bound of what compact strip
-  // buffers (bit 0) or perfect L2 sharing between neighbouring tiles (bits 0 + 1) could save.
-  {
-    auto zsrc = [&](int cz) {
-      int kk = ka - cz;  // grown z index of the source: -1 .. TZ + 2; the tile proper is 1 .. TZ
-      if (XLB_STEP2_WHATIF & 1) kk = kk < 1 ? 1 : (kk > TZ ? TZ : kk);
-      int z = tz0 - 1 + kk;
-      z = z < 0 ? z + nz : (z >= nz ? z - nz : z);
-      return (unsigned)z * ES;
-    };
-    auto ysrc = [&](int cy) {
-      int jj = ja - cy;
-      if (XLB_STEP2_WHATIF & 2) jj = jj < 1 ? 1 : (jj > TY ? TY : jj);
-      int y = ty0 - 1 + jj;
-      y = y < 0 ? y + ny : (y >= ny ? y - ny : y);
-      return (unsigned)y * (unsigned)nz * ES;
-    };
-    for (int c = -1; c <= 1; ++c) {
-      Zb[c + 1] = zsrc(c);
-      Yb[c + 1] = ysrc(c);
-    }
-  }
-#endif
   const unsigned cell_a = (unsigned)ya * (unsigned)nz + (unsigned)za;
 
   // ---- phase-B cell of this thread (tile proper); waves beyond the tile shadow a valid cell ----
@@ -386,19 +300,6 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
   zb = zb >= nz ? zb - nz : zb;
   const unsigned cell_b = (unsigned)yb * (unsigned)nz + (unsigned)zb;
   const int ctr_b = (jb + 1) * EZ + (kb + 1);  // my cell inside a grown-tile slot
-  // staged stores (S2Geom::STAGE): lane i of a phase-B wave stores cells 4 (i % 16) .. + 3 of the wave's row for population 4 g + i / 16;
-  // byte offset of that piece from population 4 g's row of the plane (the tile's z shift is a multiple of 4: a piece never straddles the wrap)
-  // (the last group holds Q % 4 populations: its idle lanes repeat the last one — same bytes to the same address, no branch around the store)
-  size_t stage_off = 0, stage_off_last = 0;
-  constexpr int SUB_LAST = (Q - 1) % 4;
-  const int sub = (t >> 4) & 3, sub_last = sub < SUB_LAST ? sub : SUB_LAST;
-  if constexpr (G::STAGE) {
-    int zc = tz0 + 4 * (t & 15);
-    zc = zc >= nz ? zc - nz : zc;
-    const size_t cell_off = (size_t)yb * (unsigned)nz + (unsigned)zc;
-    stage_off = ((size_t)sub * a.plane_stride + cell_off) * ES;
-    stage_off_last = ((size_t)sub_last * a.plane_stride + cell_off) * ES;
-  }
 
   // logical plane p -> the plane phase A works on: without ghost planes x is periodic; with them planes past x_hi
   // are prefetches whose results are discarded (clamped, so that they stay inside the allocation)
@@ -462,11 +363,10 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
     Xs[2] = SLAB ? x - 1 : ((x == 0) ? nx - 1 : x - 1);
     if constexpr (HASBC != 0) {
       if (mall != 0u) {
-        // Boundary wave (round 3): a halfway-wall lane pulls each of its missing directions from its OWN cell's OPPOSITE population —
-        // inside the same pull instruction, through a per-lane 64-bit address (4 VALU per pull, boundary waves only).  Exactly Q loads
-        // on either side of this wave-uniform branch, all of them visible to the compiler: its vmcnt model of the loop stays exact
-        // WITHOUT round 2's extra inline-asm loads, their hand-counted wait and the no-copy / no-spill invariants they needed —
-        // and a hull tile's pull phase issues 19 instructions instead of 24-29 (profiles/r03/step2_redirect.md).
+        // Boundary wave: a halfway-wall lane pulls each of its missing directions from its OWN cell's OPPOSITE population — inside the
+        // same pull instruction, through a per-lane 64-bit address (4 VALU per pull, boundary waves only).  Exactly Q loads on either
+        // side of this wave-uniform branch, all of them visible to the compiler, so its vmcnt model of the loop stays exact
+        // (round 2's extra inline-asm loads: measured and removed, profiles/r03/step2_redirect.md).
         const unsigned kind = M::kind(w);
         const unsigned m = (kind == K_HW || kind == M::K_HWM) ? M::missing(w) : 0u;
         const unsigned voff = cell_a * ES;
@@ -541,24 +441,17 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
     }
     finish(f, fullway);
     if (act_a) {
-      if constexpr (!PACKED) {
-        S* dst = lds + (q % 3) * (Q * NE) + slot_a;
-        static_for<Q>([&](auto lc) {
-          constexpr int l = decltype(lc)::value;
-          dst[l * NE] = to_store<S, T>(f[l]);  // f(t+1) passes through the store precision
-        });
-      } else {
-        // one pointer per group buffer + a compile-time offset per population (pointer form: see phase B)
-        S* gb[3];
-        static_for<3>([&](auto gc) {
-          constexpr int g = decltype(gc)::value, life = R::glife(g);
-          gb[g] = lds + (R::gbase(g) + R::template buf<life>(q) * R::gcount(g)) * NE + slot_a;
-        });
-        static_for<Q>([&](auto lc) {
-          constexpr int l = decltype(lc)::value;
-          gb[R::group(l)][R::gidx(l) * NE] = to_store<S, T>(f[l]);
-        });
-      }
+      // one pointer per group buffer + a compile-time offset per population (pointer form: see phase B); f(t+1) passes through
+      // the store precision
+      S* gb[3];
+      static_for<3>([&](auto gc) {
+        constexpr int g = decltype(gc)::value, life = R::glife(g);
+        gb[g] = lds + (R::gbase(g) + R::template buf<life>(q) * R::gcount(g)) * NE + slot_a;
+      });
+      static_for<Q>([&](auto lc) {
+        constexpr int l = decltype(lc)::value;
+        gb[R::group(l)][R::gidx(l) * NE] = to_store<S, T>(f[l]);
+      });
       if constexpr (HASBC != 0) ldsmeta[(q % 3) * NE + slot_a] = w;
     }
   };
@@ -576,31 +469,19 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
       mall = wave_or(mm);  // uniform; all lanes of the wave are active here (NB is a whole number of waves)
     }
     if (mall == 0u) {  // fluid wave (or only fullway / equilibrium lanes): one scalar branch, then straight-line reads
-      if constexpr (!PACKED) {
-        const S* base[3];  // index c_x + 1 -> plane x - c_x
-        base[0] = lds + ((q0 + 1) % 3) * (Q * NE);
-        base[1] = lds + (q0 % 3) * (Q * NE);
-        base[2] = lds + ((q0 - 1) % 3) * (Q * NE);
-        static_for<Q>([&](auto lc) {
-          constexpr int l = decltype(lc)::value;
-          constexpr int cx = L::c(0, l), cy = L::c(1, l), cz = L::c(2, l);
-          f[l] = to_compute<T, S>(base[cx + 1][l * NE + ctr_b - cy * EZ - cz]);
-        });
-      } else {
-        // (pointer + immediate form; indexing one array with run-time buffer offsets — lds[ring(l, q) + ...] — compiles to
-        // the same instruction mix but measured 9 % slower on the periodic box: profiles/r02/step2_sweeps.txt)
-        const S* gb[3];  // group g = c_x + 1 comes from plane q0 - c_x
-        static_for<3>([&](auto gc) {
-          constexpr int g = decltype(gc)::value, life = R::glife(g);
-          const int qs = q0 - (g - 1);
-          gb[g] = lds + (R::gbase(g) + R::template buf<life>(qs) * R::gcount(g)) * NE;
-        });
-        static_for<Q>([&](auto lc) {
-          constexpr int l = decltype(lc)::value;
-          constexpr int cy = L::c(1, l), cz = L::c(2, l);
-          f[l] = to_compute<T, S>(gb[R::group(l)][R::gidx(l) * NE + ctr_b - cy * EZ - cz]);
-        });
-      }
+      // (pointer + immediate form; indexing one array with run-time buffer offsets — lds[ring(l, q) + ...] — compiles to
+      // the same instruction mix but measured 9 % slower on the periodic box: profiles/r02/step2_sweeps.txt)
+      const S* gb[3];  // group g = c_x + 1 comes from plane q0 - c_x
+      static_for<3>([&](auto gc) {
+        constexpr int g = decltype(gc)::value, life = R::glife(g);
+        const int qs = q0 - (g - 1);
+        gb[g] = lds + (R::gbase(g) + R::template buf<life>(qs) * R::gcount(g)) * NE;
+      });
+      static_for<Q>([&](auto lc) {
+        constexpr int l = decltype(lc)::value;
+        constexpr int cy = L::c(1, l), cz = L::c(2, l);
+        f[l] = to_compute<T, S>(gb[R::group(l)][R::gidx(l) * NE + ctr_b - cy * EZ - cz]);
+      });
     } else {
       // boundary wave: a lane whose missing bit l is set reads its own cell's opposite population instead (select on
       // the LDS index, no branch), then the halfway-wall terms are applied to exactly those populations
@@ -621,39 +502,19 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
     }
     finish(f, fullway);
   };
-  // Tried and rejected (profiles/r02/step2_sweeps.txt): pulls running TWO planes ahead (second register buffer, loop unrolled by
-  // two; 153 VGPRs) — 0.5 % on the periodic box, 1 % on the cavity: the memory latency behind one phase B is not what the waves wait for.
-  // Tried and rejected: issuing the 19 stores from EVERY wave outside the branch (buffer stores, idle waves aimed past
-  // the end of the buffer) makes hipcc's vmcnt model exact — with the stores inside `if (act_b)` it waits for the
-  // prefetched pulls with vmcnt(19)...vmcnt(1), i.e. drains the wave's own stores every plane — but ran 9 % SLOWER
-  // without boundary conditions and the same with them: the kernel is bound by VALU issue, not by these waits.
+  // (Pulls running TWO planes ahead: measured and removed, profiles/r02/step2_sweeps.txt.)  The stores stay inside `if (act_b)` although
+  // hipcc then drains them every plane: issued from EVERY wave outside the branch they made its vmcnt model exact but ran 9 % SLOWER.
   auto phase_b = [&](int x, int d) __attribute__((always_inline)) {
     if (!act_b) return;  // whole waves (NB % 64 == 0)
     T f[Q];
     phase_b_compute(f, d);
-    if constexpr (G::STAGE) {
-      // the wave's 64 cells are one z row of the tile: population-major into the wave's staging area, back as (population, 4 cells)
-      S* st = lds + G::RING_PLANES * NE + (t >> 6) * (Q * 64);
-      const int lane = t & 63;
-      static_for<Q>([&](auto lc) { st[decltype(lc)::value * 64 + lane] = to_store<S, T>(f[decltype(lc)::value]); });
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (LDS operations of one wave complete in order; this orders the compiler's view too)
-      char* xrow = reinterpret_cast<char*>(a.dst + (ptrdiff_t)x * pc);  // uniform
-      static_for<G::N_STORES>([&](auto gc) {
-        constexpr int g = decltype(gc)::value;
-        constexpr bool last = 4 * g + 3 >= Q;
-        typedef typename VecOf<S, 4>::aligned V4;
-        const V4 v = *reinterpret_cast<const V4*>(st + (4 * g + (last ? sub_last : sub)) * 64 + (lane & 15) * 4);
-        __builtin_nontemporal_store(v, reinterpret_cast<V4*>(xrow + (size_t)(4 * g) * a.plane_stride * ES + (last ? stage_off_last : stage_off)));
-      });
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staging area is rewritten by the next plane's phase B
-    } else {
-      static_for<Q>([&](auto lc) {
-        constexpr int l = decltype(lc)::value;
-        S* drow = a.dst + (size_t)l * a.plane_stride + (ptrdiff_t)x * pc;  // uniform
-        S v[1] = {to_store<S, T>(f[l])};
-        st_aligned<S, 1, true>(drow, cell_b * ES, v);
-      });
-    }
+    // (16-byte stores staged through LDS: within the noise, measured and removed: profiles/r02/step2_sweeps.txt)
+    static_for<Q>([&](auto lc) {
+      constexpr int l = decltype(lc)::value;
+      S* drow = a.dst + (size_t)l * a.plane_stride + (ptrdiff_t)x * pc;  // uniform
+      S v[1] = {to_store<S, T>(f[l])};
+      st_aligned<S, 1, true>(drow, cell_b * ES, v);
+    });
     if constexpr (SW) {
       // the two outermost cells of the row on either side feed the strips.  Each of those four lanes parks ALL its Q values in LDS
       // ([edge lane 0..3][row][population]: one exec-masked region, Q plain writes — selecting per population what the strips
@@ -762,10 +623,10 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
 // `a.clean[blockIdx.x]` (k_step2_clean, rebuilt with the meta words every run) is block-uniform.  On the 512^3 cavity that
 // is every segment of an interior tile column but its first and last one, 54 % of the items.  (Round 1 tried the same
 // split as separate launches on two streams and lost to launch tails / kernel mixing; one launch has neither.)
-template <class L, class T, class S, int COLL, int HASBC, int TY, int TZ, bool SLAB, bool PACKED, bool FAST, int STRIPS = 0>
-__global__ void __attribute__((aligned(XLB_STEP2_ALIGN))) __launch_bounds__((S2Geom<L, HASBC, TY, TZ, PACKED>::THREADS), (S2Geom<L, HASBC, TY, TZ, PACKED>::WAVES_PER_SIMD)) k_step2(const StepArgs<T, S> a) {
-  using G = S2Geom<L, HASBC, TY, TZ, PACKED>;
-  __shared__ S lds[G::RING_PLANES * G::NE + G::STAGE_ELEMS];                          // the ring of f(t+1) (D3Q19, 8x64 tile, three-plane layout: 150 480 B -> one block per CU)
+template <class L, class T, class S, int COLL, int HASBC, int TY, int TZ, bool SLAB, bool FAST, int STRIPS = 0>
+__global__ void __attribute__((aligned(256))) __launch_bounds__((S2Geom<L, HASBC, TY, TZ>::THREADS), (S2Geom<L, HASBC, TY, TZ>::WAVES_PER_SIMD)) k_step2(const StepArgs<T, S> a) {
+  using G = S2Geom<L, HASBC, TY, TZ>;
+  __shared__ S lds[G::RING_PLANES * G::NE];                     // the ring of f(t+1) (D3Q19 BC kernel, 8x64 tile, slack ring: 150 480 B -> one block per CU)
   __shared__ unsigned ldsmeta[HASBC ? 3 * G::NE : 1];           // [plane % 3][cell] kind | slot << 4 | missing << 8 of the f(t+1) cells
   __shared__ T bcval[HASBC ? MAX_FAST_BCS * 32 : 1];            // per-BC constants (feq of EquilibriumBC / moving-wall terms), by slot
   constexpr int STRIP_SLOTS = (L::Q - n_cz0<L>()) / 2 + n_cz0<L>();  // values an edge cell contributes: its c_z = -1 or +1 populations and the c_z = 0 ones
@@ -774,11 +635,12 @@ __global__ void __attribute__((aligned(XLB_STEP2_ALIGN))) __launch_bounds__((S2G
   static_assert(G::LDS_BYTES + ((STRIPS & 2) ? 2 * STRIP_SLOTS * 4 * TY * 4 : 0) <= 160 * 1024, "strip staging does not fit the LDS");
   if constexpr (HASBC != 0) {
     if (a.clean != nullptr && a.clean[blockIdx.x] != 0) {
-      step2_body<L, T, S, COLL, 0, TY, TZ, SLAB, PACKED, XLB_STEP2_CLEAN_GMAX, XLB_PIN_CLEAN, FAST, G::SLACK, STRIPS>(a, lds, ldsmeta, bcval, strip_stage);
+      // (pair-group width 3: with 1 hipcc parks the pairs in scratch here)
+      step2_body<L, T, S, COLL, 0, TY, TZ, SLAB, 3, true, FAST, G::SLACK, STRIPS>(a, lds, ldsmeta, bcval, strip_stage);
       return;
     }
   }
-  step2_body<L, T, S, COLL, HASBC, TY, TZ, SLAB, PACKED, (HASBC != 0 ? 3 : XLB_STEP2_PLAIN_GMAX), (HASBC != 0 ? XLB_PIN_BC : false), FAST, (HASBC == 0 && G::SLACK && XLB_STEP2_SLACK_PLAIN != 0), STRIPS>(a, lds, ldsmeta, bcval, strip_stage);
+  step2_body<L, T, S, COLL, HASBC, TY, TZ, SLAB, (HASBC != 0 ? 3 : 1), HASBC != 0, FAST, false, STRIPS>(a, lds, ldsmeta, bcval, strip_stage);
 }
 
 // Strip buffers (round 3).  The grown tile's two halo COLUMNS cost phase A 64-byte sectors for 4-byte values — 5-6 sectors per

@@ -5,9 +5,6 @@
 
 namespace xlb {
 
-#ifndef XLB_STEP2_PACKED_DEFAULT
-#define XLB_STEP2_PACKED_DEFAULT true
-#endif
 // effective launch geometry (shared by the kernel launch and the clean-flag pass: both must map blocks alike)
 inline int step2_eff_segments(const StepLaunch& p) { return (p.x_segments > 1 && p.x_count >= 8 * p.x_segments) ? p.x_segments : 1; }
 // thin end segments need >= 3 segments and inner segments of at least 8 planes
@@ -17,19 +14,19 @@ inline int step2_eff_cap(const StepLaunch& p) {
 }
 inline int step2_eff_swizzle(const StepLaunch& p, unsigned tiles) { return (p.xcd_swizzle && tiles % 8u == 0u) ? 1 : 0; }
 
-template <class L, int HASBC, int TY, int TZ, bool SLAB, bool PACKED, bool FAST, class T = float, int COLL = XLBHIP_BGK, int STRIPS = 0>
+template <class L, int HASBC, int TY, int TZ, bool SLAB, bool FAST, class T = float, int COLL = XLBHIP_BGK, int STRIPS = 0>
 static int launch2f(const StepLaunch& p);
 
 // fast_bgk = 1 (opt-in): the tolerance-graded fast BGK body (cell.hpp: bgk_fast).  Measured: 20 % fewer VALU instructions buy
 // 2-4 % (profiles/r02/step2_sweeps.txt) — the kernel is bound by its real memory traffic, not by VALU issue — so the
 // bit-exact body stays the default.
-template <class L, int HASBC, int TY, int TZ, bool SLAB, bool PACKED = XLB_STEP2_PACKED_DEFAULT>
+template <class L, int HASBC, int TY, int TZ, bool SLAB>
 static int launch2(const StepLaunch& p) {
-  return p.fast_bgk ? launch2f<L, HASBC, TY, TZ, SLAB, PACKED, true>(p) : launch2f<L, HASBC, TY, TZ, SLAB, PACKED, false>(p);
+  return p.fast_bgk ? launch2f<L, HASBC, TY, TZ, SLAB, true>(p) : launch2f<L, HASBC, TY, TZ, SLAB, false>(p);
 }
 
 // T / COLL: compute type and collision (cell.hpp collide<>) of the instantiation; the store type is always fp32
-template <class L, int HASBC, int TY, int TZ, bool SLAB, bool PACKED, bool FAST, class T, int COLL, int STRIPS>
+template <class L, int HASBC, int TY, int TZ, bool SLAB, bool FAST, class T, int COLL, int STRIPS>
 static int launch2f(const StepLaunch& p) {
   static_assert(HASBC == 0 || (sizeof(T) == 4 && COLL == XLBHIP_BGK), "boundary-condition tables of the two-step kernel are fp32 / BGK");
   StepArgs<T, float> a;
@@ -77,7 +74,7 @@ static int launch2f(const StepLaunch& p) {
   a.extra.smag_cs = p.smag_cs;
   const unsigned tiles = (unsigned)(p.ny / TY) * (unsigned)(p.nz / TZ);
   a.xcd_swizzle = step2_eff_swizzle(p, tiles);
-  hipLaunchKernelGGL((k_step2<L, T, float, COLL, HASBC, TY, TZ, SLAB, PACKED, FAST, STRIPS>), dim3(tiles * (unsigned)a.x_segments), dim3(S2Geom<L, HASBC, TY, TZ, PACKED>::THREADS), 0, p.stream, a);
+  hipLaunchKernelGGL((k_step2<L, T, float, COLL, HASBC, TY, TZ, SLAB, FAST, STRIPS>), dim3(tiles * (unsigned)a.x_segments), dim3(S2Geom<L, HASBC, TY, TZ>::THREADS), 0, p.stream, a);
   XLB_HIP(hipGetLastError());
   return 0;
 }

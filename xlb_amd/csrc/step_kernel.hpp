@@ -20,6 +20,7 @@
 //   * stores are aligned (vector) stores, optionally non-temporal.
 #pragma once
 #include "cell.hpp"
+#include "step2_plan.hpp"
 
 #ifndef XLB_LB1
 #define XLB_LB1 256  // launch bound of the one-cell-per-thread variants
@@ -29,7 +30,6 @@ namespace xlb {
 
 // kinds as the kernel sees them
 enum { K_NONE = 0, K_EQ = XLBHIP_BC_EQUILIBRIUM, K_HW = XLBHIP_BC_HALFWAY_BB, K_FW = XLBHIP_BC_FULLWAY_BB, K_DN = XLBHIP_BC_DO_NOTHING };
-constexpr int MAX_FAST_BCS = 8;
 template <class T, class S>
 struct StepArgs {
   const S* src;

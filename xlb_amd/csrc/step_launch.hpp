@@ -194,7 +194,6 @@ int launch_step_f64(const StepLaunch& p) {
 // defined one per translation unit (step_<lattice>_<collision>.hip)
 int launch_step_d3q27_kbc_fast64(const StepLaunch& p);
 // two steps per pass (step2_kernel.hpp): f(t) in src -> f(t+2) in dst
-bool step2_eligible(const StepLaunch& p, int lattice, int collision);
 int launch_step2_d3q19_bgk(const StepLaunch& p);
 int launch_step2_d3q19_bgk_strips(const StepLaunch& p);  // p.strips != 0 (step2_d3q19_strips.hip)
 
