@@ -263,12 +263,32 @@ int xlbhip_stepper_set_bc_distances(xlbhip_stepper* s, int64_t n, const uint32_t
  * wall-distance and wall-velocity tables; force[3] in the internal 3-component form.  Fields without ghost planes. */
 int xlbhip_stepper_momentum_transfer(xlbhip_stepper* s, int bc_id, const xlbhip_field* f_0, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask,
                                      double force[3]);
+/* Time-dependent wall velocities: HalfwayBounceBackBC / HybridBC whose profile is profile(index, timestep) (bc_halfway_bounce_back.py:147-155,
+ * bc_hybrid.py:163-172 and :228-239; the stepper passes its timestep to every BC functional, nse_stepper.py:370-378).  The BC's storage
+ * cells (as for set_bc_profile) are declared ONCE; they become entries of the stepper's profile table whose values arrive per timestep.
+ * Calls accumulate (one per BC); the declaration order of all calls is the order of the values of xlbhip_stepper_stage_bc_profiles. */
+int xlbhip_stepper_set_bc_profile_cells(xlbhip_stepper* s, int bc_id, int64_t n, const uint32_t* storage_cells);
+/* Number of per-timestep tables the stepper keeps resident (a ring of device slots sized from a byte budget, 4 .. 64, even); 0 without
+ * time-dependent cells.  At most this many timesteps can be staged by one call. */
+int xlbhip_stepper_profile_slots(xlbhip_stepper* s, int* slots);
+/* The wall velocities of the timesteps t_first .. t_first + n_steps - 1: values = n_steps rows, each row 3 doubles (internal
+ * 3-component form, already rounded to the compute dtype) per declared cell in declaration order.  Each row is scattered into a full
+ * image of the table (the static Zou-He / profile entries stay) and copied into the next slot of the ring through a pinned host buffer
+ * by hipMemcpyAsync on the compute stream; the host waits only for the previous copy out of the same pinned row.  A timestep that is
+ * staged again replaces its older image.  Every launch of a step from timestep t (xlbhip_step, xlbhip_step2: t and t + 1, xlbhip_run*:
+ * t0 .. t0 + n - 1) reads t's image and fails, before enqueuing anything, when it is not resident. */
+int xlbhip_stepper_stage_bc_profiles(xlbhip_stepper* s, int64_t t_first, int64_t n_steps, const double* values);
+/* xlbhip_stepper_momentum_transfer with the wall velocities of `timestep` (force/momentum_transfer.py:88 evaluates the wall at timestep
+ * 0, which is what xlbhip_stepper_momentum_transfer does); a time-dependent wall needs that timestep staged. */
+int xlbhip_stepper_momentum_transfer_at(xlbhip_stepper* s, int bc_id, int64_t timestep, const xlbhip_field* f_0, const xlbhip_field* bc_mask,
+                                        const xlbhip_field* missing_mask, double force[3]);
 /* ForcedCollision with the exact-difference scheme (forced_collision.py:44-50, exact_difference_force.py:61-83):
  * force[3] in the internal 3-component form; NULL switches forcing off */
 int xlbhip_stepper_set_force(xlbhip_stepper* s, const double* force);
 /* Smagorinsky constant of XLBHIP_SMAGORINSKY_LES_BGK (default 0.17, smagorinsky_les_bgk.py:36) */
 int xlbhip_stepper_set_smagorinsky(xlbhip_stepper* s, double coef);
-/* one step: reads f_src, writes f_dst (caller swaps); omega is cast to compute dtype (bgk.py:31) */
+/* one step: reads f_src, writes f_dst (caller swaps); omega is cast to compute dtype (bgk.py:31); timestep selects the staged wall
+ * velocities of time-dependent profiles (xlbhip_stepper_stage_bc_profiles) and is ignored otherwise */
 int xlbhip_step(xlbhip_stepper* s, const xlbhip_field* f_src, xlbhip_field* f_dst, const xlbhip_field* bc_mask,
                 const xlbhip_field* missing_mask, double omega, int64_t timestep);
 /* n_steps steps with the A/B swap done natively; the result is in f_a if n_steps is even, else f_b */

@@ -80,6 +80,10 @@ SIGNATURES = {
     "xlbhip_grid_to_point": [_p, _p, _i64, _p, _p],
     "xlbhip_momentum_transfer": [_p, _i, _i, C.POINTER(BcDesc), _p, _p, _p, C.POINTER(C.c_double)],
     "xlbhip_stepper_set_bc_profile": [_p, _i, _i64, _p, _p],
+    "xlbhip_stepper_set_bc_profile_cells": [_p, _i, _i64, _p],
+    "xlbhip_stepper_profile_slots": [_p, C.POINTER(_i)],
+    "xlbhip_stepper_stage_bc_profiles": [_p, _i64, _i64, _p],
+    "xlbhip_stepper_momentum_transfer_at": [_p, _i, _i64, _p, _p, _p, C.POINTER(C.c_double)],
     "xlbhip_apply_bc_profile": [_p, _i, _i, C.POINTER(BcDesc), _p, _p, _p, _p, _i64, _p, _p],
     "xlbhip_q_criterion": [_p, _p, _p, _p, _p],
     "xlbhip_collide": [_p, _i, _i, _i, _p, _p, _p, _d],
@@ -533,10 +537,34 @@ class Stepper:
         assert w.ndim == 2 and k.shape[0] == w.shape[0]
         check(load().xlbhip_stepper_set_bc_distances(self._h, int(k.shape[0]), k.ctypes.data, w.ctypes.data))
 
+    def set_bc_profile_cells(self, bc_id, storage_cells):
+        """Storage cells of a time-dependent wall (HalfwayBounceBackBC / HybridBC with profile(cells, timestep)): values per timestep follow
+        through stage_bc_profiles, in the order of these calls."""
+        k = np.ascontiguousarray(storage_cells, dtype=np.uint32)
+        check(load().xlbhip_stepper_set_bc_profile_cells(self._h, int(bc_id), int(k.shape[0]), k.ctypes.data))
+
+    def profile_slots(self):
+        """Per-timestep tables the stepper keeps resident (0 without time-dependent walls)."""
+        n = _i()
+        check(load().xlbhip_stepper_profile_slots(self._h, C.byref(n)))
+        return n.value
+
+    def stage_bc_profiles(self, t_first, values):
+        """Wall velocities of the timesteps t_first, t_first + 1, ...: (n_steps, n_cells, 3) float64, the cells in declaration order."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        assert v.ndim == 3 and v.shape[2] == 3
+        check(load().xlbhip_stepper_stage_bc_profiles(self._h, int(t_first), int(v.shape[0]), v.ctypes.data))
+
     def momentum_transfer(self, bc_id, f_0, bc_mask, missing_mask):
         """Force (3,) on the solid behind a HybridBC / profile wall of this stepper (its distance and velocity tables)."""
         out = (C.c_double * 3)()
         check(load().xlbhip_stepper_momentum_transfer(self._h, int(bc_id), f_0.handle, _h(bc_mask), _h(missing_mask), out))
+        return np.array(out[:], dtype=np.float64)
+
+    def momentum_transfer_at(self, bc_id, timestep, f_0, bc_mask, missing_mask):
+        """As momentum_transfer with the wall velocities of `timestep` (a time-dependent wall needs it staged)."""
+        out = (C.c_double * 3)()
+        check(load().xlbhip_stepper_momentum_transfer_at(self._h, int(bc_id), int(timestep), f_0.handle, _h(bc_mask), _h(missing_mask), out))
         return np.array(out[:], dtype=np.float64)
 
     def set_smagorinsky(self, coef):

@@ -1049,6 +1049,22 @@ struct xlbhip_stepper {
   uint32_t* prof_keys = nullptr;
   void* prof_vals = nullptr;  // compute dtype [n_prof][3]
   int n_prof = 0;
+  // time-dependent wall velocities (HalfwayBounceBackBC / HybridBC with profile(cells, timestep)): their cells are entries of
+  // the same table, declared once (td_cells, in declaration order; td_pos = their rows in the sorted table).  Every timestep
+  // gets a full image of the table in one slot of a device ring; ring_t[slot] = the timestep it holds.  Images are staged
+  // through pinned host rows (one per slot, static entries written once), each guarded by the event of its last copy.  A
+  // stepper without time-dependent BCs has no ring and keeps its single table.
+  std::vector<uint32_t> td_cells;
+  std::vector<int> td_pos;
+  bool td_contiguous = false;     // td_pos[i] == td_pos[0] + i: the rows are one block of the table
+  std::array<uint8_t, 256> td_bc{};  // bc ids with time-dependent cells
+  std::vector<char> prof_image;  // host copy of the table (compute dtype): the static entries of every image
+  void* ring = nullptr;     // device [ring_slots][n_prof][3] compute dtype
+  void* ring_pin = nullptr;  // pinned host, same layout
+  std::vector<hipEvent_t> ring_ev;
+  std::vector<int64_t> ring_t;
+  std::vector<uint8_t> ring_used, ring_pin_ready;  // slot holds a staged image / pinned row holds the static entries
+  int ring_slots = 0, ring_head = 0;
   // wall-distance weights of HybridBC cells (mesh maskers): host map (storage cell -> q weights) and its sorted device image
   std::map<uint32_t, std::array<float, 27>> dist_host;
   uint32_t* dist_keys = nullptr;
@@ -1059,6 +1075,7 @@ struct xlbhip_stepper {
 namespace xlb {
 
 static int launch_any(const xlbhip_stepper* s, const StepLaunch& p) {
+  XLB_REQUIRE(p.n_prof == 0 || p.prof_vals, "step launch without its profile table (timestep not staged)");
   if (s->forced || s->collision == XLBHIP_SMAGORINSKY_LES_BGK) {
     const int coll = s->collision | (s->forced ? COLL_FORCED : 0);
     if (s->lattice == XLBHIP_D2Q9) return launch_step_d2q9_ext(p, coll);
@@ -1092,8 +1109,80 @@ static int check_step_fields(const xlbhip_stepper* s, const xlbhip_field* a, con
   return 0;
 }
 
+// ---- per-timestep profile tables (time-dependent wall velocities) ----
+// The ring holds a byte budget's worth of table images, at least 4 and at most 64, an even count (the Python stepper stages
+// chunks of half the ring, in pairs of steps).
+static const size_t PROF_RING_BYTES = (size_t)64 << 20;
+static const int PROF_RING_MIN = 4, PROF_RING_MAX = 64;
+
+static bool has_td(const xlbhip_stepper* s) { return !s->td_cells.empty(); }
+static size_t prof_image_bytes(const xlbhip_stepper* s) { return (size_t)s->n_prof * 3 * (s->cdt == XLBHIP_F32 ? 4 : 8); }
+
+static int ring_slot_count(const xlbhip_stepper* s) {
+  const size_t k = PROF_RING_BYTES / std::max<size_t>(prof_image_bytes(s), 1);
+  const int n = (int)std::min<size_t>(std::max<size_t>(k, PROF_RING_MIN), PROF_RING_MAX);
+  return n & ~1;
+}
+
+// the profile table the launches of timestep t read: the single table, or t's slot of the ring (nullptr: t is not staged)
+static const void* prof_table_at(const xlbhip_stepper* s, int64_t t) {
+  if (!has_td(s)) return s->prof_vals;
+  for (int k = 0; k < s->ring_slots; ++k)
+    if (s->ring_used[k] && s->ring_t[k] == t) return static_cast<const char*>(s->ring) + (size_t)k * prof_image_bytes(s);
+  return nullptr;
+}
+
+// the tables of the timesteps t0 .. t0 + n - 1 are all resident: checked before anything of a call is enqueued
+static int require_staged(const xlbhip_stepper* s, int64_t t0, int64_t n) {
+  if (!has_td(s)) return 0;
+  for (int64_t k = 0; k < n; ++k)
+    XLB_REQUIRE(prof_table_at(s, t0 + k), "the time-dependent wall velocities of timestep %lld are not staged (xlbhip_stepper_stage_bc_profiles)",
+                (long long)(t0 + k));
+  return 0;
+}
+
+// (the stream must be drained: copies may still read the pinned rows)
+static void free_ring(xlbhip_stepper* s) {
+  for (hipEvent_t e : s->ring_ev) (void)hipEventDestroy(e);
+  if (s->ring) (void)hipFree(s->ring);
+  if (s->ring_pin) (void)hipHostFree(s->ring_pin);
+  s->ring = nullptr;
+  s->ring_pin = nullptr;
+  s->ring_ev.clear();
+  s->ring_t.clear();
+  s->ring_used.clear();
+  s->ring_pin_ready.clear();
+  s->ring_slots = s->ring_head = 0;
+}
+
+static int ensure_ring(xlbhip_stepper* s) {
+  if (s->ring) return 0;
+  const int slots = ring_slot_count(s);
+  const size_t bytes = (size_t)slots * prof_image_bytes(s);
+  XLB_HIP(hipMalloc(&s->ring, bytes));
+  if (hipError_t e = hipHostMalloc(&s->ring_pin, bytes, hipHostMallocDefault); e != hipSuccess) {
+    s->ring_pin = nullptr;
+    free_ring(s);
+    XLB_FAIL("hipHostMalloc(%zu bytes) for the profile ring failed: %s", bytes, hipGetErrorString(e));
+  }
+  s->ring_slots = slots;
+  s->ring_ev.assign((size_t)slots, nullptr);
+  s->ring_t.assign((size_t)slots, 0);
+  s->ring_used.assign((size_t)slots, 0);
+  s->ring_pin_ready.assign((size_t)slots, 0);
+  for (int k = 0; k < slots; ++k) {
+    if (hipError_t e = hipEventCreateWithFlags(&s->ring_ev[k], hipEventDisableTiming); e != hipSuccess) {
+      s->ring_ev.resize((size_t)k);
+      free_ring(s);
+      XLB_FAIL("hipEventCreate: %s", hipGetErrorString(e));
+    }
+    XLB_HIP(hipEventRecord(s->ring_ev[k], s->ctx->stream));  // (every row starts out "copied")
+  }
+  return 0;
+}
+
 static StepLaunch make_launch(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
-                              double omega) {
+                              double omega, int64_t t) {
   xlbhip_ctx* c = s->ctx;
   StepLaunch p;
   p.src = src->data;
@@ -1118,7 +1207,7 @@ static StepLaunch make_launch(xlbhip_stepper* s, const xlbhip_field* src, xlbhip
   p.n_bc = s->n_bc;
   p.tab_values = s->tab_values;
   p.prof_keys = s->prof_keys;
-  p.prof_vals = s->prof_vals;
+  p.prof_vals = prof_table_at(s, t);  // (time-dependent walls: t's slot of the ring, checked resident by the caller)
   p.n_prof = s->n_prof;
   p.dist_keys = s->dist_keys;
   p.dist_vals = s->dist_vals;
@@ -1167,18 +1256,21 @@ static int fuse2_segments(const xlbhip_stepper* s, const StepLaunch& p) {
 }
 
 // assemble_auxiliary_data of the ExtrapolationOutflowBC cells after a step src -> dst (nse_stepper.py:270-272)
-static int outflow_aux(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss) {
+static int outflow_aux(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
+                       int64_t t) {
   if (!s->has_outflow) return 0;
   xlbhip_ctx* c = s->ctx;
   const size_t n = dst->cells();
+  const void* pv = prof_table_at(s, t);
+  XLB_REQUIRE(s->n_prof == 0 || pv, "outflow pass without its profile table (timestep %lld not staged)", (long long)t);
   return by_lattice(s->lattice, [&](auto L) {
     using LL = decltype(L);
     if (s->cdt == XLBHIP_F32)
       hipLaunchKernelGGL((k_outflow_aux<LL, float>), blocks_for(n), 256, 0, c->stream, view(src), view(dst), view(bcm), view(miss), dims(dst),
-                         s->tab_kind, static_cast<const float*>(s->tab_values), s->prof_keys, static_cast<const float*>(s->prof_vals), s->n_prof);
+                         s->tab_kind, static_cast<const float*>(s->tab_values), s->prof_keys, static_cast<const float*>(pv), s->n_prof);
     else
       hipLaunchKernelGGL((k_outflow_aux<LL, double>), blocks_for(n), 256, 0, c->stream, view(src), view(dst), view(bcm), view(miss), dims(dst),
-                         s->tab_kind, static_cast<const double*>(s->tab_values), s->prof_keys, static_cast<const double*>(s->prof_vals), s->n_prof);
+                         s->tab_kind, static_cast<const double*>(s->tab_values), s->prof_keys, static_cast<const double*>(pv), s->n_prof);
     XLB_HIP(hipGetLastError());
     return 0;
   });
@@ -1230,9 +1322,10 @@ static bool ensure_strips(xlbhip_field* f) {
 // Pair of steps for a stepper whose Zou-He / Regularized / outflow cells all sit in the planes x = 0 and x = nx - 1
 // (inlet / outlet faces): the two-step kernel updates the planes 2 .. nx-3, whose two-step cone never evaluates such a
 // cell (its f(t+1) on the planes 1 and nx-2 only PULLS from the end planes), and the four end planes go through the
-// single-step kernel twice with a third population field holding their f(t+1).
+// single-step kernel twice with a third population field holding their f(t+1).  The first of those launches reads the
+// profile table of timestep t, the second that of t + 1 (time-dependent walls on the end planes).
 static int step_twice_edge_ext(xlbhip_stepper* s, StepLaunch p, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm,
-                               const xlbhip_field* miss, double omega) {
+                               const xlbhip_field* miss, double omega, int64_t t) {
   XLB_REQUIRE(s->scratch && s->scratch->plane_stride == src->plane_stride, "scratch field missing (can_fuse2 allocates it)");
   const int nx = src->nx;
   p.x_begin = 2;
@@ -1240,21 +1333,21 @@ static int step_twice_edge_ext(xlbhip_stepper* s, StepLaunch p, const xlbhip_fie
   p.x_segments = fuse2_segments(s, p);
   if (int rc = launch_step2_d3q19_bgk(p)) return rc;
   // end planes, step 1: f(t+1) on the planes nx-3 .. nx-1 and 0 .. 2 -> scratch
-  StepLaunch q = make_launch(s, src, s->scratch, bcm, miss, omega);
+  StepLaunch q = make_launch(s, src, s->scratch, bcm, miss, omega, t);
   q.x_begin = nx - 3;
   q.x_count = 3;
   if (int rc = launch_any(s, q)) return rc;
   q.x_begin = 0;
   if (int rc = launch_any(s, q)) return rc;
-  if (int rc = outflow_aux(s, src, s->scratch, bcm, miss)) return rc;
+  if (int rc = outflow_aux(s, src, s->scratch, bcm, miss, t)) return rc;
   // step 2: f(t+2) on the planes nx-2, nx-1, 0, 1 -> dst
-  StepLaunch r = make_launch(s, s->scratch, dst, bcm, miss, omega);
+  StepLaunch r = make_launch(s, s->scratch, dst, bcm, miss, omega, t + 1);
   r.x_begin = nx - 2;
   r.x_count = 2;
   if (int rc = launch_any(s, r)) return rc;
   r.x_begin = 0;
   if (int rc = launch_any(s, r)) return rc;
-  return outflow_aux(s, s->scratch, dst, bcm, miss);
+  return outflow_aux(s, s->scratch, dst, bcm, miss, t + 1);
 }
 
 // the compute stream waits for the halo exchange; with the telemetry on, the wait is bracketed by two timing events
@@ -1290,8 +1383,8 @@ static int wait_for_halo(xlbhip_ctx* c) {
 
 // two steps in one pass (a -> scratch-free: src -> dst holds f(t+2)); caller checked eligibility
 static int step_twice(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
-                      double omega) {
-  StepLaunch p = make_launch(s, src, dst, bcm, miss, omega);
+                      double omega, int64_t t) {
+  StepLaunch p = make_launch(s, src, dst, bcm, miss, omega, t);
   p.meta = s->meta;
   // hull tiles first pays when they are much more expensive than fluid tiles (halfway walls: redirected loads) and
   // with clean work items; otherwise (fullway / equilibrium boundaries alone) the XCD-compact patch is faster
@@ -1309,7 +1402,7 @@ static int step_twice(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* 
   p.strips_src = nullptr;
   p.strips_dst = nullptr;
   touch(dst);  // (new contents: whatever was cached on the old ones — its strip buffer — is stale)
-  if (s->edge_ext_ok) return step_twice_edge_ext(s, p, src, dst, bcm, miss, omega);
+  if (s->edge_ext_ok) return step_twice_edge_ext(s, p, src, dst, bcm, miss, omega, t);
   // strip buffers (step2_kernel.hpp): phase A's halo columns come from src's strips, phase B writes dst's.  D3Q19, the
   // bit-exact body, (8 x 64) tiles; a field whose strips are not those of its current contents gets them rebuilt first.
   xlbhip_field* srcw = const_cast<xlbhip_field*>(src);
@@ -1424,7 +1517,7 @@ static bool can_fuse2(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* 
     }
     s->edge_ext_ok = true;
   }
-  const StepLaunch p = make_launch(s, src, dst, bcm, miss, 1.0);
+  const StepLaunch p = make_launch(s, src, dst, bcm, miss, 1.0, 0);  // (the plan's inputs only: no launch)
   return step2_fuse(plan_case(s, p), (int)mode, fill_cus(s->ctx), (int)opt(s->ctx, "fuse2_xseg", 0), opt(s->ctx, "fuse2_clean", 1) != 0);
 }
 
@@ -1479,9 +1572,9 @@ static int prepare_fuse2(xlbhip_stepper* s, const xlbhip_field* bcm, const xlbhi
 
 // the step kernel(s) of one step src -> dst, with the slab halo protocol when the fields carry ghost planes
 static int step_kernels(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
-                     double omega) {
+                     double omega, int64_t t) {
   xlbhip_ctx* c = s->ctx;
-  StepLaunch p = make_launch(s, src, dst, bcm, miss, omega);
+  StepLaunch p = make_launch(s, src, dst, bcm, miss, omega, t);
   if (src->halo == 0) {
     p.x_begin = 0;
     p.x_count = src->nx;
@@ -1525,10 +1618,10 @@ static int step_kernels(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field
 
 // one step src -> dst; ExtrapolationOutflowBC cells get their auxiliary data afterwards (nse_stepper.py:270-272)
 static int step_once(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
-                     double omega) {
+                     double omega, int64_t t) {
   touch(dst);  // (its strip buffer, if any, no longer matches)
-  if (int rc = step_kernels(s, src, dst, bcm, miss, omega)) return rc;
-  return outflow_aux(s, src, dst, bcm, miss);
+  if (int rc = step_kernels(s, src, dst, bcm, miss, omega, t)) return rc;
+  return outflow_aux(s, src, dst, bcm, miss, t);
 }
 
 }  // namespace xlb
@@ -1601,14 +1694,11 @@ int xlbhip_stepper_create(xlbhip_ctx* c, int lattice, int collision, int cdt, in
   return 0;
 }
 
-int xlbhip_stepper_set_bc_profile(xlbhip_stepper* s, int bc_id, int64_t n, const uint32_t* storage_cells, const double* values) {
-  XLB_REQUIRE(s && bc_id >= 1 && bc_id <= 255, "bad argument");
-  XLB_REQUIRE(n == 0 || (storage_cells && values), "null table");
-  xlbhip_ctx* c = s->ctx;
-  XLB_HIP(hipSetDevice(c->device));
-  XLB_HIP(hipStreamSynchronize(c->stream));
-  for (int64_t i = 0; i < n; ++i) s->prof_host[storage_cells[i]] = {values[3 * i], values[3 * i + 1], values[3 * i + 2]};
-  // sorted device image (std::map iterates in key order)
+}  // extern "C"
+
+// the sorted device image of the merged table (std::map iterates in key order), its host copy, the rows of the time-dependent
+// cells in it, and the PROF_FLAG of bc_id; drops the ring (its images have the old layout).  The stream is drained.
+static int upload_prof_table(xlbhip_stepper* s, int bc_id) {
   std::vector<uint32_t> keys;
   std::vector<double> v64;
   keys.reserve(s->prof_host.size());
@@ -1640,11 +1730,143 @@ int xlbhip_stepper_set_bc_profile(xlbhip_stepper* s, int bc_id, int64_t n, const
   const double one64 = 1.0;
   XLB_HIP(hipMemcpy(static_cast<char*>(s->tab_values) + ((size_t)bc_id * 27 + PROF_FLAG) * es, es == 4 ? (const void*)&one32 : (const void*)&one64, es,
                     hipMemcpyHostToDevice));
+  if (s->td_cells.empty() && !s->ring) return 0;
+  s->prof_image.resize(v64.size() * es);
+  for (size_t i = 0; i < v64.size(); ++i) {
+    if (es == 4)
+      reinterpret_cast<float*>(s->prof_image.data())[i] = (float)v64[i];
+    else
+      reinterpret_cast<double*>(s->prof_image.data())[i] = v64[i];
+  }
+  s->td_pos.resize(s->td_cells.size());
+  for (size_t i = 0; i < s->td_cells.size(); ++i)
+    s->td_pos[i] = (int)(std::lower_bound(keys.begin(), keys.end(), s->td_cells[i]) - keys.begin());
+  s->td_contiguous = true;
+  for (size_t i = 0; i < s->td_pos.size(); ++i) s->td_contiguous = s->td_contiguous && s->td_pos[i] == s->td_pos[0] + (int)i;
+  free_ring(s);
   return 0;
+}
+
+extern "C" {
+
+int xlbhip_stepper_set_bc_profile(xlbhip_stepper* s, int bc_id, int64_t n, const uint32_t* storage_cells, const double* values) {
+  XLB_REQUIRE(s && bc_id >= 1 && bc_id <= 255, "bad argument");
+  XLB_REQUIRE(n == 0 || (storage_cells && values), "null table");
+  xlbhip_ctx* c = s->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipStreamSynchronize(c->stream));
+  for (int64_t i = 0; i < n; ++i) s->prof_host[storage_cells[i]] = {values[3 * i], values[3 * i + 1], values[3 * i + 2]};
+  return upload_prof_table(s, bc_id);
+}
+
+int xlbhip_stepper_set_bc_profile_cells(xlbhip_stepper* s, int bc_id, int64_t n, const uint32_t* storage_cells) {
+  XLB_REQUIRE(s && bc_id >= 1 && bc_id <= 255, "bad argument");
+  XLB_REQUIRE(n == 0 || storage_cells, "null cell list");
+  xlbhip_ctx* c = s->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  uint8_t kind = 0;
+  XLB_HIP(hipMemcpy(&kind, s->tab_kind + bc_id, 1, hipMemcpyDeviceToHost));
+  XLB_REQUIRE((kind >= XLBHIP_BC_HYBRID_BB_REGULARIZED && kind <= XLBHIP_BC_HYBRID_NEQ_REGULARIZED) || kind == XLBHIP_BC_HALFWAY_BB_PROFILE,
+              "time-dependent wall velocities: bc %d is of kind %d (HybridBC / HalfwayBounceBackBC with a profile)", bc_id, (int)kind);
+  XLB_HIP(hipStreamSynchronize(c->stream));
+  for (int64_t i = 0; i < n; ++i)
+    XLB_REQUIRE(s->prof_host.find(storage_cells[i]) == s->prof_host.end(), "cell %u has a profile table entry already", storage_cells[i]);
+  for (int64_t i = 0; i < n; ++i) {
+    s->prof_host[storage_cells[i]] = {0.0, 0.0, 0.0};  // (placeholder: every image carries this timestep's value)
+    s->td_cells.push_back(storage_cells[i]);
+  }
+  if (n > 0) s->td_bc[bc_id] = 1;
+  return upload_prof_table(s, bc_id);
+}
+
+int xlbhip_stepper_profile_slots(xlbhip_stepper* s, int* slots) {
+  XLB_REQUIRE(s && slots, "null argument");
+  *slots = has_td(s) ? ring_slot_count(s) : 0;
+  return 0;
+}
+
+int xlbhip_stepper_stage_bc_profiles(xlbhip_stepper* s, int64_t t_first, int64_t n_steps, const double* values) {
+  XLB_REQUIRE(s, "stepper is null");
+  XLB_REQUIRE(has_td(s), "this stepper has no time-dependent wall velocities (xlbhip_stepper_set_bc_profile_cells)");
+  XLB_REQUIRE(n_steps >= 0 && (n_steps == 0 || values), "bad argument");
+  xlbhip_ctx* c = s->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  if (int rc = ensure_ring(s)) return rc;
+  XLB_REQUIRE(n_steps <= s->ring_slots, "%lld tables staged at once, the ring holds %d (xlbhip_stepper_profile_slots)", (long long)n_steps,
+              s->ring_slots);
+  const size_t img = prof_image_bytes(s), nt = s->td_cells.size();
+  char* ring = static_cast<char*>(s->ring);
+  char* pin = static_cast<char*>(s->ring_pin);
+  std::vector<int64_t> pending((size_t)s->ring_slots, 0);  // timestep a filled row is about to carry
+  int run_first = 0, run_len = 0;
+  // one copy per run of consecutive slots, on the compute stream: it lands after every kernel enqueued so far (those that still
+  // read an older image of these slots) and before every launch that looks these timesteps up.  A slot counts as resident only
+  // once its copy is enqueued; if that fails, nothing of the run is claimed.
+  auto flush = [&]() -> int {
+    if (run_len == 0) return 0;
+    const size_t off = (size_t)run_first * img;
+    XLB_HIP(hipMemcpyAsync(ring + off, pin + off, (size_t)run_len * img, hipMemcpyHostToDevice, c->stream));
+    for (int k = run_first; k < run_first + run_len; ++k) {
+      if (hipError_t e = hipEventRecord(s->ring_ev[k], c->stream); e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);  // (no copy out of a pinned row may stay in flight behind a stale event)
+        XLB_FAIL("hipEventRecord: %s", hipGetErrorString(e));
+      }
+    }
+    for (int k = run_first; k < run_first + run_len; ++k) {
+      for (int j = 0; j < s->ring_slots; ++j)
+        if (s->ring_used[j] && s->ring_t[j] == pending[k]) s->ring_used[j] = 0;  // (an older image of that timestep: superseded)
+      s->ring_t[k] = pending[k];
+      s->ring_used[k] = 1;
+    }
+    run_len = 0;
+    return 0;
+  };
+  for (int64_t r = 0; r < n_steps; ++r) {
+    const int k = s->ring_head;
+    s->ring_head = (k + 1) % s->ring_slots;
+    if (k == 0)
+      if (int rc = flush()) return rc;
+    s->ring_used[k] = 0;  // (its image is about to be replaced)
+    XLB_HIP(hipEventSynchronize(s->ring_ev[k]));  // the previous copy out of this pinned row (not the kernels)
+    char* row = pin + (size_t)k * img;
+    if (!s->ring_pin_ready[k]) {
+      std::memcpy(row, s->prof_image.data(), img);
+      s->ring_pin_ready[k] = 1;
+    }
+    const double* v = values + (size_t)r * nt * 3;
+    // (one time-dependent BC, or several whose cells are not interleaved with others: one block of the table)
+    const size_t base = s->td_contiguous ? (size_t)s->td_pos[0] * 3 : 0;
+    if (s->cdt == XLBHIP_F32) {
+      float* d = reinterpret_cast<float*>(row);
+      if (s->td_contiguous) {
+        for (size_t i = 0; i < 3 * nt; ++i) d[base + i] = (float)v[i];
+      } else {
+        for (size_t i = 0; i < nt; ++i)
+          for (int a = 0; a < 3; ++a) d[(size_t)s->td_pos[i] * 3 + a] = (float)v[i * 3 + a];
+      }
+    } else {
+      double* d = reinterpret_cast<double*>(row);
+      if (s->td_contiguous) {
+        std::memcpy(d + base, v, 3 * nt * sizeof(double));
+      } else {
+        for (size_t i = 0; i < nt; ++i)
+          for (int a = 0; a < 3; ++a) d[(size_t)s->td_pos[i] * 3 + a] = v[i * 3 + a];
+      }
+    }
+    pending[k] = t_first + r;
+    if (run_len == 0) run_first = k;
+    ++run_len;
+  }
+  return flush();
 }
 
 int xlbhip_stepper_momentum_transfer(xlbhip_stepper* s, int bc_id, const xlbhip_field* f_0, const xlbhip_field* bcm, const xlbhip_field* miss,
                                      double force_out[3]) {
+  return xlbhip_stepper_momentum_transfer_at(s, bc_id, 0, f_0, bcm, miss, force_out);
+}
+
+int xlbhip_stepper_momentum_transfer_at(xlbhip_stepper* s, int bc_id, int64_t timestep, const xlbhip_field* f_0, const xlbhip_field* bcm,
+                                        const xlbhip_field* miss, double force_out[3]) {
   XLB_REQUIRE(s && force_out && bc_id >= 1 && bc_id <= 255, "bad argument");
   xlbhip_ctx* c = s->ctx;
   XLB_CHECK_POP(f_0, s->lattice, "momentum_transfer(f_0)");
@@ -1657,6 +1879,10 @@ int xlbhip_stepper_momentum_transfer(xlbhip_stepper* s, int bc_id, const xlbhip_
   XLB_REQUIRE((kind >= XLBHIP_BC_HYBRID_BB_REGULARIZED && kind <= XLBHIP_BC_HYBRID_NEQ_REGULARIZED) || kind == XLBHIP_BC_HALFWAY_BB_PROFILE,
               "momentum_transfer through the stepper: bc %d is of kind %d (HybridBC / profile walls; plain walls use xlbhip_momentum_transfer)", bc_id,
               (int)kind);
+  // a time-dependent wall: the wall velocities of this timestep.  Any other BC: the single table (the kernel reads entries of bc_id's
+  // cells only, and every staged image carries the same static entries), whatever is staged.
+  const void* pv = s->td_bc[bc_id] ? prof_table_at(s, timestep) : s->prof_vals;
+  XLB_REQUIRE(s->n_prof == 0 || pv, "momentum_transfer: the time-dependent wall velocities of timestep %lld are not staged", (long long)timestep);
   double* dforce = nullptr;
   XLB_HIP(hipMalloc(&dforce, 3 * sizeof(double)));
   XLB_HIP(hipMemsetAsync(dforce, 0, 3 * sizeof(double), c->stream));
@@ -1665,11 +1891,11 @@ int xlbhip_stepper_momentum_transfer(xlbhip_stepper* s, int bc_id, const xlbhip_
     using LL = decltype(L);
     if (s->cdt == XLBHIP_F32)
       hipLaunchKernelGGL((k_momentum_transfer_tab<LL, float>), blocks_for(n), 256, 0, c->stream, view(f_0), view(bcm), view(miss), dims(f_0), bc_id,
-                         s->tab_kind, static_cast<const float*>(s->tab_values), s->prof_keys, static_cast<const float*>(s->prof_vals), s->n_prof,
+                         s->tab_kind, static_cast<const float*>(s->tab_values), s->prof_keys, static_cast<const float*>(pv), s->n_prof,
                          s->dist_keys, s->dist_vals, s->n_dist, dforce);
     else
       hipLaunchKernelGGL((k_momentum_transfer_tab<LL, double>), blocks_for(n), 256, 0, c->stream, view(f_0), view(bcm), view(miss), dims(f_0), bc_id,
-                         s->tab_kind, static_cast<const double*>(s->tab_values), s->prof_keys, static_cast<const double*>(s->prof_vals), s->n_prof,
+                         s->tab_kind, static_cast<const double*>(s->tab_values), s->prof_keys, static_cast<const double*>(pv), s->n_prof,
                          s->dist_keys, s->dist_vals, s->n_dist, dforce);
     XLB_HIP(hipGetLastError());
     return 0;
@@ -1743,6 +1969,7 @@ int xlbhip_stepper_destroy(xlbhip_stepper* s) {
   if (s->prof_vals) (void)hipFree(s->prof_vals);
   if (s->dist_keys) (void)hipFree(s->dist_keys);
   if (s->dist_vals) (void)hipFree(s->dist_vals);
+  free_ring(s);
   if (s->scratch) xlbhip_field_destroy(s->scratch);
   if (s->meta) {
     comm_forget_buffer(s->ctx, s->meta);
@@ -1756,17 +1983,19 @@ int xlbhip_stepper_destroy(xlbhip_stepper* s) {
 
 int xlbhip_step(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
                 double omega, int64_t timestep) {
-  (void)timestep;  // only time-dependent BC profiles use it in the reference (out of scope)
+  // the timestep selects the wall velocities of time-dependent profiles (nse_stepper.py:370-378 passes it to every BC functional)
   if (int rc = check_step_fields(s, src, dst, bcm, miss)) return rc;
-  return step_once(s, src, dst, bcm, miss, omega);
+  if (int rc = require_staged(s, timestep, 1)) return rc;
+  return step_once(s, src, dst, bcm, miss, omega, timestep);
 }
 
 // n steps; `fixed_placement`: the result must land in f_a for even n and in f_b for odd n (xlbhip_run's contract);
 // otherwise every pair of steps is fused and *result_in_b reports where the result is (xlbhip_run_any)
 static int run_steps(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const xlbhip_field* bcm, const xlbhip_field* miss, double omega,
-                     int64_t n, bool fixed_placement, int* result_in_b) {
+                     int64_t t0, int64_t n, bool fixed_placement, int* result_in_b) {
   XLB_REQUIRE(n >= 0, "n_steps < 0");
   if (int rc = check_step_fields(s, a, b, bcm, miss)) return rc;
+  if (int rc = require_staged(s, t0, n)) return rc;
   // With two-step fusion ("fuse2") a pair of steps is ONE pass a -> b: pairs alternate direction (a -> b, b -> a, ...).
   // Under the fixed placement contract a trailing half pair (buffer parity) is fixed up by single steps.
   int64_t i = 0;
@@ -1789,7 +2018,7 @@ static int run_steps(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const 
     // P + r must be congruent to n (mod 2)  <=>  P even.  Use the largest even P with 2P <= n.
     int64_t pairs = fixed_placement ? ((n / 2) & ~int64_t(1)) : n / 2;
     for (int64_t k = 0; k < pairs; ++k) {
-      if (int rc = step_twice(s, cur, oth, bcm, miss, omega)) return rc;
+      if (int rc = step_twice(s, cur, oth, bcm, miss, omega, t0 + 2 * k)) return rc;
       xlbhip_field* tmp = cur;
       cur = oth;
       oth = tmp;
@@ -1797,7 +2026,7 @@ static int run_steps(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const 
     i = 2 * pairs;
   }
   for (; i < n; ++i) {
-    if (int rc = step_once(s, cur, oth, bcm, miss, omega)) return rc;
+    if (int rc = step_once(s, cur, oth, bcm, miss, omega, t0 + i)) return rc;
     xlbhip_field* tmp = cur;
     cur = oth;
     oth = tmp;
@@ -1808,15 +2037,13 @@ static int run_steps(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const 
 
 int xlbhip_run(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const xlbhip_field* bcm, const xlbhip_field* miss, double omega,
                int64_t t0, int64_t n) {
-  (void)t0;
-  return run_steps(s, a, b, bcm, miss, omega, n, true, nullptr);
+  return run_steps(s, a, b, bcm, miss, omega, t0, n, true, nullptr);
 }
 
 int xlbhip_run_any(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const xlbhip_field* bcm, const xlbhip_field* miss, double omega,
                    int64_t t0, int64_t n, int* result_in_b) {
-  (void)t0;
   XLB_REQUIRE(result_in_b, "result_in_b is null");
-  return run_steps(s, a, b, bcm, miss, omega, n, false, result_in_b);
+  return run_steps(s, a, b, bcm, miss, omega, t0, n, false, result_in_b);
 }
 
 int xlbhip_step2_eligible(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss) {
@@ -1826,11 +2053,11 @@ int xlbhip_step2_eligible(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_fie
 
 int xlbhip_step2(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
                  double omega, int64_t timestep) {
-  (void)timestep;
   if (int rc = check_step_fields(s, src, dst, bcm, miss)) return rc;
+  if (int rc = require_staged(s, timestep, 2)) return rc;
   XLB_REQUIRE(can_fuse2(s, src, dst, bcm, miss), "this stepper / field layout has no two-step kernel (see xlbhip_step2_eligible)");
   if (int rc = prepare_fuse2(s, bcm, miss)) return rc;
-  return step_twice(s, src, dst, bcm, miss, omega);
+  return step_twice(s, src, dst, bcm, miss, omega, timestep);
 }
 
 int xlbhip_run_timed(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const xlbhip_field* bcm, const xlbhip_field* miss, double omega,
@@ -1839,7 +2066,7 @@ int xlbhip_run_timed(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const 
   xlbhip_ctx* c = s->ctx;
   XLB_HIP(hipEventRecord(c->ev_a, c->stream));
   // (result_in_b == NULL: xlbhip_run's fixed placement; else as xlbhip_run_any)
-  if (int rc = run_steps(s, a, b, bcm, miss, omega, n, result_in_b == nullptr, result_in_b)) return rc;
+  if (int rc = run_steps(s, a, b, bcm, miss, omega, t0, n, result_in_b == nullptr, result_in_b)) return rc;
   XLB_HIP(hipEventRecord(c->ev_b, c->stream));
   XLB_HIP(hipEventSynchronize(c->ev_b));
   XLB_HIP(hipEventElapsedTime(ms, c->ev_a, c->ev_b));

@@ -10,6 +10,7 @@ Each BC is (a) a stand-alone operator ``bc(f_pre, f_post, bc_mask, missing_mask)
 and (b) a descriptor consumed by the fused stepper kernel (``_hip_descriptor``).
 """
 
+import inspect
 from enum import Enum, auto
 
 import numpy as np
@@ -53,6 +54,41 @@ class _GridOfField:
             raise NotImplementedError("the stand-alone call of a profile BC needs fields without ghost planes; use the stepper")
         self.shape = self.local_shape = field.grid_shape
         self.x_offset, self.halo = 0, 0
+
+
+def profile_is_time_dependent(profile):
+    """The reference's rule (bc_hybrid.py:163-172): a wall-velocity profile with more than one parameter is ``profile(index, timestep)``.
+    A callable whose signature cannot be inspected is time-independent."""
+    try:
+        return len(inspect.signature(profile).parameters) > 1
+    except (TypeError, ValueError):
+        return False
+
+
+class _TimeDependentWall:
+    """A wall velocity ``profile(cells, timestep)`` of HalfwayBounceBackBC / HybridBC (bc_halfway_bounce_back.py:147-155,
+    bc_hybrid.py:228-239).  The stepper evaluates it on the host ahead of the device, once per timestep, and stages the values as that
+    step's profile table.  It must be a pure function of (cells, timestep): the same timestep may be evaluated more than once (when a
+    field left virtual by a fused pair is read, when a force is computed)."""
+
+    def _declare_time_dependent(self, cells, storage_keys):
+        self._td_cells = cells[3 - self.velocity_set.d :]
+        self._td_keys = np.asarray(storage_keys, dtype=np.uint32)
+        self._profile_table_data = None
+        self.profile_at(0)  # (fails early on a wrong shape)
+
+    def profile_at(self, timestep, out=None):
+        """(n, 3) wall velocities of this BC's cells at ``timestep``: internal 3-component form, rounded to the compute dtype.  Written
+        into ``out`` (an (n, 3) float64 array, e.g. a slice of the stepper's staging rows) when given."""
+        d, n = self.velocity_set.d, self._td_cells.shape[1]
+        t = int(timestep)
+        vals = np.asarray(self.profile(self._td_cells, t), dtype=np.float64)
+        if vals.shape != (d, n):
+            raise ValueError(f"profile(indices, timestep) at t={t} must return an array of shape (d, n) = {(d, n)}, got {vals.shape}")
+        v3 = np.empty((n, 3)) if out is None else out
+        v3[:, : 3 - d] = 0.0
+        v3[:, 3 - d :] = vals.T.astype(self.compute_dtype)  # (rounded to the compute dtype, widened back exactly by the assignment)
+        return v3
 
 
 class BoundaryCondition(Operator):
@@ -157,9 +193,10 @@ class EquilibriumBC(BoundaryCondition):
         return self._apply(f_pre, f_post, bc_mask, missing_mask)
 
 
-class HalfwayBounceBackBC(BoundaryCondition):
+class HalfwayBounceBackBC(_TimeDependentWall, BoundaryCondition):
     """Missing populations are replaced by the opposite pre-streaming population of the same
-    cell (+ 6 w_l c_l.u_wall for a moving wall), after streaming."""
+    cell (+ 6 w_l c_l.u_wall for a moving wall), after streaming.  ``profile``: the wall velocity per boundary cell,
+    ``profile(cells)`` or, time-dependent, ``profile(cells, timestep)`` (a pure function: see _TimeDependentWall)."""
 
     hip_kind = _lib.BC_HALFWAY_BB
 
@@ -177,6 +214,7 @@ class HalfwayBounceBackBC(BoundaryCondition):
             # bc_halfway_bounce_back.py:76-96): evaluated by the stepper at this BC's cells, a sparse table for the kernel
             self.hip_kind = _lib.BC_HALFWAY_BB_PROFILE
         self.profile = profile
+        self.is_time_dependent = profile is not None and profile_is_time_dependent(profile)
         self._profile_table_data = None
         self.needs_moving_wall_treatment = prescribed_value is not None or profile is not None
         if prescribed_value is None and profile is not None:
@@ -192,6 +230,8 @@ class HalfwayBounceBackBC(BoundaryCondition):
 
     def _evaluate_profile(self, cells, storage_keys):
         """Called by the stepper with this BC's cells ((3, n) global indices, x first) and their storage cell indices."""
+        if self.is_time_dependent:
+            return self._declare_time_dependent(cells, storage_keys)
         d = self.velocity_set.d
         vals = np.asarray(self.profile(cells[3 - d :]), dtype=np.float64)
         if vals.shape != (d, cells.shape[1]):
@@ -431,21 +471,22 @@ class ExtrapolationOutflowBC(BoundaryCondition):
         return self._apply(f_pre, f_post, bc_mask, missing_mask)
 
 
-class HybridBC(BoundaryCondition):
+class HybridBC(_TimeDependentWall, BoundaryCondition):
     """Curved / moving wall boundary condition of the reference's kernel backends (bc_hybrid.py:40-391), 3-D only:
 
     * ``"bounceback_regularized"``  interpolated bounce-back (Bouzidi / Yu et al.) + Latt regularisation,
     * ``"bounceback_grads"``        interpolated bounce-back + Grad's approximation of the missing populations,
     * ``"nonequilibrium_regularized"``  Tao et al.'s non-equilibrium bounce-back + regularisation.
 
-    ``prescribed_value`` = constant wall velocity (moving-wall treatment), none = no-slip; ``profile`` = a time-independent wall velocity
-    per boundary cell (the reference's ``profile(index)`` Warp function, bc_hybrid.py:163-172, 265 — e.g. a rotating body,
+    ``prescribed_value`` = constant wall velocity (moving-wall treatment), none = no-slip; ``profile`` = a wall velocity per boundary cell
+    (the reference's ``profile(index)`` Warp function, bc_hybrid.py:163-172, 265 — e.g. a rotating body,
     examples/cfd/rotating_sphere_3d.py:114-131): here a Python callable that takes the (3, n) integer array of this BC's cell indices and
     returns the (3, n) velocities; the stepper evaluates it once the masks exist and hands the values to the kernel as a sparse
-    per-cell table.  ``use_mesh_distance`` needs
+    per-cell table.  A profile with two parameters, ``profile(cells, timestep)`` (the reference's rule: more than one parameter), is
+    time-dependent: the stepper evaluates it on the host for every timestep ahead of the device and stages one table per step; it must
+    be a pure function of (cells, timestep).  ``use_mesh_distance`` needs
     ``mesh_vertices`` and a voxelisation method with distances (RAY, WINDING, AABB_CLOSE): the interpolation then uses the
-    fractional distance to the surface along every cut link instead of the halfway assumption.  Time-dependent profiles
-    (``profile(index, timestep)``) are out of scope."""
+    fractional distance to the surface along every cut link instead of the halfway assumption."""
 
     _kinds = {"bounceback_regularized": _lib.BC_HYBRID_BB_REGULARIZED, "bounceback_grads": _lib.BC_HYBRID_BB_GRADS,
               "nonequilibrium_regularized": _lib.BC_HYBRID_NEQ_REGULARIZED}
@@ -467,6 +508,7 @@ class HybridBC(BoundaryCondition):
             if not callable(profile):
                 raise ValueError("profile must be a callable: cell indices (3, n) -> wall velocities (3, n)")
         self.profile = profile
+        self.is_time_dependent = profile is not None and profile_is_time_dependent(profile)
         self._profile_table_data = None  # (storage cells, (n, 3) values): the stepper evaluates the profile at this BC's cells
         self.needs_moving_wall_treatment = prescribed_value is not None or profile is not None
         if prescribed_value is None and profile is not None:
@@ -491,6 +533,8 @@ class HybridBC(BoundaryCondition):
 
     def _evaluate_profile(self, cells, storage_keys):
         """Called by the stepper with this BC's cells ((3, n) global indices) and their storage cell indices."""
+        if self.is_time_dependent:
+            return self._declare_time_dependent(cells, storage_keys)
         vals = np.asarray(self.profile(cells), dtype=np.float64)
         if vals.shape != (3, cells.shape[1]):
             raise ValueError(f"profile(indices) must return an array of shape (3, n) = {(3, cells.shape[1])}, got {vals.shape}")

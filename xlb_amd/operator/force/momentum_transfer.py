@@ -26,7 +26,9 @@ class MomentumTransfer(Operator):
             raise NotImplementedError("MomentumTransfer supports halfway / fullway bounce-back walls and HybridBC on the HIP backend")
 
     @Operator.register_backend(ComputeBackend.HIP)
-    def hip_implementation(self, f_0, f_1, bc_mask, missing_mask):
+    def hip_implementation(self, f_0, f_1, bc_mask, missing_mask, timestep=0):
+        """``timestep``: the step whose wall velocities a time-dependent wall (``profile(cells, timestep)``) has; the reference
+        evaluates it at 0 (momentum_transfer.py:88), the default here.  Other walls ignore it."""
         if self._via_stepper:
             # HybridBC / profile walls: the BC's post-stream populations need the wall-distance and wall-velocity tables, which
             # live in the stepper the BC belongs to (the reference applies bc.warp_functional here, momentum_transfer.py:75-92)
@@ -34,7 +36,7 @@ class MomentumTransfer(Operator):
             stepper = owner() if owner is not None else None
             if stepper is None:
                 raise RuntimeError("MomentumTransfer(HybridBC): the BC is not part of a live stepper (stepper.prepare_fields() comes first)")
-            force = stepper._native_stepper().momentum_transfer(self.no_slip_bc_instance.id, f_0, bc_mask, missing_mask)
+            force = stepper._momentum_transfer(self.no_slip_bc_instance, f_0, bc_mask, missing_mask, int(timestep))
             return force[3 - self.velocity_set.d :].astype(self.compute_dtype)
         desc = self.no_slip_bc_instance._hip_descriptor()
         out = (C.c_double * 3)()

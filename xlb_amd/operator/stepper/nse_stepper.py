@@ -23,7 +23,13 @@ to single steps.  After a fused pair the field that received step t+1 in the ref
 (the fused pass writes f(t+2) next to f(t), and the two field objects exchange their device buffers): if it is read
 before the next call overwrites it, it is materialised through a temporary third field.  Fields exported through DLPack /
 ``__cuda_array_interface__`` are never deferred (their memory must stay put); ``backend_config={"lazy_pairs": False}``
-switches the mechanism off."""
+switches the mechanism off.
+
+**Time-dependent walls.**  A HalfwayBounceBackBC / HybridBC with ``profile(cells, timestep)`` gets one profile table per timestep:
+the host evaluates the profile and stages the values (``xlbhip_stepper_stage_bc_profiles``: a ring of device slots, asynchronous
+copies on the compute stream) before the launch that reads them; the step from f(t) to f(t+1) uses ``profile(cells, t)``.  A
+reference-style call stages its own timestep; a deferred call at t pairs only with a call at t + 1; ``run`` stages chunks of at most
+half the ring and evaluates the next chunk while the device runs the current one."""
 
 import numpy as np
 
@@ -40,6 +46,21 @@ from ..macroscopic import Macroscopic
 from ..operator import Operator
 from ..stream import Stream
 from .stepper import Stepper
+
+
+def chunk_plan(n_steps, ring_slots):
+    """Chunk sizes of a run with time-dependent walls: at most half the ring (the next chunk is staged while the device still reads
+    this one's tables) and even, so that pairs of steps stay pairs; only the last chunk may be odd.  (Chunks that start at 2 and
+    double measured slower at 512^3 — the device idles at every doubling: profiles/time_dependent_walls.md.)"""
+    size = max(2, (int(ring_slots) // 2) & ~1)
+    n = int(n_steps)
+    return [min(size, n - i) for i in range(0, n, size)]
+
+
+def pairs_in_time(t_deferred, timestep, time_dependent):
+    """May a deferred call at t_deferred be fused with a call at `timestep`?  Always without time-dependent walls (the timestep does not
+    enter the step); with them only when the call is the next timestep — the fused pair runs steps t and t + 1."""
+    return not time_dependent or int(timestep) == int(t_deferred) + 1
 
 
 class _Materialise:
@@ -68,6 +89,7 @@ class IncompressibleNavierStokesStepper(Stepper):
         self.forcing_scheme = forcing_scheme
         self.force_vector = force_vector
         self._native = None
+        self._td_bcs, self._td_slots = [], 0  # BCs with time-dependent wall velocities (declaration order) and the ring's slot count
         self._deferred = None   # (f_src, f_dst, bc_mask, missing_mask, omega, timestep): a step not enqueued yet
         self._n_fused_pairs = self._n_materialised = 0  # statistics of the pairing (tests, diagnostics)
         super().__init__(grid, boundary_conditions)
@@ -98,6 +120,13 @@ class IncompressibleNavierStokesStepper(Stepper):
                 table = bc._profile_table(self.grid) if hasattr(bc, "_profile_table") else None
                 if table is not None:
                     self._native.set_bc_profile(bc.id, *table)
+            for bc in self.boundary_conditions:
+                keys = getattr(bc, "_td_keys", None) if getattr(bc, "is_time_dependent", False) else None
+                if keys is not None and keys.size > 0:
+                    self._native.set_bc_profile_cells(bc.id, keys)
+                    self._td_bcs.append(bc)
+            if self._td_bcs:
+                self._td_slots = self._native.profile_slots()
             for bc in self.boundary_conditions:
                 table = getattr(bc, "_distance_table", None)
                 if table is not None:
@@ -156,8 +185,34 @@ class IncompressibleNavierStokesStepper(Stepper):
     @Operator.register_backend(ComputeBackend.HIP)
     def hip_implementation(self, f_0, f_1, bc_mask, missing_mask, omega, timestep):
         if not self._lazy_pair(f_0, f_1, bc_mask, missing_mask, omega, timestep):
+            self._stage(timestep, 1)
             self._native_stepper().step(f_0, f_1, bc_mask, missing_mask, omega, timestep)
         return f_0, f_1
+
+    # -- time-dependent wall velocities (module docstring) ---------------------------------------------------------
+    def _time_dependent_bcs(self):
+        self._native_stepper()
+        return self._td_bcs
+
+    def _td_rows(self, t_first, n):
+        """(n, cells, 3) wall velocities of the time-dependent BCs' cells (declaration order) at t_first .. t_first + n - 1, written in
+        place into ONE staging buffer that every call reuses (stage_bc_profiles has copied the previous rows when it returned)."""
+        sizes = [bc._td_keys.size for bc in self._td_bcs]
+        buf = getattr(self, "_td_buf", None)
+        if buf is None or buf.shape[0] < n:
+            buf = self._td_buf = np.empty((max(n, self._td_slots // 2), sum(sizes), 3))
+        rows = buf[:n]
+        for k in range(n):
+            o = 0
+            for bc, m in zip(self._td_bcs, sizes):
+                bc.profile_at(int(t_first) + k, out=rows[k, o : o + m])
+                o += m
+        return rows
+
+    def _stage(self, t_first, n):
+        """Evaluate and stage the tables of timesteps t_first .. t_first + n - 1 (nothing without time-dependent walls)."""
+        if self._time_dependent_bcs():
+            self._native.stage_bc_profiles(int(t_first), self._td_rows(t_first, n))
 
     # -- pairing of reference-style calls (module docstring) ------------------------------------------------------
     def _lazy_eligible(self, f_0, f_1, bc_mask, missing_mask):
@@ -189,6 +244,7 @@ class IncompressibleNavierStokesStepper(Stepper):
         f_src, f_dst, bcm, miss, omega, t = d
         self._unhook(f_src, f_dst, bcm, miss)
         try:
+            self._stage(t, 1)
             self._native_stepper().step(f_src, f_dst, bcm, miss, omega, t)
         except BaseException:
             # not enqueued: the step stays owed (the next use of any of its fields tries again and raises again)
@@ -206,11 +262,13 @@ class IncompressibleNavierStokesStepper(Stepper):
 
     def _materialise(self, field, bcm, miss, omega, t):
         """`field` should hold f(t+1) but its buffer holds f(t) (a fused pair passed it by): one single step through a
-        temporary field, whose buffer the field then adopts."""
+        temporary field, whose buffer the field then adopts.  (Time-dependent walls: t's table is staged again — the ring may
+        have moved on since the pair — from the same pure profile.)"""
         # the temporary comes first: if it cannot be allocated this raises with the hook still owed (Field.handle puts it
         # back), so the next reader raises again instead of being handed f(t) for f(t+1)
         tmp = self.grid.create_field(cardinality=self.velocity_set.q, dtype=self.precision_policy.store_precision)
         try:
+            self._stage(t, 1)
             self._native_stepper().step(field, tmp, bcm, miss, omega, t)  # (field._hook is None while its hook runs)
         except BaseException:
             tmp.free()
@@ -226,13 +284,16 @@ class IncompressibleNavierStokesStepper(Stepper):
         d = self._deferred
         if d is not None:
             f_src, f_dst, bcm, miss, om, t = d
-            if f_0 is f_dst and f_1 is f_src and bc_mask is bcm and missing_mask is miss and float(omega) == om and not (f_0._pinned or f_1._pinned):
+            if (f_0 is f_dst and f_1 is f_src and bc_mask is bcm and missing_mask is miss and float(omega) == om and not (f_0._pinned or f_1._pinned)
+                    and pairs_in_time(t, timestep, bool(self._time_dependent_bcs()))):
                 # the caller swapped the fields: steps t and t + 1 in one pass, f(t) in f_src's buffer -> f(t+2) in f_dst's
                 self._deferred = None
                 self._unhook(f_src, f_dst, bcm, miss)
                 if not self._native_stepper().step2_eligible(f_src, f_dst, bcm, miss):  # (an option changed in between)
+                    self._stage(t, 1)
                     self._native_stepper().step(f_src, f_dst, bcm, miss, om, t)
                     return False
+                self._stage(t, 2)
                 self._native_stepper().step2(f_src, f_dst, bcm, miss, om, t)
                 self._n_fused_pairs += 1
                 # the reference's protocol leaves f(t+2) in THIS call's f_1 (= f_src) and f(t+1) in its f_0 (= f_dst):
@@ -269,29 +330,74 @@ class IncompressibleNavierStokesStepper(Stepper):
         self._drop_virtual_destination(f_1, n_steps)
         if f_0.halo > 0 and self._ctx.get_option("external_halo"):
             return self._run_host_staged(f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep)
+        if self._time_dependent_bcs():
+            return self._run_chunked(f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep)
         in_b = self._native_stepper().run(f_0, f_1, bc_mask, missing_mask, omega, first_timestep, n_steps)
         return (f_1, f_0) if in_b else (f_0, f_1)
 
     def run_timed(self, f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep=0):
-        """As :meth:`run`; also returns the device time in ms measured with HIP events."""
+        """As :meth:`run`; also returns the device time in ms measured with HIP events.  (Host-staged transports and time-dependent
+        walls: the wall clock between two synchronisations — those loops interleave host work with the device's.)"""
         self._flush_deferred()
         self._drop_virtual_destination(f_1, n_steps)
-        if f_0.halo > 0 and self._ctx.get_option("external_halo"):
+        host_staged = f_0.halo > 0 and self._ctx.get_option("external_halo")
+        if host_staged or self._time_dependent_bcs():
             import time
 
-            self._ctx.sync()  # host-staged transport: no native loop to bracket with events; wall clock instead
+            self._ctx.sync()  # no single native loop to bracket with events; wall clock instead
             t0 = time.perf_counter()
-            out = self._run_host_staged(f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep)
+            if host_staged:
+                out = self._run_host_staged(f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep)
+            else:
+                out = self._run_chunked(f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep)
             self._ctx.sync()
             return out, (time.perf_counter() - t0) * 1e3
         in_b, ms = self._native_stepper().run_timed(f_0, f_1, bc_mask, missing_mask, omega, first_timestep, n_steps)
         return ((f_1, f_0) if in_b else (f_0, f_1)), ms
+
+    def _run_chunked(self, f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep):
+        """The native run loop in chunks (chunk_plan) for a stepper with time-dependent walls: every chunk's tables are staged before
+        its xlbhip_run_any, and the next chunk's profiles are evaluated while the device runs this one (nothing here waits for it).
+
+        A profile that raises in the first chunk stops the run before anything is enqueued.  One that raises later leaves the chunks
+        before it enqueued: the exception then carries ``timestep_reached`` (the run holds f(t) for that t) and ``fields`` = (the field
+        holding it, the other one), and its message says so."""
+        native = self._native
+        cur, oth, t = f_0, f_1, int(first_timestep)
+        plan = chunk_plan(n_steps, self._td_slots)
+        rows = self._td_rows(t, plan[0]) if plan else None
+        for i, k in enumerate(plan):
+            native.stage_bc_profiles(t, rows)
+            if native.run(cur, oth, bc_mask, missing_mask, omega, t, k):
+                cur, oth = oth, cur
+            t += k
+            if i + 1 < len(plan):
+                try:
+                    rows = self._td_rows(t, plan[i + 1])
+                except Exception as e:
+                    where = "f_0" if cur is f_0 else "f_1"
+                    e.timestep_reached, e.fields = t, (cur, oth)
+                    e.args = (f"{e.args[0] if e.args else e} (the run stopped at timestep {t}: f({t}) is in the field passed as {where})",) + e.args[1:]
+                    raise
+        return cur, oth
+
+    def _momentum_transfer(self, bc, f_0, bc_mask, missing_mask, timestep=0):
+        """MomentumTransfer of a HybridBC / profile wall of this stepper; a time-dependent wall with its velocities at `timestep`."""
+        native = self._native_stepper()
+        if bc not in self._td_bcs:
+            return native.momentum_transfer(bc.id, f_0, bc_mask, missing_mask)
+        for fld in (f_0, bc_mask, missing_mask):
+            fld.handle  # (deferred work on these fields runs first: it stages its own tables)
+        self._stage(timestep, 1)
+        return native.momentum_transfer_at(bc.id, timestep, f_0, bc_mask, missing_mask)
 
     def _run_host_staged(self, f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep):
         """The native run loop with the ghost planes moved by the host (``init_process_group(transport="host")``):
         same kernels and the same pairing of steps as ``xlbhip_run``, the debugging transport in between."""
         from ...distribute import HostStagedHalo, all_reduce_min
 
+        if self._time_dependent_bcs():
+            raise NotImplementedError("time-dependent wall-velocity profiles run on a single rank (fields without ghost planes)")
         native = self._native_stepper()
         halo = HostStagedHalo(self.grid, self.velocity_set)
         cur, oth, i = f_0, f_1, 0
