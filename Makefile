@@ -7,7 +7,7 @@ LIB       ?= xlb_amd/lib/libxlbhip.so
 # -ffp-contract=off: fp32/fp64 results are bit-identical to the oracle's operation order
 EXTRA     ?=
 HIPFLAGS  := $(EXTRA) --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fPIC -Wall -Wno-unused-function -Iinclude
-SRCS      := api.hip comm.cpp step_d2q9_bgk.hip step_d2q9_kbc.hip step_d3q19_bgk.hip step_d3q27_bgk.hip step_d3q27_kbc.hip step_d3q27_kbc_fast.hip \
+SRCS      := api.hip masker.hip stepper.hip comm.cpp step_d2q9_bgk.hip step_d2q9_kbc.hip step_d3q19_bgk.hip step_d3q27_bgk.hip step_d3q27_kbc.hip step_d3q27_kbc_fast.hip \
              step_d2q9_ext.hip step_d3q19_ext.hip step_d3q27_ext.hip step2_d3q19.hip step2_d3q19_strips.hip step2_d3q27.hip yardstick.hip
 OBJS      := $(addprefix $(OBJDIR)/,$(addsuffix .o,$(basename $(SRCS))))
 HDRS      := $(wildcard $(CSRC)/*.hpp) include/xlbhip.h
@@ -35,15 +35,25 @@ oracle: oracle/liblbmref.so
 oracle/liblbmref.so: oracle/lbm_ref.c oracle/lbm_ref_body.inc
 	gcc -O2 -fPIC -shared -fopenmp -ffp-contract=off -fno-fast-math -o $@ $< -lm
 
-# Host-side AddressSanitizer / UBSan build (tools/asan_host.py): only the two translation units with host logic are
-# instrumented, for the host compilation only; the kernel objects are the ordinary ones.  ~12 minutes (api.hip's device pass).
+# Host-side AddressSanitizer / UBSan build (tools/asan_host.py): only the translation units with host logic (api, masker, stepper,
+# comm) are instrumented, for the host compilation only; the kernel objects are the ordinary ones.  Their device passes are compiled
+# again (minutes each; run with -j to overlap them).
 ASANDIR := build/asan
 ASANFLAGS := --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -fPIC -Iinclude -fsanitize=address,undefined -fno-gpu-sanitize -fno-omit-frame-pointer
-asan: $(LIB)
+ASANSRCS := api.hip masker.hip stepper.hip comm.cpp
+ASANOBJS := $(addprefix $(ASANDIR)/,$(addsuffix .o,$(basename $(ASANSRCS))))
+HOSTOBJS := $(addprefix $(OBJDIR)/,$(addsuffix .o,$(basename $(ASANSRCS))))
+
+$(ASANDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(ASANDIR)
-	$(HIPCC) $(ASANFLAGS) -c $(CSRC)/api.hip -o $(ASANDIR)/api.o
-	$(HIPCC) $(ASANFLAGS) -x hip -c $(CSRC)/comm.cpp -o $(ASANDIR)/comm.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -fsanitize=address,undefined -o $(ASANDIR)/libxlbhip_asan.so $(ASANDIR)/api.o $(ASANDIR)/comm.o $(filter-out $(OBJDIR)/api.o $(OBJDIR)/comm.o,$(OBJS)) -ldl
+	$(HIPCC) $(ASANFLAGS) -c $< -o $@
+
+$(ASANDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
+	@mkdir -p $(ASANDIR)
+	$(HIPCC) $(ASANFLAGS) -x hip -c $< -o $@
+
+asan: $(LIB) $(ASANOBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -fsanitize=address,undefined -o $(ASANDIR)/libxlbhip_asan.so $(ASANOBJS) $(filter-out $(HOSTOBJS),$(OBJS)) -ldl
 
 clean:
 	rm -rf build xlb_amd/lib/libxlbhip.so oracle/liblbmref.so

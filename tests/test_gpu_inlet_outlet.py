@@ -304,7 +304,7 @@ def test_flow_past_sphere_vs_golden():
 @pytest.mark.parametrize("outlet", ["outflow", "pressure"])
 def test_two_step_kernel_with_inlet_outlet_planes(outlet, steps):
     """Steppers whose Zou-He / Regularized / outflow cells all sit in the planes x = 0 and x = nx-1 still use the two-step
-    kernel for the planes 2 .. nx-3; the four end planes go through the single-step kernel twice (api.hip:
+    kernel for the planes 2 .. nx-3; the four end planes go through the single-step kernel twice (stepper.hip:
     step_twice_edge_ext).  Same bits as the oracle — i.e. as the single-step path — for every step-count parity."""
     from xlb_amd.default_config import get_context
 

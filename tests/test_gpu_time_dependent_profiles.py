@@ -99,7 +99,7 @@ def test_ramped_lid_vs_oracle(lattice, shape):
 
 def end_plane_case(plate, shape=(24, 16, 64)):
     """halfway walls on the y / z faces, a time-dependent wall on the plane x = 0 and a static one on x = nx - 1: the two-step kernel
-    takes it (fuse2 = 2) with the end planes through the single-step kernel (api.hip: step_twice_edge_ext)"""
+    takes it (fuse2 = 2) with the end planes through the single-step kernel (stepper.hip: step_twice_edge_ext)"""
     vs, pp = init_hip("D3Q19")
     lat = orc.Lattice("D3Q19")
     grid = grid_factory(shape)

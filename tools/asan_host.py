@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Host-side sanitizer run (SURVEY.md section 5 "sanitizers"), on the CPU — GPU AddressSanitizer is not
-available on this pool.  `make asan` builds build/asan/libxlbhip_asan.so: api.hip and comm.cpp compiled with
+available on this pool.  `make asan` builds build/asan/libxlbhip_asan.so: api.hip, masker.hip, stepper.hip and comm.cpp compiled with
 -fsanitize=address,undefined for the HOST side only (-fno-gpu-sanitize), linked with the ordinary kernel objects.  This script
 loads it (the sanitizer runtime preloaded) and walks the argument paths of the C ABI that a machine without a GPU can reach:
 NULL handles, bad enums, bad ranks / tokens, the error channel's formatting, xlbhip_create's failure path, the lattice tables.
@@ -24,7 +24,7 @@ def runtime():
 
 def main():
     if not os.path.exists(LIB):
-        sys.exit(f"{LIB} not built: run `make asan` (about 12 minutes: api.hip's device code is compiled again)")
+        sys.exit(f"{LIB} not built: run `make asan` (a few minutes: the device code of the instrumented units is compiled again)")
     if os.environ.get("XLB_ASAN_CHILD") != "1":
         rt = runtime()
         if rt is None:

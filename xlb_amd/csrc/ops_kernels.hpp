@@ -289,7 +289,7 @@ __global__ void k_velocity_gradient(FieldView u, FieldView bc, FieldView out_a, 
 }
 
 // any Zou-He / Regularized / outflow / do-nothing cell strictly inside the x range?  (two-step kernel with inlet / outlet planes)
-__global__ void k_ext_interior_scan(FieldView bc, const uint8_t* kind_tab, Dims d, int* flag) {
+static __global__ void k_ext_interior_scan(FieldView bc, const uint8_t* kind_tab, Dims d, int* flag) {
   int x, y, z;
   if (!cell_of_thread(d, x, y, z)) return;
   if (x < 1 || x > d.nx - 2) return;
@@ -539,7 +539,7 @@ __global__ void k_outflow_aux(FieldView f0, FieldView f1, FieldView bc, FieldVie
 // ---- masker (indices_boundary_masker.py:73-143, JAX semantics) ---------------------------
 // scatter `value` at the listed GLOBAL indices that fall inside this rank's planes
 // [x_lo, x_hi) (storage plane = gx - x_lo)
-__global__ void k_scatter_u8(uint8_t* out, const int32_t* idx, int64_t n, uint8_t value, int x_lo, int x_hi, int gy,
+static __global__ void k_scatter_u8(uint8_t* out, const int32_t* idx, int64_t n, uint8_t value, int x_lo, int x_hi, int gy,
                              int gz) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -571,7 +571,7 @@ __global__ void k_missing(uint32_t* out, const uint32_t* old, const uint8_t* sol
 }
 
 // pack / unpack the host (q, nx, ny, nz) u8 view of missing_mask <-> device bit-sets
-__global__ void k_pack_missing(const uint8_t* bytes, uint32_t* bits, int q, Dims d, int halo) {
+static __global__ void k_pack_missing(const uint8_t* bytes, uint32_t* bits, int q, Dims d, int halo) {
   int x, y, z;
   if (!cell_of_thread(d, x, y, z)) return;
   const size_t n = (size_t)d.nx * d.ny * d.nz;
@@ -580,7 +580,7 @@ __global__ void k_pack_missing(const uint8_t* bytes, uint32_t* bits, int q, Dims
   for (int l = 0; l < q; ++l) b |= (bytes[(size_t)l * n + c] ? 1u : 0u) << l;
   bits[((size_t)(x + halo) * d.ny + y) * d.nz + z] = b;
 }
-__global__ void k_unpack_missing(const uint32_t* bits, uint8_t* bytes, int q, Dims d, int halo) {
+static __global__ void k_unpack_missing(const uint32_t* bits, uint8_t* bytes, int q, Dims d, int halo) {
   int x, y, z;
   if (!cell_of_thread(d, x, y, z)) return;
   const size_t n = (size_t)d.nx * d.ny * d.nz;
@@ -649,7 +649,7 @@ __device__ inline bool tri_box_overlap(const TriBox& t, float lx, float ly, floa
   return true;
 }
 // one thread per triangle: every unit voxel [i, i+1]^3 its bounding box touches is tested, hits are marked solid
-__global__ void k_mesh_solid(const float* verts /*[n_tri][3][3]*/, int64_t n_tri, uint8_t* solid, int nx, int ny, int nz) {
+static __global__ void k_mesh_solid(const float* verts /*[n_tri][3][3]*/, int64_t n_tri, uint8_t* solid, int nx, int ny, int nz) {
   const int64_t tix = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (tix >= n_tri) return;
   const float* v = verts + 9 * tix;
@@ -843,7 +843,7 @@ __global__ void k_mesh_weights_ray(const unsigned* tbuf, FieldView dist, Dims d)
 // inside test: generalized winding number of the triangle soup at the voxel centre, exact (sum of the signed solid angles,
 // Van Oosterom & Strackee, fp64) instead of Warp's BVH approximation; > 0.5 = inside.  One thread per voxel of the mesh's
 // bounding box, every thread walks all triangles (the triangle data is a broadcast read).
-__global__ void k_mesh_winding(const float* verts, int64_t n_tri, uint8_t* solid, Dims d, int lo0, int lo1, int lo2, int n0, int n1, int n2) {
+static __global__ void k_mesh_winding(const float* verts, int64_t n_tri, uint8_t* solid, Dims d, int lo0, int lo1, int lo2, int n0, int n1, int n2) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (int64_t)n0 * n1 * n2) return;
   const int i = lo0 + (int)(t / ((int64_t)n1 * n2)), j = lo1 + (int)((t / n2) % n1), k = lo2 + (int)(t % n2);
@@ -931,7 +931,7 @@ __global__ void k_mesh_winding_tag(const uint8_t* solid, const unsigned* tbuf, u
 // ---- MeshMaskerAABBClose (aabb_close.py:67-154, 216-263, 303-344) ----
 // AABB voxelisation on the grid padded by `pad` voxels per side (voxel (i, j, k) of the padded grid is the unit cube at
 // (i - pad, j - pad, k - pad))
-__global__ void k_mesh_solid_padded(const float* verts, int64_t n_tri, uint8_t* solid, int px, int py, int pz, int pad) {
+static __global__ void k_mesh_solid_padded(const float* verts, int64_t n_tri, uint8_t* solid, int px, int py, int pz, int pad) {
   const int64_t tix = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (tix >= n_tri) return;
   const float* v = verts + 9 * tix;
@@ -950,7 +950,7 @@ __global__ void k_mesh_solid_padded(const float* verts, int64_t n_tri, uint8_t* 
         if (tri_box_overlap(t, (float)(i - pad), (float)(j - pad), (float)(k - pad))) solid[((size_t)i * py + j) * pz + k] = 1;
 }
 // max (dilate) / min (erode) filter over the (2 h + 1)^3 cube; voxels within h of the padded grid's faces are copied
-__global__ void k_morph(const uint8_t* in, uint8_t* out, int px, int py, int pz, int h, int dilate) {
+static __global__ void k_morph(const uint8_t* in, uint8_t* out, int px, int py, int pz, int h, int dilate) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (int64_t)px * py * pz) return;
   const int i = (int)(t / ((int64_t)py * pz)), j = (int)((t / pz) % py), k = (int)(t % pz);
@@ -968,7 +968,7 @@ __global__ void k_morph(const uint8_t* in, uint8_t* out, int px, int py, int pz,
   out[t] = acc;
 }
 // crop the padded mask to the domain
-__global__ void k_crop(const uint8_t* in, uint8_t* out, Dims d, int py, int pz, int pad) {
+static __global__ void k_crop(const uint8_t* in, uint8_t* out, Dims d, int py, int pz, int pad) {
   int x, y, z;
   if (!cell_of_thread(d, x, y, z)) return;
   out[((size_t)x * d.ny + y) * d.nz + z] = in[((size_t)(x + pad) * py + (y + pad)) * pz + (z + pad)];
@@ -1037,7 +1037,7 @@ __global__ void k_gather(const E* data, size_t plane_stride, size_t ghost, int c
 // meta word of the two-step kernel, resolved once per run so that the kernel never searches an id table (layouts: step2_kernel.hpp
 // S2Meta): kind (0 fluid, XLBHIP_BC_* for the basic kinds, or "halfway wall WITH a moving-wall term"), slot of the BC in the
 // stepper's packed tables, missing bit-set.  wide = 0: 4 + 4 + up to 24 bits (D3Q19); wide = 1: 3 + 3 + bits 1 .. 26 (D3Q27).
-__global__ void k_build_meta(const uint8_t* bc, const uint32_t* miss, uint32_t* meta, size_t n, unsigned long long ids_packed,
+static __global__ void k_build_meta(const uint8_t* bc, const uint32_t* miss, uint32_t* meta, size_t n, unsigned long long ids_packed,
                              unsigned kinds_packed, unsigned moving_mask, int wide) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

@@ -258,7 +258,7 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
   // piece per pull instead of the tail of one row + the head of the next), the last wave the two halo columns of all rows
   // Row-aligned lanes are the mapping of the stand-alone BC-free kernel (two barriers per plane): periodic 512^3 2.28 -> 2.11-2.16
   // ms/step in round 3's A/B (round 2 measured -2...3 %); the bodies of the BC kernel lose 0-3 % with it and keep the dense mapping.
-  // (STRIPS & 4: row-aligned lanes for this body WITHOUT strip buffers — the run-time A/B of api.hip's "fuse2_rowmap" option)
+  // (STRIPS & 4: row-aligned lanes for this body WITHOUT strip buffers — the run-time A/B of stepper.hip's "fuse2_rowmap" option)
   constexpr bool ROWMAP = (SR || (STRIPS & 4) != 0 || (HASBC == 0 && !SLACK)) && TZ == 64;
   // strip buffers: the last wave holds the 2 x EY halo-column cells of the grown tile (ROWMAP) and pulls for them from the
   // strips — the same instructions as every other wave, with the strip buffer's geometry in place of the field's
@@ -651,7 +651,7 @@ __global__ void __attribute__((aligned(256))) __launch_bounds__((S2Geom<L, HASBC
 // for every population exactly the two values the halo cells left and right of boundary b pull from row (x, y).  Phase B
 // writes them with the field (two cells per row edge, staged through LDS, written by the waves without output cells: +3 %
 // bytes); phase A's last wave — the 2 x EY halo cells — pulls from it: per population and plane 4 sectors instead of ~15.
-// Anything else that writes the field invalidates its strips (api.hip: strips_version); the next pass then only writes them.
+// Anything else that writes the field invalidates its strips (stepper.hip: strips_version); the next pass then only writes them.
 // clean[b] = 1 when no cell of work item b — grown tile (periodic images included), planes x_lo - 1 .. x_hi + 1 as the kernel
 // visits them — carries a boundary condition.  Same block -> (tile, segment) mapping as k_step2; one block per item.
 template <int TY, int TZ, bool SLAB>

@@ -1,6 +1,6 @@
 // Launch plan of the two-steps-per-pass kernel (step2_kernel.hpp): which steppers and fields it takes, when pairs pay, its tile,
 // the x segments of a tile column and the order in which the blocks take the tiles.  Host rules on plain integers — no HIP:
-// api.hip feeds them and keeps the memory, the caches and the launches; tests/test_step2_plan.py compiles them on the CPU.
+// stepper.hip feeds them and keeps the memory, the caches and the launches; tests/test_step2_plan.py compiles them on the CPU.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -13,7 +13,7 @@ namespace xlb {
 
 constexpr int MAX_FAST_BCS = 8;  // bc ids the kernels look up in their arguments (step_kernel.hpp); more leave the two-step kernel out
 
-// what the rules look at, filled from the stepper and the launch (api.hip: plan_case)
+// what the rules look at, filled from the stepper and the launch (stepper.hip: plan_case)
 struct Step2Case {
   int lattice, collision, compute_dtype, store_dtype;
   int fast_math;  // 1: tolerance-graded collisions allowed (exact_math = 0)

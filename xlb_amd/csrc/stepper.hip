@@ -1,0 +1,938 @@
+// libxlbhip: the stepper.  Its tables and caches, the launches of one step and of a fused pair of steps, the slab halo protocol,
+// the fuse decision (step2_plan.hpp), the per-timestep profile tables, and the stepper's C entry points.
+#include <algorithm>
+#include <array>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <vector>
+
+#include "api_internal.hpp"
+#include "comm.hpp"
+#include "prof_ring.hpp"
+#include "step_launch.hpp"
+
+using namespace xlb;
+
+// what a cache was computed from: a field's address and contents version (versions are globally unique: a new field that
+// recycles a freed one's address cannot match).  The empty key matches no field.
+struct FieldKey {
+  const xlbhip_field* field = nullptr;
+  uint64_t version = 0;
+  FieldKey() = default;
+  FieldKey(const xlbhip_field* f) : field(f), version(f ? f->version : 0) {}
+  bool operator==(const FieldKey& o) const { return field == o.field && version == o.version; }
+};
+struct MetaKey {
+  FieldKey bc, miss;
+  bool external_halo = false;
+  bool operator==(const MetaKey& o) const { return bc == o.bc && miss == o.miss && external_halo == o.external_halo; }
+};
+
+// The stepper owns its device tables through DeviceBuf members: the destructor releases them, a rebuild re-allocates in place.
+// Its caches and when each is rebuilt or dropped:
+//   meta words      rebuilt when either mask's address or contents version, or the external_halo option, differs from meta_key,
+//                   or the cell count changed (prepare_fuse2)
+//   tile order      rebuilt when the tile counts (tys, tzs) of the (y, z) plane change (prepare_fuse2)
+//   clean flags     per launch geometry; all dropped whenever the meta words or the tile order are rebuilt
+//   edge-kind scan  redone when the bc mask's address or contents version differs from scan_key (can_fuse2)
+//   scratch field   re-created when the population fields' shape or dtype differs (can_fuse2)
+//   strip buffers   (the fields' own, common.hpp) valid iff strips_version == version && strips_oz == the launch's tile_oz
+//   profile ring    dropped whenever the profile table's layout changes (upload_prof_table)
+struct xlbhip_stepper {
+  xlbhip_ctx* ctx = nullptr;
+  int lattice = 0, collision = 0, cdt = 0, sdt = 0;
+  int n_bc = 0;
+  bool needs_missing = false;
+  bool extended_bcs = false;
+  bool has_outflow = false;  // ExtrapolationOutflowBC present: k_outflow_aux runs after every step
+  // two-step kernel with extended BCs on the x end planes only (inlet / outlet): the end planes go through the
+  // single-step kernel twice via this third population field
+  xlbhip_field* scratch = nullptr;
+  bool edge_ext_ok = false;
+  bool has_edge_kinds = false;  // kinds the two-step kernel does not evaluate itself: Zou-He family, outflow, do-nothing
+  // result of the last "are all such cells in the x end planes" scan, and the bc_mask it holds for
+  FieldKey scan_key;
+  int scan_flag = 1;
+  DeviceBuf tile_order;  // two-step kernel: uint32 block -> tile, hull tiles first (step2_tile_order)
+  int order_ty = 0, order_tz = 0;
+  DeviceBuf meta;  // two-step kernel: uint32 id | missing << 8 per cell
+  size_t meta_cells = 0;
+  // the masks the meta words were built from: xlbhip_step2 called per pair (the Python stepper pairing reference-style
+  // calls) must not rebuild them every time
+  MetaKey meta_key;
+  // two-step kernel: per launch geometry (x_begin, x_count, segments) the per-block "no boundary cell" flags
+  std::map<std::array<int, 3>, DeviceBuf> clean_cache;
+  bool forced = false;
+  double force[3] = {0, 0, 0};
+  double smag_cs = 0.17;
+  DeviceBuf tab_kind;  // uint8 [256]
+  unsigned long long ids_packed = 0;
+  unsigned kinds_packed = 0;
+  unsigned moving_mask = 0;  // slots (first 8 BCs) whose halfway wall has a non-zero moving-wall term
+  DeviceBuf tab_values;      // [256][27] compute dtype
+  // per-cell prescribed values of Zou-He / Regularized BCs built with a profile: host map (storage cell -> 3 values)
+  // and its sorted device image
+  std::map<uint32_t, std::array<double, 3>> prof_host;
+  DeviceBuf prof_keys;  // uint32 [n_prof]
+  DeviceBuf prof_vals;  // compute dtype [n_prof][3]
+  int n_prof = 0;
+  // time-dependent wall velocities (HalfwayBounceBackBC / HybridBC with profile(cells, timestep)): their cells are entries of
+  // the same table, declared once (td_cells, in declaration order; td_pos = their rows in the sorted table).  Every timestep
+  // gets a full image of the table in one slot of a device ring (prof_ring.hpp keeps the books).  Images are staged through
+  // pinned host rows (one per slot, static entries written once), each guarded by the event of its last copy.  A stepper
+  // without time-dependent BCs has no ring and keeps its single table.
+  std::vector<uint32_t> td_cells;
+  std::vector<int> td_pos;
+  bool td_contiguous = false;        // td_pos[i] == td_pos[0] + i: the rows are one block of the table
+  std::array<uint8_t, 256> td_bc{};  // bc ids with time-dependent cells
+  std::vector<char> prof_image;      // host copy of the table (compute dtype): the static entries of every image
+  ProfRing ring_book;
+  DeviceBuf ring;      // [slots][n_prof][3] compute dtype
+  PinnedBuf ring_pin;  // same layout
+  std::vector<hipEvent_t> ring_ev;
+  std::vector<uint8_t> ring_pin_ready;  // pinned row holds the static entries
+  // wall-distance weights of HybridBC cells (mesh maskers): host map (storage cell -> q weights) and its sorted device image
+  std::map<uint32_t, std::array<float, 27>> dist_host;
+  DeviceBuf dist_keys;  // uint32 [n_dist]
+  DeviceBuf dist_vals;  // float [n_dist][q]
+  int n_dist = 0;
+};
+
+namespace xlb {
+
+static int launch_any(const xlbhip_stepper* s, const StepLaunch& p) {
+  XLB_REQUIRE(p.n_prof == 0 || p.prof_vals, "step launch without its profile table (timestep not staged)");
+  if (s->forced || s->collision == XLBHIP_SMAGORINSKY_LES_BGK) {
+    const int coll = s->collision | (s->forced ? COLL_FORCED : 0);
+    if (s->lattice == XLBHIP_D2Q9) return launch_step_d2q9_ext(p, coll);
+    if (s->lattice == XLBHIP_D3Q19) return launch_step_d3q19_ext(p, coll);
+    return launch_step_d3q27_ext(p, coll);
+  }
+  if (s->lattice == XLBHIP_D2Q9) return s->collision == XLBHIP_BGK ? launch_step_d2q9_bgk(p) : launch_step_d2q9_kbc(p);
+  if (s->lattice == XLBHIP_D3Q19) return launch_step_d3q19_bgk(p);
+  if (s->collision == XLBHIP_BGK) return launch_step_d3q27_bgk(p);
+  return (p.fast_math && p.compute_dtype == XLBHIP_F64) ? launch_step_d3q27_kbc_fast64(p) : launch_step_d3q27_kbc(p);
+}
+
+static int check_step_fields(const xlbhip_stepper* s, const xlbhip_field* a, const xlbhip_field* b, const xlbhip_field* bcm,
+                             const xlbhip_field* miss) {
+  XLB_REQUIRE(s && a && b, "null argument");
+  XLB_REQUIRE(a != b, "f_0 and f_1 must be different fields (double buffering)");
+  const int q = lattice_q(s->lattice);
+  XLB_REQUIRE(a->card == q && b->card == q, "population fields must have cardinality %d", q);
+  XLB_REQUIRE(a->dtype == s->sdt && b->dtype == s->sdt, "population fields must have the stepper's store dtype %d", s->sdt);
+  XLB_REQUIRE(same_grid(a, b) && a->halo == b->halo && a->plane_stride == b->plane_stride, "f_0 and f_1 layouts differ");
+  if (s->n_bc > 0) {
+    XLB_REQUIRE(bcm, "this stepper has boundary conditions: bc_mask is required");
+  }
+  if (bcm) {
+    XLB_REQUIRE(bcm->dtype == XLBHIP_U8 && bcm->card == 1 && same_grid(bcm, a) && bcm->halo == a->halo, "bad bc_mask field");
+  }
+  if (s->needs_missing) {
+    XLB_REQUIRE(miss && miss->dtype == XLBHIP_MISSING && same_grid(miss, a) && miss->halo == a->halo,
+                "halfway bounce-back needs a missing_mask field on the same grid");
+  }
+  return 0;
+}
+
+// ---- per-timestep profile tables (time-dependent wall velocities) ----
+static bool has_td(const xlbhip_stepper* s) { return !s->td_cells.empty(); }
+static size_t prof_image_bytes(const xlbhip_stepper* s) { return (size_t)s->n_prof * 3 * (s->cdt == XLBHIP_F32 ? 4 : 8); }
+
+// the profile table the launches of timestep t read: the single table, or t's slot of the ring (nullptr: t is not staged)
+static const void* prof_table_at(const xlbhip_stepper* s, int64_t t) {
+  if (!has_td(s)) return s->prof_vals.get();
+  const int k = s->ring_book.find(t);
+  return k < 0 ? nullptr : s->ring.get<char>() + (size_t)k * prof_image_bytes(s);
+}
+
+// the tables of the timesteps t0 .. t0 + n - 1 are all resident: checked before anything of a call is enqueued
+static int require_staged(const xlbhip_stepper* s, int64_t t0, int64_t n) {
+  if (!has_td(s)) return 0;
+  for (int64_t k = 0; k < n; ++k)
+    XLB_REQUIRE(prof_table_at(s, t0 + k), "the time-dependent wall velocities of timestep %lld are not staged (xlbhip_stepper_stage_bc_profiles)",
+                (long long)(t0 + k));
+  return 0;
+}
+
+// (the stream must be drained: copies may still read the pinned rows)
+static void free_ring(xlbhip_stepper* s) {
+  for (hipEvent_t e : s->ring_ev) (void)hipEventDestroy(e);
+  (void)s->ring.reset();
+  (void)s->ring_pin.reset();
+  s->ring_ev.clear();
+  s->ring_pin_ready.clear();
+  s->ring_book.reset(0);
+}
+
+static int ensure_ring(xlbhip_stepper* s) {
+  if (s->ring) return 0;
+  const int slots = prof_ring_slot_count(prof_image_bytes(s));
+  const size_t bytes = (size_t)slots * prof_image_bytes(s);
+  XLB_HIP(s->ring.alloc(bytes));
+  if (hipError_t e = s->ring_pin.alloc(bytes); e != hipSuccess) {
+    free_ring(s);
+    XLB_FAIL("hipHostMalloc(%zu bytes) for the profile ring failed: %s", bytes, hipGetErrorString(e));
+  }
+  s->ring_book.reset(slots);
+  s->ring_ev.assign((size_t)slots, nullptr);
+  s->ring_pin_ready.assign((size_t)slots, 0);
+  for (int k = 0; k < slots; ++k) {
+    if (hipError_t e = hipEventCreateWithFlags(&s->ring_ev[k], hipEventDisableTiming); e != hipSuccess) {
+      s->ring_ev.resize((size_t)k);
+      free_ring(s);
+      XLB_FAIL("hipEventCreate: %s", hipGetErrorString(e));
+    }
+    XLB_HIP(hipEventRecord(s->ring_ev[k], s->ctx->stream));  // (every row starts out "copied")
+  }
+  return 0;
+}
+
+static StepLaunch make_launch(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
+                              double omega, int64_t t) {
+  xlbhip_ctx* c = s->ctx;
+  StepLaunch p;
+  p.src = src->data;
+  p.dst = dst->data;
+  p.bc = (s->n_bc > 0 && bcm) ? static_cast<const uint8_t*>(bcm->data) : nullptr;
+  p.miss = miss ? static_cast<const uint32_t*>(miss->data) : nullptr;
+  p.meta = nullptr;
+  p.clean = nullptr;
+  p.strips_src = nullptr;
+  p.strips_dst = nullptr;
+  p.strips = 0;
+  p.tile_order = nullptr;
+  p.x_segments = 1;
+  p.x_cap = 0;
+  p.tile_oy = p.tile_oz = 0;
+  const Step2Tile tile = step2_tile(s->lattice, s->collision, p.bc != nullptr);
+  p.tile_ty = tile.ty;
+  p.tile_tz = tile.tz;
+  p.tab_kind = s->tab_kind.get<uint8_t>();
+  p.ids_packed = s->ids_packed;
+  p.kinds_packed = s->kinds_packed;
+  p.n_bc = s->n_bc;
+  p.tab_values = s->tab_values.get();
+  p.prof_keys = s->prof_keys.get<uint32_t>();
+  p.prof_vals = prof_table_at(s, t);  // (time-dependent walls: t's slot of the ring, checked resident by the caller)
+  p.n_prof = s->n_prof;
+  p.dist_keys = s->dist_keys.get<uint32_t>();
+  p.dist_vals = s->dist_vals.get<float>();
+  p.n_dist = s->n_dist;
+  p.plane_stride = src->plane_stride;
+  p.nx = src->nx;
+  p.ny = src->ny;
+  p.nz = src->nz;
+  p.halo = src->halo;
+  p.omega = omega;
+  p.force[0] = s->force[0];
+  p.force[1] = s->force[1];
+  p.force[2] = s->force[2];
+  p.smag_cs = s->smag_cs;
+  p.compute_dtype = s->cdt;
+  p.store_dtype = s->sdt;
+  p.vec = (int)opt(c, "vec", 0);
+  p.has_bc = p.bc != nullptr ? (s->extended_bcs ? 2 : 1) : 0;
+  p.edge_ext = s->edge_ext_ok ? 1 : 0;
+  p.flags = (opt(c, "nt_store", 1) ? 1 : 0) | (int)(opt(c, "nt_load", 0) << 1);
+  p.block_threads = (int)opt(c, "block_threads", 256);
+  p.block_tz = (int)opt(c, "block_tz", 0);
+  p.xcd_swizzle = (int)opt(c, "xcd_swizzle", 0);
+  p.fast_math = opt(c, "exact_math", 0) ? 0 : 1;
+  p.fast_bgk = (opt(c, "fast_bgk", 0) && !opt(c, "exact_math", 0)) ? 1 : 0;
+  p.stream = c->stream;
+  p.x_begin = 0;
+  p.x_count = src->nx;
+  return p;
+}
+
+// the inputs of the two-step plan (step2_plan.hpp)
+static Step2Case plan_case(const xlbhip_stepper* s, const StepLaunch& p) {
+  return {s->lattice, s->collision, p.compute_dtype, p.store_dtype, p.fast_math, p.nx, p.ny, p.nz, p.halo,
+          p.has_bc, p.edge_ext, p.n_bc, p.kinds_packed, s->needs_missing ? 1 : 0};
+}
+
+// CUs the work items of the two-step kernel are to fill
+static long fill_cus(const xlbhip_ctx* c) {
+  const int64_t o = opt(c, "fuse2_cus", 0);
+  return o > 0 ? (long)o : (c->compute_units > 0 ? c->compute_units : 256);
+}
+
+static int fuse2_segments(const xlbhip_stepper* s, const StepLaunch& p) {
+  return step2_segments(plan_case(s, p), p.x_count, fill_cus(s->ctx), (int)opt(s->ctx, "fuse2_xseg", 0), opt(s->ctx, "fuse2_clean", 1) != 0);
+}
+
+// assemble_auxiliary_data of the ExtrapolationOutflowBC cells after a step src -> dst (nse_stepper.py:270-272)
+static int outflow_aux(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
+                       int64_t t) {
+  if (!s->has_outflow) return 0;
+  xlbhip_ctx* c = s->ctx;
+  const size_t n = dst->cells();
+  const void* pv = prof_table_at(s, t);
+  XLB_REQUIRE(s->n_prof == 0 || pv, "outflow pass without its profile table (timestep %lld not staged)", (long long)t);
+  return by_lattice(s->lattice, [&](auto L) {
+    return by_compute(s->cdt, [&](auto T) {
+      using TT = decltype(T);
+      hipLaunchKernelGGL((k_outflow_aux<decltype(L), TT>), blocks_for(n), 256, 0, c->stream, view(src), view(dst), view(bcm), view(miss), dims(dst),
+                         s->tab_kind.get<uint8_t>(), s->tab_values.get<const TT>(), s->prof_keys.get<uint32_t>(), static_cast<const TT*>(pv),
+                         s->n_prof);
+      XLB_HIP(hipGetLastError());
+      return 0;
+    });
+  });
+}
+
+static int launch_step2(xlbhip_stepper* s, StepLaunch p) {
+  if (s->lattice == XLBHIP_D3Q27 && s->collision == XLBHIP_KBC) return launch_step2_d3q27_kbc(p);
+  p.clean = nullptr;
+  if (p.has_bc && p.meta && opt(s->ctx, "fuse2_clean", 1)) {
+    // what the block -> (tile, x-segment) mapping depends on and may differ between the launches of one stepper (tile, shift and
+    // order are the stepper's; x_cap follows fuse2_clean): the flags say "no boundary cell in THIS block's item"
+    const std::array<int, 3> key = {p.x_begin, p.x_count, p.x_segments};
+    auto it = s->clean_cache.find(key);
+    if (it == s->clean_cache.end()) {
+      DeviceBuf flags;
+      XLB_HIP(flags.alloc((size_t)step2_items(p)));
+      if (int rc = step2_build_clean(p, flags.get<uint8_t>())) return rc;
+      it = s->clean_cache.emplace(key, std::move(flags)).first;
+    }
+    p.clean = it->second.get<uint8_t>();
+  }
+  if (s->lattice == XLBHIP_D3Q27) return launch_step2_d3q27_bgk(p);
+  return p.strips ? launch_step2_d3q19_bgk_strips(p) : launch_step2_d3q19_bgk(p);
+}
+
+// strip buffer of a population field (1 / 32 of it): allocated on first use; false (and no error) when there is no memory for it
+static bool ensure_strips(xlbhip_field* f) {
+  if (f->strips) return true;
+  const size_t bytes = f->planes * f->plane_stride * dtype_size(f->dtype) / 32 + 512;
+  if (hipMalloc(&f->strips, bytes) != hipSuccess) {
+    f->strips = nullptr;
+    (void)hipGetLastError();
+    return false;
+  }
+  f->strips_version = 0;
+  f->strips_oz = -1;
+  return true;
+}
+
+// Pair of steps for a stepper whose Zou-He / Regularized / outflow cells all sit in the planes x = 0 and x = nx - 1
+// (inlet / outlet faces): the two-step kernel updates the planes 2 .. nx-3, whose two-step cone never evaluates such a
+// cell (its f(t+1) on the planes 1 and nx-2 only PULLS from the end planes), and the four end planes go through the
+// single-step kernel twice with a third population field holding their f(t+1).  The first of those launches reads the
+// profile table of timestep t, the second that of t + 1 (time-dependent walls on the end planes).
+static int step_twice_edge_ext(xlbhip_stepper* s, StepLaunch p, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm,
+                               const xlbhip_field* miss, double omega, int64_t t) {
+  XLB_REQUIRE(s->scratch && s->scratch->plane_stride == src->plane_stride, "scratch field missing (can_fuse2 allocates it)");
+  const int nx = src->nx;
+  p.x_begin = 2;
+  p.x_count = nx - 4;
+  p.x_segments = fuse2_segments(s, p);
+  if (int rc = launch_step2_d3q19_bgk(p)) return rc;
+  // end planes, step 1: f(t+1) on the planes nx-3 .. nx-1 and 0 .. 2 -> scratch
+  StepLaunch q = make_launch(s, src, s->scratch, bcm, miss, omega, t);
+  q.x_begin = nx - 3;
+  q.x_count = 3;
+  if (int rc = launch_any(s, q)) return rc;
+  q.x_begin = 0;
+  if (int rc = launch_any(s, q)) return rc;
+  if (int rc = outflow_aux(s, src, s->scratch, bcm, miss, t)) return rc;
+  // step 2: f(t+2) on the planes nx-2, nx-1, 0, 1 -> dst
+  StepLaunch r = make_launch(s, s->scratch, dst, bcm, miss, omega, t + 1);
+  r.x_begin = nx - 2;
+  r.x_count = 2;
+  if (int rc = launch_any(s, r)) return rc;
+  r.x_begin = 0;
+  if (int rc = launch_any(s, r)) return rc;
+  return outflow_aux(s, s->scratch, dst, bcm, miss, t + 1);
+}
+
+// the compute stream waits for the halo exchange; with the telemetry on, the wait is bracketed by two timing events
+static int wait_for_halo(xlbhip_ctx* c) {
+  if (!opt(c, "halo_telemetry", 1)) {
+    XLB_HIP(hipStreamWaitEvent(c->stream, c->ev_halo, 0));
+    return 0;
+  }
+  const int slot = c->wait_head;
+  c->wait_head = (c->wait_head + 1) % xlbhip_ctx::WAIT_RING;
+  if (int rc = harvest_wait(c, slot)) return rc;  // (32 exchanges old: long complete)
+  if (!c->ev_w0[slot]) {
+    XLB_HIP(hipEventCreate(&c->ev_w0[slot]));
+    XLB_HIP(hipEventCreate(&c->ev_w1[slot]));
+  }
+  XLB_HIP(hipEventRecord(c->ev_w0[slot], c->stream));
+  XLB_HIP(hipStreamWaitEvent(c->stream, c->ev_halo, 0));
+  XLB_HIP(hipEventRecord(c->ev_w1[slot], c->stream));
+  c->wait_used[slot] = true;
+  return 0;
+}
+
+// One pass over a slab with ghost planes: the ghosts of src are refilled from the ring neighbours on the comm stream (comm.cpp,
+// `depth` planes per side) while the planes that need none of them are updated (role interior); the `edge` planes per side
+// follow.  Without overlap the whole slab is updated after the exchange (role whole).  launch(x_begin, x_count, role) enqueues
+// the kernels of a plane range on the compute stream.
+enum class SlabRole { interior, whole, edge };
+
+template <class Launch>
+static int slab_pass(xlbhip_ctx* c, int lattice, xlbhip_field* src, int depth, int edge, bool overlap, Launch&& launch) {
+  XLB_HIP(hipEventRecord(c->ev_edge, c->stream));  // src complete (previous pass)
+  if (overlap) {
+    // the interior launch goes out BEFORE the exchange is enqueued: posting an exchange costs host time (dozens of copy /
+    // send calls, some of which the runtime may only accept once earlier work of the communication stream has finished —
+    // measured with the ipc transport: 1 ms of exposed wait per pair when the launch came second) and the device must
+    // already have the interior to work on meanwhile
+    if (int rc = launch(edge, src->nx - 2 * edge, SlabRole::interior)) return rc;
+  }
+  XLB_HIP(hipStreamWaitEvent(c->comm_stream, c->ev_edge, 0));
+  if (int rc = halo_exchange_on(c, lattice, src, c->comm_stream, depth)) return rc;
+  XLB_HIP(hipEventRecord(c->ev_halo, c->comm_stream));
+  if (!overlap) {
+    XLB_HIP(hipStreamWaitEvent(c->stream, c->ev_halo, 0));
+    return launch(0, src->nx, SlabRole::whole);
+  }
+  if (int rc = wait_for_halo(c)) return rc;
+  if (int rc = launch(0, edge, SlabRole::edge)) return rc;
+  return launch(src->nx - edge, edge, SlabRole::edge);
+}
+
+// two steps in one pass (a -> scratch-free: src -> dst holds f(t+2)); caller checked eligibility
+static int step_twice(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
+                      double omega, int64_t t) {
+  StepLaunch p = make_launch(s, src, dst, bcm, miss, omega, t);
+  p.meta = s->meta.get<uint32_t>();
+  // hull tiles first pays when they are much more expensive than fluid tiles (halfway walls: redirected loads) and
+  // with clean work items; otherwise (fullway / equilibrium boundaries alone) the XCD-compact patch is faster
+  const bool clean_on = p.has_bc && opt(s->ctx, "fuse2_clean", 1) != 0;
+  p.tile_order = (p.has_bc && (s->needs_missing || clean_on)) ? s->tile_order.get<uint32_t>() : nullptr;
+  p.x_segments = fuse2_segments(s, p);
+  p.x_cap = clean_on ? 8 : 0;  // thin first / last x-segments: with walls on the x faces the inner segments are free of them
+  if (p.has_bc) {  // half-tile shift: both walls of an axis in one (wrapping) tile row
+    p.tile_oy = p.tile_ty / 2;
+    p.tile_oz = p.tile_tz / 2;
+  }
+  p.xcd_swizzle = 1;
+  xlbhip_ctx* c = s->ctx;
+  touch(dst);  // (new contents: whatever was cached on the old ones — its strip buffer — is stale)
+  if (s->edge_ext_ok) return step_twice_edge_ext(s, p, src, dst, bcm, miss, omega, t);
+  // strip buffers (step2_kernel.hpp): phase A's halo columns come from src's strips, phase B writes dst's.  D3Q19, the
+  // bit-exact body, (8 x 64) tiles; a field whose strips are not those of its current contents gets them rebuilt first.
+  xlbhip_field* srcw = const_cast<xlbhip_field*>(src);
+  const bool native_slab = src->halo > 0 && !opt(c, "external_halo", 0);
+  // With boundary conditions only: there they buy 1-3 % (cavity 512^3, interleaved A/B: halfway 2.353 -> 2.334, fullway 2.220 -> 2.149
+  // ms/step); the BC-free kernel is faster with row-aligned lanes alone (2.12 against 2.18 with strips, 2.29 before: profiles/r03/step2_strips.md).
+  // fuse2_strips = 2 forces them for every D3Q19 stepper.
+  const int64_t strips_opt = opt(c, "fuse2_strips", 1);
+  const bool strips = (strips_opt == 2 || (strips_opt == 1 && p.has_bc)) && s->lattice == XLBHIP_D3Q19 && !p.fast_bgk && p.tile_ty == 8 && p.tile_tz == 64 &&
+                      (src->halo == 0 || native_slab) && src->nx >= 8 && ensure_strips(srcw) && ensure_strips(dst);
+  // q writes dst's strips, and reads src's when they are those of src's current contents (all interior planes).  After anything but
+  // a strip-writing pass wrote src — a single step, an upload — the first pass only WRITES strips (no separate rebuild pass: at 512^3
+  // that would cost 1.5 ms, a third of a pair, inside e.g. the driver's 20-step timed region after its 5 warm-up steps).
+  auto read_strips = [&](StepLaunch& q) {
+    const bool valid = srcw->strips_version == srcw->version && srcw->strips_oz == q.tile_oz;
+    q.strips = valid ? 3 : 2;
+    q.strips_src = valid ? srcw->strips : nullptr;
+    q.strips_dst = dst->strips;
+  };
+  const bool rowmap_only = !strips && opt(c, "fuse2_rowmap", 0) != 0 && p.has_bc && s->lattice == XLBHIP_D3Q19 && !p.fast_bgk && p.tile_ty == 8 && p.tile_tz == 64;
+  if (rowmap_only) p.strips = 4;
+  auto dst_strips_done = [&]() {  // every interior plane of dst was written by strip-writing launches
+    dst->strips_version = dst->version;
+    dst->strips_oz = p.tile_oz;
+  };
+  if (src->halo == 0 || opt(c, "external_halo", 0)) {
+    if (strips) read_strips(p);
+    if (int rc = launch_step2(s, p)) return rc;
+    if (strips) dst_strips_done();
+    return 0;
+  }
+  // slab protocol for a PAIR of steps: the two ghost planes per side of src are refilled (depth 2) while the planes whose
+  // two-step cone stays inside the slab are updated; the two edge plane pairs follow (each warms its own 3-plane window up
+  // from the fresh ghosts).
+  const bool overlap = opt(c, "overlap", 1) != 0 && src->nx >= 16;
+  auto launch = [&](int x_begin, int x_count, SlabRole role) -> int {
+    StepLaunch q = p;
+    q.x_begin = x_begin;
+    q.x_count = x_count;
+    q.x_segments = role == SlabRole::edge ? 1 : fuse2_segments(s, q);
+    if (strips && role == SlabRole::interior) {
+      read_strips(q);
+    } else if (strips) {  // launches whose phase A pulls from ghost planes (no strips there) only WRITE strips
+      q.strips = 2;
+      q.strips_dst = dst->strips;
+    }
+    return launch_step2(s, q);
+  };
+  if (int rc = slab_pass(c, s->lattice, srcw, 2, 2, overlap, launch)) return rc;
+  if (strips) dst_strips_done();
+  return 0;
+}
+
+static bool can_fuse2(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss) {
+  const int64_t mode = opt(s->ctx, "fuse2", 1);
+  if (mode == 0 || s->forced) return false;
+  s->edge_ext_ok = false;
+  if (s->has_edge_kinds) {
+    // Zou-He / Regularized / outflow / do-nothing cells: fine when they all sit in the two x end planes (scan of bc_mask, 1 B / cell)
+    if (!bcm || src->halo != 0 || src->nx < 16 || s->lattice != XLBHIP_D3Q19) return false;
+    xlbhip_ctx* c = s->ctx;
+    if (!(s->scan_key == FieldKey(bcm))) {  // one scan per (stepper, bc_mask contents), not per run
+      DeviceBuf dflag;
+      int flag = 1;
+      if (dflag.alloc(sizeof(int)) != hipSuccess) return false;
+      (void)hipMemsetAsync(dflag.get(), 0, sizeof(int), c->stream);
+      hipLaunchKernelGGL(k_ext_interior_scan, blocks_for(bcm->cells()), 256, 0, c->stream, view(bcm), s->tab_kind.get<uint8_t>(), dims(bcm),
+                         dflag.get<int>());
+      if (hipMemcpyAsync(&flag, dflag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+        flag = 1;
+      s->scan_key = FieldKey(bcm);
+      s->scan_flag = flag;
+    }
+    if (s->scan_flag != 0) return false;
+    // the end planes need a third population field; without the memory for it the stepper stays on single steps
+    if (!s->scratch || s->scratch->nx != src->nx || s->scratch->ny != src->ny || s->scratch->nz != src->nz || s->scratch->dtype != src->dtype) {
+      if (s->scratch) xlbhip_field_destroy(s->scratch);
+      s->scratch = nullptr;
+      if (xlbhip_field_create(c, src->card, src->nx, src->ny, src->nz, src->dtype, src->halo, 0.0, &s->scratch) != 0 ||
+          s->scratch->plane_stride != src->plane_stride) {
+        if (s->scratch) xlbhip_field_destroy(s->scratch);
+        s->scratch = nullptr;
+        (void)hipGetLastError();
+        return false;
+      }
+    }
+    s->edge_ext_ok = true;
+  }
+  const StepLaunch p = make_launch(s, src, dst, bcm, miss, 1.0, 0);  // (the plan's inputs only: no launch)
+  return step2_fuse(plan_case(s, p), (int)mode, fill_cus(s->ctx), (int)opt(s->ctx, "fuse2_xseg", 0), opt(s->ctx, "fuse2_clean", 1) != 0);
+}
+
+// per-run tables of the two-step kernel: the meta words (bc kind | slot | missing bits per cell, ghost planes
+// included) and the hull-first tile order
+static int prepare_fuse2(xlbhip_stepper* s, const xlbhip_field* bcm, const xlbhip_field* miss) {
+  if (!(s->n_bc > 0 && bcm)) return 0;
+  xlbhip_ctx* c = s->ctx;
+  const size_t cells = bcm->cells_with_halo();
+  if (s->meta_cells != cells) {
+    if (s->meta) comm_forget_buffer(c, s->meta.get());
+    XLB_HIP(s->meta.alloc(cells * sizeof(uint32_t)));
+    s->meta_cells = cells;
+    s->meta_key = MetaKey();  // (contents gone: rebuild below)
+  }
+  const Step2Tile tile = step2_tile(s->lattice, s->collision, true);
+  const int tys = bcm->ny / tile.ty, tzs = bcm->nz / tile.tz;
+  if (s->order_ty != tys || s->order_tz != tzs) {
+    const std::vector<uint32_t> order = step2_tile_order(tys, tzs);
+    s->clean_cache.clear();  // the flags were computed for the old block -> tile mapping
+    if (int rc = upload_bytes(order.data(), order.size() * sizeof(uint32_t), s->tile_order)) return rc;
+    s->order_ty = tys;
+    s->order_tz = tzs;
+  }
+  const MetaKey key{FieldKey(bcm), FieldKey(miss), opt(c, "external_halo", 0) != 0};
+  if (s->meta_key == key) return 0;  // meta words, tile order and clean flags are those of these very masks
+  s->meta_key = key;
+  s->clean_cache.clear();  // (stream-ordered: the flags' last readers were enqueued before this point and hipFree synchronises)
+  hipLaunchKernelGGL(k_build_meta, blocks_for(cells), 256, 0, c->stream, static_cast<const uint8_t*>(bcm->data),
+                     miss ? static_cast<const uint32_t*>(miss->data) : nullptr, s->meta.get<uint32_t>(), cells, s->ids_packed, s->kinds_packed,
+                     s->moving_mask, s->lattice == XLBHIP_D3Q27 ? 1 : 0);
+  XLB_HIP(hipGetLastError());
+  // slab decomposition: phase A also runs on the ghost planes -1 and nx, so it needs the neighbours' boundary
+  // information there.  Host-staged transports (external_halo) fill the ghost planes of the masks themselves.
+  if (bcm->halo > 0 && !opt(c, "external_halo", 0))
+    return plane_exchange_on(c, s->meta.get(), sizeof(uint32_t), bcm->nx, bcm->ny, bcm->nz, bcm->halo, c->stream);
+  return 0;
+}
+
+// the step kernel(s) of one step src -> dst, with the slab halo protocol when the fields carry ghost planes
+static int step_kernels(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
+                     double omega, int64_t t) {
+  xlbhip_ctx* c = s->ctx;
+  StepLaunch p = make_launch(s, src, dst, bcm, miss, omega, t);
+  if (src->halo == 0 || opt(c, "external_halo", 0)) return launch_any(s, p);  // (p covers all of x)
+  // slab protocol for one step.
+  // The launch that runs BEFORE this step's exchange has completed must not write a plane a neighbour may still be pulling
+  // (ipc transport: the puller, not the owner, knows when a pull is done; what orders the two is that the owner's edge launches
+  // wait for the NEXT exchange, which the neighbour posts after its pulls).  On fields with two ghost planes the previous exchange
+  // may have been a fused pair's — planes 0, 1, nx - 2, nx - 1 of `dst` lent out — so their "edge" is two planes wide.
+  const int edge = src->halo >= 2 ? 2 : 1;
+  const bool overlap = opt(c, "overlap", 1) != 0 && src->nx > 2 * edge;
+  return slab_pass(c, s->lattice, const_cast<xlbhip_field*>(src), 1, edge, overlap, [&](int x_begin, int x_count, SlabRole) {
+    p.x_begin = x_begin;
+    p.x_count = x_count;
+    return launch_any(s, p);
+  });
+}
+
+// one step src -> dst; ExtrapolationOutflowBC cells get their auxiliary data afterwards (nse_stepper.py:270-272)
+static int step_once(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
+                     double omega, int64_t t) {
+  touch(dst);  // (its strip buffer, if any, no longer matches)
+  if (int rc = step_kernels(s, src, dst, bcm, miss, omega, t)) return rc;
+  return outflow_aux(s, src, dst, bcm, miss, t);
+}
+
+}  // namespace xlb
+
+extern "C" {
+
+int xlbhip_stepper_create(xlbhip_ctx* c, int lattice, int collision, int cdt, int sdt, int n_bc, const xlbhip_bc_desc* bcs,
+                          xlbhip_stepper** out) {
+  XLB_REQUIRE(c && out, "null argument");
+  XLB_REQUIRE(lattice_q(lattice) > 0, "unknown lattice %d", lattice);
+  XLB_REQUIRE(collision == XLBHIP_BGK || collision == XLBHIP_KBC || collision == XLBHIP_SMAGORINSKY_LES_BGK, "unknown collision %d", collision);
+  XLB_REQUIRE(!(collision == XLBHIP_KBC && lattice == XLBHIP_D3Q19), "Velocity set not supported: D3Q19 has no KBC (reference kbc.py:65-66)");
+  XLB_REQUIRE(cdt == XLBHIP_F32 || cdt == XLBHIP_F64, "bad compute dtype %d", cdt);
+  XLB_REQUIRE(is_float(sdt) && dtype_size(sdt) <= dtype_size(cdt), "bad store dtype %d for compute dtype %d", sdt, cdt);
+  XLB_REQUIRE(n_bc == 0 || bcs, "null bc list");
+  std::vector<uint8_t> kind(256, 0);
+  const int q = lattice_q(lattice);
+  std::vector<double> vals(256 * 27, 0.0);
+  bool needs_missing = false, extended = false, has_outflow = false, has_edge_kinds = false;
+  for (int i = 0; i < n_bc; ++i) {
+    const xlbhip_bc_desc& b = bcs[i];
+    XLB_REQUIRE(b.id >= 1 && b.id <= 255, "bc id %d out of range 1..255", b.id);
+    XLB_REQUIRE(b.kind >= XLBHIP_BC_EQUILIBRIUM && b.kind <= XLBHIP_BC_HALFWAY_BB_PROFILE, "unknown bc kind %d", b.kind);
+    XLB_REQUIRE(b.kind < XLBHIP_BC_HYBRID_BB_REGULARIZED || b.kind > XLBHIP_BC_HYBRID_NEQ_REGULARIZED || lattice_d(lattice) == 3,
+                "This BC is not implemented in 2D!");  // bc_hybrid.py:119-120
+    if (b.kind == XLBHIP_BC_EXTRAPOLATION_OUTFLOW) has_outflow = true;
+    if (b.kind >= XLBHIP_BC_ZOUHE_VELOCITY || b.kind == XLBHIP_BC_DO_NOTHING) has_edge_kinds = true;
+    XLB_REQUIRE(kind[b.id] == 0, "bc id %d used twice", b.id);
+    if (b.kind >= XLBHIP_BC_ZOUHE_VELOCITY) extended = needs_missing = true;
+    kind[b.id] = (uint8_t)b.kind;
+    for (int l = 0; l < q; ++l) vals[b.id * 27 + l] = b.values[l];
+    if (b.kind == XLBHIP_BC_HALFWAY_BB) needs_missing = true;
+  }
+  unsigned long long ids_packed = 0;
+  unsigned kinds_packed = 0;
+  unsigned moving_mask = 0;
+  for (int i = 0; i < n_bc && i < 8; ++i) {
+    ids_packed |= (unsigned long long)(bcs[i].id & 0xff) << (8 * i);
+    kinds_packed |= (unsigned)(bcs[i].kind & 0xf) << (4 * i);
+    if (bcs[i].kind == XLBHIP_BC_HALFWAY_BB)
+      for (int l = 0; l < q; ++l)
+        if (bcs[i].values[l] != 0.0) moving_mask |= 1u << i;
+  }
+  XLB_HIP(hipSetDevice(c->device));
+  auto s = std::make_unique<xlbhip_stepper>();  // (a failure below releases it and the tables uploaded so far)
+  s->ctx = c;
+  s->lattice = lattice;
+  s->collision = collision;
+  s->cdt = cdt;
+  s->sdt = sdt;
+  s->n_bc = n_bc;
+  s->needs_missing = needs_missing;
+  s->extended_bcs = extended;
+  s->has_outflow = has_outflow;
+  s->has_edge_kinds = has_edge_kinds;
+  s->ids_packed = ids_packed;
+  s->kinds_packed = kinds_packed;
+  s->moving_mask = moving_mask;
+  if (int rc = upload_bytes(kind.data(), 256, s->tab_kind)) return rc;
+  if (int rc = upload_values(cdt, vals, s->tab_values)) return rc;
+  *out = s.release();
+  return 0;
+}
+
+}  // extern "C"
+
+// the sorted device image of the merged table (std::map iterates in key order), its host copy, the rows of the time-dependent
+// cells in it, and the PROF_FLAG of bc_id; drops the ring (its images have the old layout).  The stream is drained.
+static int upload_prof_table(xlbhip_stepper* s, int bc_id) {
+  std::vector<uint32_t> keys;
+  std::vector<double> v64;
+  keys.reserve(s->prof_host.size());
+  v64.reserve(3 * s->prof_host.size());
+  for (const auto& kv : s->prof_host) {
+    keys.push_back(kv.first);
+    v64.insert(v64.end(), kv.second.begin(), kv.second.end());
+  }
+  s->n_prof = (int)keys.size();
+  if (int rc = upload_keys(keys, s->prof_keys)) return rc;
+  if (int rc = upload_values(s->cdt, v64, s->prof_vals)) return rc;
+  // flag the BC: its prescribed values come from the table (cell.hpp: PROF_FLAG)
+  const std::vector<char> one = compute_image(s->cdt, {1.0});
+  XLB_HIP(hipMemcpy(s->tab_values.get<char>() + ((size_t)bc_id * 27 + PROF_FLAG) * one.size(), one.data(), one.size(), hipMemcpyHostToDevice));
+  if (s->td_cells.empty() && !s->ring) return 0;
+  s->prof_image = compute_image(s->cdt, v64);
+  s->td_pos.resize(s->td_cells.size());
+  for (size_t i = 0; i < s->td_cells.size(); ++i)
+    s->td_pos[i] = (int)(std::lower_bound(keys.begin(), keys.end(), s->td_cells[i]) - keys.begin());
+  s->td_contiguous = true;
+  for (size_t i = 0; i < s->td_pos.size(); ++i) s->td_contiguous = s->td_contiguous && s->td_pos[i] == s->td_pos[0] + (int)i;
+  free_ring(s);
+  return 0;
+}
+
+extern "C" {
+
+int xlbhip_stepper_set_bc_profile(xlbhip_stepper* s, int bc_id, int64_t n, const uint32_t* storage_cells, const double* values) {
+  XLB_REQUIRE(s && bc_id >= 1 && bc_id <= 255, "bad argument");
+  XLB_REQUIRE(n == 0 || (storage_cells && values), "null table");
+  xlbhip_ctx* c = s->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipStreamSynchronize(c->stream));
+  for (int64_t i = 0; i < n; ++i) s->prof_host[storage_cells[i]] = {values[3 * i], values[3 * i + 1], values[3 * i + 2]};
+  return upload_prof_table(s, bc_id);
+}
+
+int xlbhip_stepper_set_bc_profile_cells(xlbhip_stepper* s, int bc_id, int64_t n, const uint32_t* storage_cells) {
+  XLB_REQUIRE(s && bc_id >= 1 && bc_id <= 255, "bad argument");
+  XLB_REQUIRE(n == 0 || storage_cells, "null cell list");
+  xlbhip_ctx* c = s->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  uint8_t kind = 0;
+  XLB_HIP(hipMemcpy(&kind, s->tab_kind.get<uint8_t>() + bc_id, 1, hipMemcpyDeviceToHost));
+  XLB_REQUIRE((kind >= XLBHIP_BC_HYBRID_BB_REGULARIZED && kind <= XLBHIP_BC_HYBRID_NEQ_REGULARIZED) || kind == XLBHIP_BC_HALFWAY_BB_PROFILE,
+              "time-dependent wall velocities: bc %d is of kind %d (HybridBC / HalfwayBounceBackBC with a profile)", bc_id, (int)kind);
+  XLB_HIP(hipStreamSynchronize(c->stream));
+  for (int64_t i = 0; i < n; ++i)
+    XLB_REQUIRE(s->prof_host.find(storage_cells[i]) == s->prof_host.end(), "cell %u has a profile table entry already", storage_cells[i]);
+  for (int64_t i = 0; i < n; ++i) {
+    s->prof_host[storage_cells[i]] = {0.0, 0.0, 0.0};  // (placeholder: every image carries this timestep's value)
+    s->td_cells.push_back(storage_cells[i]);
+  }
+  if (n > 0) s->td_bc[bc_id] = 1;
+  return upload_prof_table(s, bc_id);
+}
+
+int xlbhip_stepper_profile_slots(xlbhip_stepper* s, int* slots) {
+  XLB_REQUIRE(s && slots, "null argument");
+  *slots = has_td(s) ? prof_ring_slot_count(prof_image_bytes(s)) : 0;
+  return 0;
+}
+
+int xlbhip_stepper_stage_bc_profiles(xlbhip_stepper* s, int64_t t_first, int64_t n_steps, const double* values) {
+  XLB_REQUIRE(s, "stepper is null");
+  XLB_REQUIRE(has_td(s), "this stepper has no time-dependent wall velocities (xlbhip_stepper_set_bc_profile_cells)");
+  XLB_REQUIRE(n_steps >= 0 && (n_steps == 0 || values), "bad argument");
+  xlbhip_ctx* c = s->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  if (int rc = ensure_ring(s)) return rc;
+  XLB_REQUIRE(n_steps <= s->ring_book.slots(), "%lld tables staged at once, the ring holds %d (xlbhip_stepper_profile_slots)", (long long)n_steps,
+              s->ring_book.slots());
+  const size_t img = prof_image_bytes(s), nt = s->td_cells.size();
+  char* pin = s->ring_pin.get<char>();
+  int64_t r = 0;  // the image of timestep t_first + r goes next
+  for (const ProfRing::Run run : s->ring_book.take((int)n_steps)) {
+    const int64_t r_first = r;
+    for (int k = run.first; k < run.first + run.len; ++k, ++r) {
+      XLB_HIP(hipEventSynchronize(s->ring_ev[k]));  // the previous copy out of this pinned row (not the kernels)
+      char* row = pin + (size_t)k * img;
+      if (!s->ring_pin_ready[k]) {
+        std::memcpy(row, s->prof_image.data(), img);
+        s->ring_pin_ready[k] = 1;
+      }
+      const double* v = values + (size_t)r * nt * 3;
+      by_compute(s->cdt, [&](auto T) {
+        auto* d = reinterpret_cast<decltype(T)*>(row);
+        if (s->td_contiguous) {  // one time-dependent BC, or several whose cells are not interleaved with others: one block of the table
+          std::copy(v, v + 3 * nt, d + (size_t)s->td_pos[0] * 3);
+        } else {
+          for (size_t i = 0; i < nt; ++i)
+            for (int a = 0; a < 3; ++a) d[(size_t)s->td_pos[i] * 3 + a] = (decltype(T))v[i * 3 + a];
+        }
+        return 0;
+      });
+    }
+    // one copy per run of consecutive slots, on the compute stream: it lands after every kernel enqueued so far (those that still
+    // read an older image of these slots) and before every launch that looks these timesteps up.  A slot counts as resident only
+    // once its copy is enqueued; if that fails, nothing of the run is claimed.
+    const size_t off = (size_t)run.first * img;
+    XLB_HIP(hipMemcpyAsync(s->ring.get<char>() + off, pin + off, (size_t)run.len * img, hipMemcpyHostToDevice, c->stream));
+    for (int k = run.first; k < run.first + run.len; ++k) {
+      if (hipError_t e = hipEventRecord(s->ring_ev[k], c->stream); e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);  // (no copy out of a pinned row may stay in flight behind a stale event)
+        XLB_FAIL("hipEventRecord: %s", hipGetErrorString(e));
+      }
+    }
+    s->ring_book.mark_resident(run, t_first + r_first);
+  }
+  return 0;
+}
+
+int xlbhip_stepper_momentum_transfer(xlbhip_stepper* s, int bc_id, const xlbhip_field* f_0, const xlbhip_field* bcm, const xlbhip_field* miss,
+                                     double force_out[3]) {
+  return xlbhip_stepper_momentum_transfer_at(s, bc_id, 0, f_0, bcm, miss, force_out);
+}
+
+int xlbhip_stepper_momentum_transfer_at(xlbhip_stepper* s, int bc_id, int64_t timestep, const xlbhip_field* f_0, const xlbhip_field* bcm,
+                                        const xlbhip_field* miss, double force_out[3]) {
+  XLB_REQUIRE(s && force_out && bc_id >= 1 && bc_id <= 255, "bad argument");
+  xlbhip_ctx* c = s->ctx;
+  XLB_CHECK_POP(f_0, s->lattice, "momentum_transfer(f_0)");
+  XLB_REQUIRE(bcm && bcm->dtype == XLBHIP_U8 && bcm->card == 1 && same_grid(bcm, f_0) && bcm->halo == f_0->halo, "momentum_transfer: bad bc_mask field");
+  XLB_REQUIRE(miss && miss->dtype == XLBHIP_MISSING && same_grid(miss, f_0) && miss->halo == f_0->halo, "momentum_transfer: needs the missing_mask field");
+  XLB_REQUIRE(f_0->halo == 0, "momentum_transfer through the stepper's tables: fields without ghost planes (mesh / profile BCs live on one rank)");
+  uint8_t kind = 0;
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipMemcpy(&kind, s->tab_kind.get<uint8_t>() + bc_id, 1, hipMemcpyDeviceToHost));
+  XLB_REQUIRE((kind >= XLBHIP_BC_HYBRID_BB_REGULARIZED && kind <= XLBHIP_BC_HYBRID_NEQ_REGULARIZED) || kind == XLBHIP_BC_HALFWAY_BB_PROFILE,
+              "momentum_transfer through the stepper: bc %d is of kind %d (HybridBC / profile walls; plain walls use xlbhip_momentum_transfer)", bc_id,
+              (int)kind);
+  // a time-dependent wall: the wall velocities of this timestep.  Any other BC: the single table (the kernel reads entries of bc_id's
+  // cells only, and every staged image carries the same static entries), whatever is staged.
+  const void* pv = s->td_bc[bc_id] ? prof_table_at(s, timestep) : s->prof_vals.get();
+  XLB_REQUIRE(s->n_prof == 0 || pv, "momentum_transfer: the time-dependent wall velocities of timestep %lld are not staged", (long long)timestep);
+  DeviceBuf dforce;
+  XLB_HIP(dforce.alloc(3 * sizeof(double)));
+  XLB_HIP(hipMemsetAsync(dforce.get(), 0, 3 * sizeof(double), c->stream));
+  const size_t n = f_0->cells();
+  const int rc = by_lattice(s->lattice, [&](auto L) {
+    return by_compute(s->cdt, [&](auto T) {
+      using TT = decltype(T);
+      hipLaunchKernelGGL((k_momentum_transfer_tab<decltype(L), TT>), blocks_for(n), 256, 0, c->stream, view(f_0), view(bcm), view(miss), dims(f_0), bc_id,
+                         s->tab_kind.get<uint8_t>(), s->tab_values.get<const TT>(), s->prof_keys.get<uint32_t>(), static_cast<const TT*>(pv),
+                         s->n_prof, s->dist_keys.get<uint32_t>(), s->dist_vals.get<float>(), s->n_dist, dforce.get<double>());
+      XLB_HIP(hipGetLastError());
+      return 0;
+    });
+  });
+  if (rc) return rc;
+  hipError_t e = hipMemcpyAsync(force_out, dforce.get(), 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  XLB_REQUIRE(e == hipSuccess, "momentum_transfer: %s", hipGetErrorString(e));
+  return 0;
+}
+
+int xlbhip_stepper_set_bc_distances(xlbhip_stepper* s, int64_t n, const uint32_t* storage_cells, const float* weights) {
+  XLB_REQUIRE(s, "stepper is null");
+  XLB_REQUIRE(n == 0 || (storage_cells && weights), "null table");
+  xlbhip_ctx* c = s->ctx;
+  const int q = lattice_q(s->lattice);
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipStreamSynchronize(c->stream));
+  for (int64_t i = 0; i < n; ++i) {
+    std::array<float, 27> w{};
+    for (int l = 0; l < q; ++l) w[(size_t)l] = weights[i * q + l];
+    s->dist_host[storage_cells[i]] = w;
+  }
+  std::vector<uint32_t> keys;
+  std::vector<float> vals;
+  keys.reserve(s->dist_host.size());
+  vals.reserve(s->dist_host.size() * (size_t)q);
+  for (const auto& kv : s->dist_host) {  // std::map iterates in key order
+    keys.push_back(kv.first);
+    vals.insert(vals.end(), kv.second.begin(), kv.second.begin() + q);
+  }
+  s->n_dist = (int)keys.size();
+  if (int rc = upload_keys(keys, s->dist_keys)) return rc;
+  return upload_bytes(vals.data(), vals.size() * sizeof(float), s->dist_vals);
+}
+
+int xlbhip_stepper_set_force(xlbhip_stepper* s, const double* force) {
+  XLB_REQUIRE(s, "stepper is null");
+  s->forced = force != nullptr;
+  for (int a = 0; a < 3; ++a) s->force[a] = force ? force[a] : 0.0;
+  return 0;
+}
+
+int xlbhip_stepper_set_smagorinsky(xlbhip_stepper* s, double coef) {
+  XLB_REQUIRE(s, "stepper is null");
+  s->smag_cs = coef;
+  return 0;
+}
+
+int xlbhip_stepper_destroy(xlbhip_stepper* s) {
+  if (!s) return 0;
+  (void)hipSetDevice(s->ctx->device);
+  (void)hipStreamSynchronize(s->ctx->stream);
+  free_ring(s);  // (explicitly here, after the drain: copies may still read the pinned rows)
+  if (s->meta) comm_forget_buffer(s->ctx, s->meta.get());
+  if (s->scratch) xlbhip_field_destroy(s->scratch);
+  delete s;  // (the device tables go with their owners)
+  return 0;
+}
+
+int xlbhip_step(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
+                double omega, int64_t timestep) {
+  // the timestep selects the wall velocities of time-dependent profiles (nse_stepper.py:370-378 passes it to every BC functional)
+  if (int rc = check_step_fields(s, src, dst, bcm, miss)) return rc;
+  if (int rc = require_staged(s, timestep, 1)) return rc;
+  return step_once(s, src, dst, bcm, miss, omega, timestep);
+}
+
+// n steps; `fixed_placement`: the result must land in f_a for even n and in f_b for odd n (xlbhip_run's contract);
+// otherwise every pair of steps is fused and *result_in_b reports where the result is (xlbhip_run_any)
+static int run_steps(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const xlbhip_field* bcm, const xlbhip_field* miss, double omega,
+                     int64_t t0, int64_t n, bool fixed_placement, int* result_in_b) {
+  XLB_REQUIRE(n >= 0, "n_steps < 0");
+  if (int rc = check_step_fields(s, a, b, bcm, miss)) return rc;
+  if (int rc = require_staged(s, t0, n)) return rc;
+  // With two-step fusion ("fuse2") a pair of steps is ONE pass a -> b: pairs alternate direction (a -> b, b -> a, ...).
+  // Under the fixed placement contract a trailing half pair (buffer parity) is fixed up by single steps.
+  int64_t i = 0;
+  xlbhip_field* cur = a;
+  xlbhip_field* oth = b;
+  // (a host-staged transport refills the ghosts between calls: it drives pairs through xlbhip_step2 itself)
+  const bool caller_fills_ghosts = a->halo > 0 && opt(s->ctx, "external_halo", 0) != 0;
+  bool fuse = n >= 2 && !caller_fills_ghosts && can_fuse2(s, a, b, bcm, miss);
+  if (n >= 2 && a->halo > 0 && !caller_fills_ghosts && comm_ranks(s->ctx) > 1) {
+    // pairs and single steps post different message sets (depth-2 / depth-1 exchange, meta planes): every rank must take
+    // the same decision, and uneven slabs may sit on either side of the chip-filling rule -> MIN over the ranks
+    int all = 0;
+    if (int rc = comm_all_min(s->ctx, fuse ? 1 : 0, &all)) return rc;
+    fuse = all != 0;
+  }
+  if (fuse) {
+    if (int rc = prepare_fuse2(s, bcm, miss)) return rc;
+    // choose the number of pairs so that the remaining single steps land the result in the right buffer:
+    // after P pairs the data sits in (P odd ? b : a); then r = n - 2P single steps flip r more times.
+    // P + r must be congruent to n (mod 2)  <=>  P even.  Use the largest even P with 2P <= n.
+    int64_t pairs = fixed_placement ? ((n / 2) & ~int64_t(1)) : n / 2;
+    for (int64_t k = 0; k < pairs; ++k) {
+      if (int rc = step_twice(s, cur, oth, bcm, miss, omega, t0 + 2 * k)) return rc;
+      xlbhip_field* tmp = cur;
+      cur = oth;
+      oth = tmp;
+    }
+    i = 2 * pairs;
+  }
+  for (; i < n; ++i) {
+    if (int rc = step_once(s, cur, oth, bcm, miss, omega, t0 + i)) return rc;
+    xlbhip_field* tmp = cur;
+    cur = oth;
+    oth = tmp;
+  }
+  if (result_in_b) *result_in_b = cur == b ? 1 : 0;
+  return 0;
+}
+
+int xlbhip_run(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const xlbhip_field* bcm, const xlbhip_field* miss, double omega,
+               int64_t t0, int64_t n) {
+  return run_steps(s, a, b, bcm, miss, omega, t0, n, true, nullptr);
+}
+
+int xlbhip_run_any(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const xlbhip_field* bcm, const xlbhip_field* miss, double omega,
+                   int64_t t0, int64_t n, int* result_in_b) {
+  XLB_REQUIRE(result_in_b, "result_in_b is null");
+  return run_steps(s, a, b, bcm, miss, omega, t0, n, false, result_in_b);
+}
+
+int xlbhip_step2_eligible(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss) {
+  if (check_step_fields(s, src, dst, bcm, miss)) return 0;
+  return can_fuse2(s, src, dst, bcm, miss) ? 1 : 0;
+}
+
+int xlbhip_step2(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
+                 double omega, int64_t timestep) {
+  if (int rc = check_step_fields(s, src, dst, bcm, miss)) return rc;
+  if (int rc = require_staged(s, timestep, 2)) return rc;
+  XLB_REQUIRE(can_fuse2(s, src, dst, bcm, miss), "this stepper / field layout has no two-step kernel (see xlbhip_step2_eligible)");
+  if (int rc = prepare_fuse2(s, bcm, miss)) return rc;
+  return step_twice(s, src, dst, bcm, miss, omega, timestep);
+}
+
+int xlbhip_run_timed(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const xlbhip_field* bcm, const xlbhip_field* miss, double omega,
+                     int64_t t0, int64_t n, float* ms, int* result_in_b) {
+  XLB_REQUIRE(s && ms, "null argument");
+  xlbhip_ctx* c = s->ctx;
+  XLB_HIP(hipEventRecord(c->ev_a, c->stream));
+  // (result_in_b == NULL: xlbhip_run's fixed placement; else as xlbhip_run_any)
+  if (int rc = run_steps(s, a, b, bcm, miss, omega, t0, n, result_in_b == nullptr, result_in_b)) return rc;
+  XLB_HIP(hipEventRecord(c->ev_b, c->stream));
+  XLB_HIP(hipEventSynchronize(c->ev_b));
+  XLB_HIP(hipEventElapsedTime(ms, c->ev_a, c->ev_b));
+  return 0;
+}
+
+}  // extern "C"

@@ -5,7 +5,7 @@ slowest spatial axis (array axis 1) and, every step, the populations with c_x = 
 slab faces travel to the right / left ring neighbour (``rightPerm`` / ``leftPerm``, periodic
 wrap included).  Here each rank keeps ghost x-planes, filled before the pull on a dedicated HIP stream
 (csrc/comm.cpp) — by RCCL ``ncclSend``/``ncclRecv``, or by copy-engine pulls out of the neighbours' IPC-mapped
-fields — and overlapped with the update of the planes that do not touch a ghost (csrc/api.hip: step_once, step_twice).
+fields — and overlapped with the update of the planes that do not touch a ghost (csrc/stepper.hip: step_once, step_twice).
 
 Process-group plumbing (rendezvous, unique-id broadcast, barriers, small reductions, gathering
 results for tests) goes through ``rendezvous.py`` — a star of plain TCP sockets with rank 0 as the
