@@ -34,6 +34,7 @@ extern "C" {
 typedef struct xlbhip_ctx xlbhip_ctx;
 typedef struct xlbhip_field xlbhip_field;
 typedef struct xlbhip_stepper xlbhip_stepper;
+typedef struct xlbhip_ibm xlbhip_ibm;
 
 /* element types of a field; mirrors Precision in xlb/precision_policy.py:13-54 */
 enum {
@@ -312,6 +313,39 @@ int xlbhip_run_any(xlbhip_stepper* s, xlbhip_field* f_a, xlbhip_field* f_b, cons
 int xlbhip_run_timed(xlbhip_stepper* s, xlbhip_field* f_a, xlbhip_field* f_b, const xlbhip_field* bc_mask,
                      const xlbhip_field* missing_mask, double omega, int64_t first_timestep, int64_t n_steps,
                      float* device_ms, int* result_in_b);
+
+/* ---- immersed-boundary stepper -------------------------------------------- */
+/* replaces: IBMStepper.warp_implementation and its kernels, xlb/operator/stepper/ibm_stepper.py:156-178 (Peskin's 4-point
+ * weights) and :264-476 (the multi-direct-forcing sweeps).  One xlbhip_ibm_step = xlbhip_step of `stepper` (never the two-step
+ * kernel), then the coupling on the field it wrote: the Lagrangian forces start at zero; per sweep the marker forces are spread to
+ * the cells (acc = sum_k w A F, W = sum_k w), G = relaxation (acc / W - u) where W > 0, the fluid velocity is interpolated back and
+ * F_k += U_k - u_k; from the second sweep on a sweep raises a flag when any |F_k - prev_k|^2 > tolerance^2 and the next sweep runs
+ * only if it was raised (tolerance 0: all sweeps run); finally f_1 += store(feq(rho, u + G) - feq(rho, u)).
+ * Cell (i, j, k) sits at (i + 1/2, j + 1/2, k + 1/2); supports are clipped at the box faces (no periodic wrap).
+ * Everything runs on the markers' footprint (cells with W > 0): no launch and no buffer of the coupling scales with the grid except
+ * one int32 per cell (cell -> footprint slot).  acc and W are accumulated in 64-bit fixed point (per cell: quantum 2^-40 of its largest weight) with integer atomics:
+ * results are bit-identical run to run and independent of the order of the markers.  The early exit is taken on the device; no call
+ * below waits for it except _forces, _iterations and _footprint.
+ * 3-D lattices, fp32 / fp64 storage, fields without ghost planes of nx x ny x nz cells; max_iterations 0 .. 64. */
+int xlbhip_ibm_create(xlbhip_ctx* ctx, xlbhip_stepper* stepper, int lattice, int compute_dtype, int store_dtype, int nx, int ny, int nz,
+                      int max_iterations, double tolerance, double relaxation, xlbhip_ibm** out);
+int xlbhip_ibm_destroy(xlbhip_ibm* ibm);
+/* n markers: positions (n, 3), areas (n), velocities (n, 3), float32, any of them NULL = keep what the device holds (all three are
+ * needed when n changes).  Copied through a pinned staging buffer by hipMemcpyAsync on the compute stream; the host waits only for
+ * the previous copy out of that buffer.  The footprint is rebuilt only when the positions differ from the last ones passed. */
+int xlbhip_ibm_set_markers(xlbhip_ibm* ibm, int64_t n, const float* positions, const float* areas, const float* velocities);
+/* one step f_src -> f_dst with the coupling applied to f_dst (caller swaps), ibm_stepper.py:379-476 */
+int xlbhip_ibm_step(xlbhip_ibm* ibm, const xlbhip_field* f_src, xlbhip_field* f_dst, const xlbhip_field* bc_mask,
+                    const xlbhip_field* missing_mask, double omega, int64_t timestep);
+/* n_steps such steps with fixed markers and the A/B swap done natively; *result_in_b = 1 when the result is in f_b */
+int xlbhip_ibm_run(xlbhip_ibm* ibm, xlbhip_field* f_a, xlbhip_field* f_b, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask,
+                   double omega, int64_t first_timestep, int64_t n_steps, int* result_in_b);
+/* the Lagrangian forces of the last step (ibm_stepper.py:476: s_lagr_forces), (n, 3) widened to double.  Synchronous. */
+int xlbhip_ibm_forces(xlbhip_ibm* ibm, int64_t n, double* forces);
+/* the number of sweeps the last step ran (0 without markers).  Synchronous. */
+int xlbhip_ibm_iterations(xlbhip_ibm* ibm, int* sweeps);
+/* size of the footprint and, with cells != NULL, its linear cell indices ((x * ny + y) * nz + z, in slot order).  Synchronous. */
+int xlbhip_ibm_footprint(xlbhip_ibm* ibm, int64_t* n_cells, int64_t capacity, uint32_t* cells);
 
 /* ---- slab decomposition over ranks (one process per GPU) ------------------ */
 /* semantics reference: xlb/distribute/distribute.py:18-48 (ring exchange of the

@@ -106,6 +106,14 @@ SIGNATURES = {
     "xlbhip_halo_exchange_wide": [_p, _i, _p],
     "xlbhip_step2_eligible": [_p, _p, _p, _p, _p],
     "xlbhip_step2": [_p, _p, _p, _p, _p, _d, _i64],
+    "xlbhip_ibm_create": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _d, _pp],
+    "xlbhip_ibm_destroy": [_p],
+    "xlbhip_ibm_set_markers": [_p, _i64, _p, _p, _p],
+    "xlbhip_ibm_step": [_p, _p, _p, _p, _p, _d, _i64],
+    "xlbhip_ibm_run": [_p, _p, _p, _p, _p, _d, _i64, _i64, C.POINTER(C.c_int)],
+    "xlbhip_ibm_forces": [_p, _i64, _p],
+    "xlbhip_ibm_iterations": [_p, C.POINTER(_i)],
+    "xlbhip_ibm_footprint": [_p, C.POINTER(_i64), _i64, _p],
 }
 
 _lib = None
@@ -597,6 +605,73 @@ class Stepper:
     def free(self):
         if self._h:
             load().xlbhip_stepper_destroy(self._h)
+            self._h = _p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class IBM:
+    """Native immersed-boundary object (xlbhip_ibm_create): the markers, their footprint and the coupling after a stepper's step."""
+
+    def __init__(self, ctx, stepper, lattice_id, compute_code, store_code, shape3, max_iterations, tolerance, relaxation):
+        self.ctx = ctx
+        self._stepper = stepper  # (kept alive: the native object calls into it)
+        self.n = 0
+        self._h = _p()
+        check(load().xlbhip_ibm_create(ctx.handle, stepper._h, lattice_id, compute_code, store_code, int(shape3[0]), int(shape3[1]), int(shape3[2]),
+                                       int(max_iterations), float(tolerance), float(relaxation), C.byref(self._h)))
+
+    @staticmethod
+    def _f32(a, shape):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape:
+            raise ValueError(f"marker array of shape {a.shape}, expected {shape}")
+        return a
+
+    def set_markers(self, n, positions=None, areas=None, velocities=None):
+        """(n, 3) / (n,) / (n, 3) float32 arrays; None keeps what the device holds."""
+        n = int(n)
+        p, a, v = self._f32(positions, (n, 3)), self._f32(areas, (n,)), self._f32(velocities, (n, 3))
+        check(load().xlbhip_ibm_set_markers(self._h, n, *(None if x is None else x.ctypes.data for x in (p, a, v))))
+        self.n = n
+
+    def step(self, f_src, f_dst, bc_mask, missing_mask, omega, timestep):
+        check(load().xlbhip_ibm_step(self._h, _hf(f_src), _hf(f_dst), _h(bc_mask), _h(missing_mask), float(omega), int(timestep)))
+
+    def run(self, f_a, f_b, bc_mask, missing_mask, omega, first_timestep, n_steps):
+        where = C.c_int()
+        check(load().xlbhip_ibm_run(self._h, _hf(f_a), _hf(f_b), _h(bc_mask), _h(missing_mask), float(omega), int(first_timestep), int(n_steps),
+                                    C.byref(where)))
+        return bool(where.value)
+
+    def forces(self):
+        out = np.zeros((self.n, 3), np.float64)
+        check(load().xlbhip_ibm_forces(self._h, self.n, out.ctypes.data))
+        return out
+
+    def iterations(self):
+        n = _i()
+        check(load().xlbhip_ibm_iterations(self._h, C.byref(n)))
+        return n.value
+
+    def footprint(self):
+        """Linear cell indices ((x * ny + y) * nz + z) of the cells the coupling touches."""
+        n = _i64()
+        check(load().xlbhip_ibm_footprint(self._h, C.byref(n), 0, None))
+        cells = np.zeros(n.value, np.uint32)
+        if n.value:
+            check(load().xlbhip_ibm_footprint(self._h, C.byref(n), cells.size, cells.ctypes.data))
+        return cells
+
+    def free(self):
+        if self._h:
+            load().xlbhip_ibm_destroy(self._h)
             self._h = _p()
 
     def __del__(self):

@@ -1,0 +1,323 @@
+// libxlbhip: the immersed-boundary stepper (reference: xlb/operator/stepper/ibm_stepper.py).  One call = the ordinary step of a
+// stepper, then the coupling of ibm_kernels.hpp on the field the step wrote.  The object owns the markers, their footprint and the
+// per-footprint-cell scratch; everything it enqueues goes to the context's compute stream and nothing in a call waits for the device.
+#include <cstddef>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "api_internal.hpp"
+#include "ibm_kernels.hpp"
+
+using namespace xlb;
+
+struct xlbhip_ibm {
+  xlbhip_ctx* ctx = nullptr;
+  xlbhip_stepper* stepper = nullptr;
+  int lattice = 0, cdt = 0, sdt = 0;
+  int nx = 0, ny = 0, nz = 0;
+  int max_sweeps = 0;
+  double tolerance = 0.0, relaxation = 1.0;
+  int64_t n = 0;    // markers
+  int64_t cap = 0;  // slots the footprint arrays hold: min(64 n, cells)
+  // markers: float32 as the caller passes them; staged through ONE pinned buffer [positions 3n | areas n | velocities 3n], guarded
+  // by the event of the last copy out of it
+  DeviceBuf pos, area, vel;
+  PinnedBuf pin;
+  hipEvent_t pin_ev = nullptr;
+  std::vector<float> host_pos;  // what the footprint was built from
+  // footprint
+  DeviceBuf map;    // int32 per grid cell: slot, or -1
+  DeviceBuf list;   // uint32 [cap]: slot -> cell
+  DeviceBuf count;  // int: slots in use
+  DeviceBuf wbits;  // uint32 [cap]: fp32 bit pattern of the slot's largest weight (sets the slot's fixed-point quantum)
+  DeviceBuf W;      // fixed point [cap]
+  DeviceBuf acc;    // fixed point [cap][3]; zero between uses
+  DeviceBuf u, G;   // compute dtype [cap][3]
+  // per marker, compute dtype [n][3]
+  DeviceBuf dk, F;
+  DeviceBuf ctl;  // IbmControl
+  size_t csize() const { return cdt == XLBHIP_F32 ? 4 : 8; }
+  size_t cells() const { return (size_t)nx * ny * nz; }
+};
+
+namespace xlb {
+
+// f(L{}, T{}, S{}) for the object's lattice, compute and store dtypes (3-D lattices; fp32 / fp64 stores)
+template <class Fn>
+static int ibm_dispatch(const xlbhip_ibm* b, Fn&& f) {
+  auto by_types = [&](auto L) {
+    if (b->cdt == XLBHIP_F32) return f(L, float{}, float{});
+    if (b->sdt == XLBHIP_F32) return f(L, double{}, float{});
+    return f(L, double{}, double{});
+  };
+  return b->lattice == XLBHIP_D3Q19 ? by_types(D3Q19{}) : by_types(D3Q27{});
+}
+
+static int ibm_clear_footprint(xlbhip_ibm* b) {
+  if (b->cap == 0) return 0;
+  hipLaunchKernelGGL(k_ibm_clear, blocks_for((size_t)b->cap), 256, 0, b->ctx->stream, b->map.get<int32_t>(), b->list.get<uint32_t>(), b->count.get<int>(),
+                     b->cap);
+  XLB_HIP(hipGetLastError());
+  XLB_HIP(hipMemsetAsync(b->count.get(), 0, sizeof(int), b->ctx->stream));
+  return 0;
+}
+
+// buffers for n markers (the old footprint has been cleared out of the map)
+static int ibm_resize(xlbhip_ibm* b, int64_t n) {
+  b->n = 0;
+  b->cap = 0;
+  b->host_pos.clear();
+  if (n == 0) return 0;
+  const int64_t cap = (int64_t)std::min<size_t>((size_t)n * 64, b->cells());
+  const size_t cs = b->csize();
+  XLB_HIP(b->pos.alloc((size_t)n * 3 * sizeof(float)));
+  XLB_HIP(b->area.alloc((size_t)n * sizeof(float)));
+  XLB_HIP(b->vel.alloc((size_t)n * 3 * sizeof(float)));
+  XLB_HIP(b->pin.alloc((size_t)n * 7 * sizeof(float)));
+  XLB_HIP(b->list.alloc((size_t)cap * sizeof(uint32_t)));
+  XLB_HIP(b->wbits.alloc((size_t)cap * 4));
+  XLB_HIP(b->W.alloc((size_t)cap * 8));
+  XLB_HIP(b->acc.alloc((size_t)cap * 3 * 8));
+  XLB_HIP(b->u.alloc((size_t)cap * 3 * cs));
+  XLB_HIP(b->G.alloc((size_t)cap * 3 * cs));
+  XLB_HIP(b->dk.alloc((size_t)n * 3 * cs));
+  XLB_HIP(b->F.alloc((size_t)n * 3 * cs));
+  hipStream_t st = b->ctx->stream;
+  XLB_HIP(hipMemsetAsync(b->area.get(), 0, (size_t)n * sizeof(float), st));
+  XLB_HIP(hipMemsetAsync(b->vel.get(), 0, (size_t)n * 3 * sizeof(float), st));
+  XLB_HIP(hipMemsetAsync(b->G.get(), 0, (size_t)cap * 3 * cs, st));
+  XLB_HIP(hipMemsetAsync(b->F.get(), 0, (size_t)n * 3 * cs, st));
+  b->n = n;
+  b->cap = cap;
+  return 0;
+}
+
+// cell <-> slot mapping and weight sums of the markers' current positions
+static int ibm_build_footprint(xlbhip_ibm* b) {
+  hipStream_t st = b->ctx->stream;
+  if (int rc = ibm_clear_footprint(b)) return rc;
+  XLB_HIP(hipMemsetAsync(b->wbits.get(), 0, (size_t)b->cap * 4, st));
+  XLB_HIP(hipMemsetAsync(b->W.get(), 0, (size_t)b->cap * 8, st));
+  XLB_HIP(hipMemsetAsync(b->acc.get(), 0, (size_t)b->cap * 3 * 8, st));
+  const Dims d{b->nx, b->ny, b->nz};
+  return by_compute(b->cdt, [&](auto T) {
+    using TT = decltype(T);
+    hipLaunchKernelGGL((k_ibm_mark<TT>), blocks_for((size_t)b->n * 64), 256, 0, st, b->pos.get<float>(), b->n, d, b->map.get<int32_t>(),
+                       b->list.get<uint32_t>(), b->count.get<int>(), b->cap);
+    XLB_HIP(hipGetLastError());
+    hipLaunchKernelGGL((k_ibm_wmax<TT>), blocks_for((size_t)b->n * 64), 256, 0, st, b->pos.get<float>(), b->n, d, b->map.get<int32_t>(),
+                       b->wbits.get<unsigned>(), b->cap);
+    XLB_HIP(hipGetLastError());
+    hipLaunchKernelGGL((k_ibm_weights<TT>), blocks_for((size_t)b->n * 64), 256, 0, st, b->pos.get<float>(), b->n, d, b->map.get<int32_t>(),
+                       b->wbits.get<unsigned>(), b->W.get<unsigned long long>(), b->cap);
+    XLB_HIP(hipGetLastError());
+    return 0;
+  });
+}
+
+// the coupling on f (the field a step has just written)
+static int ibm_couple(xlbhip_ibm* b, xlbhip_field* f) {
+  hipStream_t st = b->ctx->stream;
+  XLB_HIP(hipMemsetAsync(b->ctl.get(), 0, sizeof(IbmControl), st));
+  if (b->n == 0 || b->max_sweeps == 0) return 0;
+  const Dims d{b->nx, b->ny, b->nz};
+  const unsigned slot_blocks = blocks_for((size_t)b->cap), marker_blocks = blocks_for((size_t)b->n), pair_blocks = blocks_for((size_t)b->n * 64);
+  const int residual_on = b->tolerance > 0.0 ? 1 : 0;
+  IbmControl* ctl = b->ctl.get<IbmControl>();
+  const int rc = ibm_dispatch(b, [&](auto L, auto T, auto S) {
+    using LL = decltype(L);
+    using TT = decltype(T);
+    using SS = decltype(S);
+    const float* pos = b->pos.get<float>();
+    const int32_t* map = b->map.get<int32_t>();
+    const int* count = b->count.get<int>();
+    unsigned long long* acc = b->acc.get<unsigned long long>();
+    TT* u = b->u.get<TT>();
+    TT* G = b->G.get<TT>();
+    TT* F = b->F.get<TT>();
+    TT* dk = b->dk.get<TT>();
+    hipLaunchKernelGGL((k_ibm_moments<LL, TT, SS>), slot_blocks, 256, 0, st, static_cast<const SS*>(f->data), f->plane_stride, b->list.get<uint32_t>(), count,
+                       b->cap, u);
+    XLB_HIP(hipGetLastError());
+    hipLaunchKernelGGL((k_ibm_interp<TT>), marker_blocks, 256, 0, st, pos, b->vel.get<float>(), b->n, d, map, b->cap, u, dk, F);
+    XLB_HIP(hipGetLastError());
+    for (int it = 0; it < b->max_sweeps; ++it) {
+      if (it > 0) {  // (the forces are zero in the first sweep: nothing to spread, acc is zero already)
+        hipLaunchKernelGGL((k_ibm_spread<TT>), pair_blocks, 256, 0, st, it, residual_on, ctl, pos, b->area.get<float>(), F, b->n, d, map, b->cap,
+                           b->wbits.get<unsigned>(), acc);
+        XLB_HIP(hipGetLastError());
+      }
+      hipLaunchKernelGGL((k_ibm_correct<TT>), slot_blocks, 256, 0, st, it, residual_on, ctl, count, b->cap, b->wbits.get<unsigned>(), b->W.get<unsigned long long>(), acc, u,
+                         (TT)b->relaxation, G);
+      XLB_HIP(hipGetLastError());
+      hipLaunchKernelGGL((k_ibm_update<TT>), marker_blocks, 256, 0, st, it, residual_on, ctl, b->n, dk, F, (TT)(b->tolerance * b->tolerance));
+      XLB_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL((k_ibm_apply<LL, TT, SS>), slot_blocks, 256, 0, st, static_cast<SS*>(f->data), f->plane_stride, b->list.get<uint32_t>(), count, b->cap,
+                       G);
+    XLB_HIP(hipGetLastError());
+    return 0;
+  });
+  if (rc) return rc;
+  touch(f);
+  return 0;
+}
+
+static int ibm_check_field(const xlbhip_ibm* b, const xlbhip_field* f) {
+  XLB_REQUIRE(f, "null field");
+  XLB_REQUIRE(f->halo == 0, "the immersed-boundary stepper does not run on slab-decomposed fields (ghost planes)");
+  XLB_REQUIRE(f->nx == b->nx && f->ny == b->ny && f->nz == b->nz, "field of %d x %d x %d cells, the immersed-boundary stepper was made for %d x %d x %d", f->nx,
+              f->ny, f->nz, b->nx, b->ny, b->nz);
+  XLB_REQUIRE(f->dtype == b->sdt && f->card == lattice_q(b->lattice), "population field does not match the immersed-boundary stepper's lattice / store dtype");
+  return 0;
+}
+
+}  // namespace xlb
+
+extern "C" {
+
+int xlbhip_ibm_create(xlbhip_ctx* c, xlbhip_stepper* stepper, int lattice, int compute_dtype, int store_dtype, int nx, int ny, int nz,
+                      int max_iterations, double tolerance, double relaxation, xlbhip_ibm** out) {
+  XLB_REQUIRE(c && stepper && out, "null argument");
+  XLB_REQUIRE(lattice == XLBHIP_D3Q19 || lattice == XLBHIP_D3Q27, "the immersed-boundary stepper needs a 3-D lattice (2-D grids are not supported)");
+  XLB_REQUIRE(compute_dtype == XLBHIP_F32 || compute_dtype == XLBHIP_F64, "bad compute dtype %d", compute_dtype);
+  XLB_REQUIRE(store_dtype == XLBHIP_F32 || store_dtype == XLBHIP_F64, "the immersed-boundary stepper does not support fp16 storage");
+  XLB_REQUIRE(dtype_size(store_dtype) <= dtype_size(compute_dtype), "bad store dtype %d for compute dtype %d", store_dtype, compute_dtype);
+  XLB_REQUIRE(nx > 0 && ny > 0 && nz > 0 && (size_t)nx * ny * nz < ((size_t)1 << 31), "bad grid %d x %d x %d", nx, ny, nz);
+  XLB_REQUIRE(max_iterations >= 0 && max_iterations <= IBM_MAX_SWEEPS, "ibm_max_iterations must be 0 .. %d", IBM_MAX_SWEEPS);
+  XLB_REQUIRE(tolerance >= 0.0, "ibm_tolerance must not be negative");
+  XLB_HIP(hipSetDevice(c->device));
+  auto b = std::make_unique<xlbhip_ibm>();
+  b->ctx = c;
+  b->stepper = stepper;
+  b->lattice = lattice;
+  b->cdt = compute_dtype;
+  b->sdt = store_dtype;
+  b->nx = nx;
+  b->ny = ny;
+  b->nz = nz;
+  b->max_sweeps = max_iterations;
+  b->tolerance = tolerance;
+  b->relaxation = relaxation;
+  XLB_HIP(b->map.alloc(b->cells() * sizeof(int32_t)));
+  XLB_HIP(b->count.alloc(sizeof(int)));
+  XLB_HIP(b->ctl.alloc(sizeof(IbmControl)));
+  XLB_HIP(hipMemsetAsync(b->map.get(), 0xff, b->cells() * sizeof(int32_t), c->stream));  // every cell: no slot (-1)
+  XLB_HIP(hipMemsetAsync(b->count.get(), 0, sizeof(int), c->stream));
+  XLB_HIP(hipMemsetAsync(b->ctl.get(), 0, sizeof(IbmControl), c->stream));
+  XLB_HIP(hipEventCreateWithFlags(&b->pin_ev, hipEventDisableTiming));
+  XLB_HIP(hipEventRecord(b->pin_ev, c->stream));
+  *out = b.release();
+  return 0;
+}
+
+int xlbhip_ibm_destroy(xlbhip_ibm* b) {
+  if (!b) return 0;
+  (void)hipSetDevice(b->ctx->device);
+  (void)hipStreamSynchronize(b->ctx->stream);  // copies may still read the pinned buffer
+  if (b->pin_ev) (void)hipEventDestroy(b->pin_ev);
+  delete b;
+  return 0;
+}
+
+int xlbhip_ibm_set_markers(xlbhip_ibm* b, int64_t n, const float* positions, const float* areas, const float* velocities) {
+  XLB_REQUIRE(b && n >= 0, "bad argument");
+  XLB_REQUIRE((size_t)n < ((size_t)1 << 25), "too many markers (%lld)", (long long)n);
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  if (n != b->n) {
+    XLB_REQUIRE(n == 0 || (positions && areas && velocities), "a new number of markers needs positions, areas and velocities");
+    if (int rc = ibm_clear_footprint(b)) return rc;
+    XLB_HIP(hipStreamSynchronize(c->stream));
+    if (int rc = ibm_resize(b, n)) return rc;
+  }
+  if (n == 0) return 0;
+  XLB_HIP(hipEventSynchronize(b->pin_ev));  // the previous copy out of the pinned buffer (not the kernels)
+  float* pin = b->pin.get<float>();
+  const size_t n3 = (size_t)n * 3 * sizeof(float);
+  bool moved = false;
+  if (positions) {
+    moved = b->host_pos.size() != (size_t)n * 3 || std::memcmp(b->host_pos.data(), positions, n3) != 0;
+    if (moved) {
+      b->host_pos.assign(positions, positions + (size_t)n * 3);
+      std::memcpy(pin, positions, n3);
+      XLB_HIP(hipMemcpyAsync(b->pos.get(), pin, n3, hipMemcpyHostToDevice, c->stream));
+    }
+  }
+  if (areas) {
+    std::memcpy(pin + 3 * n, areas, (size_t)n * sizeof(float));
+    XLB_HIP(hipMemcpyAsync(b->area.get(), pin + 3 * n, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  }
+  if (velocities) {
+    std::memcpy(pin + 4 * n, velocities, n3);
+    XLB_HIP(hipMemcpyAsync(b->vel.get(), pin + 4 * n, n3, hipMemcpyHostToDevice, c->stream));
+  }
+  XLB_HIP(hipEventRecord(b->pin_ev, c->stream));
+  if (moved) return ibm_build_footprint(b);
+  return 0;
+}
+
+int xlbhip_ibm_step(xlbhip_ibm* b, const xlbhip_field* f_src, xlbhip_field* f_dst, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask,
+                    double omega, int64_t timestep) {
+  XLB_REQUIRE(b, "null argument");
+  if (int rc = ibm_check_field(b, f_src)) return rc;
+  if (int rc = ibm_check_field(b, f_dst)) return rc;
+  if (int rc = xlbhip_step(b->stepper, f_src, f_dst, bc_mask, missing_mask, omega, timestep)) return rc;
+  return ibm_couple(b, f_dst);
+}
+
+int xlbhip_ibm_run(xlbhip_ibm* b, xlbhip_field* f_a, xlbhip_field* f_b, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, double omega,
+                   int64_t first_timestep, int64_t n_steps, int* result_in_b) {
+  XLB_REQUIRE(b && result_in_b && n_steps >= 0, "bad argument");
+  xlbhip_field* cur = f_a;
+  xlbhip_field* oth = f_b;
+  for (int64_t i = 0; i < n_steps; ++i) {
+    if (int rc = xlbhip_ibm_step(b, cur, oth, bc_mask, missing_mask, omega, first_timestep + i)) return rc;
+    std::swap(cur, oth);
+  }
+  *result_in_b = cur == f_b ? 1 : 0;
+  return 0;
+}
+
+int xlbhip_ibm_forces(xlbhip_ibm* b, int64_t n, double* forces) {
+  XLB_REQUIRE(b && n == b->n && (n == 0 || forces), "xlbhip_ibm_forces: expected room for %lld markers", b ? (long long)b->n : 0LL);
+  if (n == 0) return 0;
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  std::vector<char> host((size_t)n * 3 * b->csize());
+  XLB_HIP(hipMemcpyAsync(host.data(), b->F.get(), host.size(), hipMemcpyDeviceToHost, c->stream));
+  XLB_HIP(hipStreamSynchronize(c->stream));
+  by_compute(b->cdt, [&](auto T) {
+    const auto* v = reinterpret_cast<const decltype(T)*>(host.data());
+    for (size_t i = 0; i < (size_t)n * 3; ++i) forces[i] = (double)v[i];
+    return 0;
+  });
+  return 0;
+}
+
+int xlbhip_ibm_iterations(xlbhip_ibm* b, int* sweeps) {
+  XLB_REQUIRE(b && sweeps, "null argument");
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipMemcpyAsync(sweeps, b->ctl.get<char>() + offsetof(IbmControl, sweeps), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  XLB_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int xlbhip_ibm_footprint(xlbhip_ibm* b, int64_t* n_cells, int64_t capacity, uint32_t* cells) {
+  XLB_REQUIRE(b && n_cells, "null argument");
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  int count = 0;
+  XLB_HIP(hipMemcpyAsync(&count, b->count.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  XLB_HIP(hipStreamSynchronize(c->stream));
+  *n_cells = count;
+  if (cells && count > 0) {
+    XLB_REQUIRE(capacity >= count, "xlbhip_ibm_footprint: room for %lld cells, the footprint has %d", (long long)capacity, count);
+    XLB_HIP(hipMemcpy(cells, b->list.get(), (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+}  // extern "C"
