@@ -35,6 +35,7 @@ typedef struct xlbhip_ctx xlbhip_ctx;
 typedef struct xlbhip_field xlbhip_field;
 typedef struct xlbhip_stepper xlbhip_stepper;
 typedef struct xlbhip_ibm xlbhip_ibm;
+typedef struct xlbhip_stats xlbhip_stats;
 
 /* element types of a field; mirrors Precision in xlb/precision_policy.py:13-54 */
 enum {
@@ -346,6 +347,30 @@ int xlbhip_ibm_forces(xlbhip_ibm* ibm, int64_t n, double* forces);
 int xlbhip_ibm_iterations(xlbhip_ibm* ibm, int* sweeps);
 /* size of the footprint and, with cells != NULL, its linear cell indices ((x * ny + y) * nz + z, in slot order).  Synchronous. */
 int xlbhip_ibm_footprint(xlbhip_ibm* ibm, int64_t* n_cells, int64_t capacity, uint32_t* cells);
+
+/* ---- flow statistics ------------------------------------------------------- */
+/* No counterpart in the reference: its drivers copy whole fields to the host and reduce them in NumPy (e.g.
+ * examples/cfd/turbulent_channel_3d.py).  The object keeps running fp64 sums on the device of, per sampled cell: 1 (count), rho,
+ * rho^2, u_a (d components), u_a u_b (xx, xy, xz, yy, yz, zz; three in 2-D) with order 2 (12 channels in 3-D, 8 in 2-D), or count,
+ * rho, u_a with order 1.  rho and u are the values xlbhip_macroscopic writes (compute dtype), promoted to double before any product
+ * or sum.  keep_mask says which STORAGE axes are kept (bit 0: x, bit 1: y, bit 2: z; a 2-D grid is nx = 1); the others are summed
+ * over, so there are (kept nx) * (kept ny) * (kept nz) bins, x slowest.  exclude: 256 bits, bit v set = cells whose bc_mask value is
+ * v are not sampled.  Ghost planes are never sampled.  No floating-point atomics: which cells meet in which partial sum, and the
+ * order the partial sums are added in, depend on (nx, ny, nz, keep_mask, order) only, so the sums are bit-identical from run to run
+ * and from device to device.  The partial sums take at most 48 MiB of scratch; the running sums channels * bins * 8 bytes. */
+int xlbhip_stats_create(xlbhip_ctx* ctx, int lattice, int compute_dtype, int nx, int ny, int nz, int keep_mask, int order,
+                        const uint32_t exclude[8], xlbhip_stats** out);
+int xlbhip_stats_destroy(xlbhip_stats* stats);
+/* add one sample of f (any store dtype the compute dtype can hold; with or without ghost planes) to the running sums; bc_mask NULL:
+ * every cell is sampled.  Enqueues on the compute stream; the host neither waits nor reads anything. */
+int xlbhip_stats_sample(xlbhip_stats* stats, const xlbhip_field* f, const xlbhip_field* bc_mask);
+/* Synchronous.  sums (capacity = channels * bins doubles, [channel][bin]; NULL: skipped), the number of samples since the last
+ * reset, the largest u.u over the sampled cells of the LAST sample (compute-dtype arithmetic, (ux ux + uy uy) + uz uz), and the
+ * number of sampled cells whose rho or u was not finite: nonfinite[0] in the last sample, nonfinite[1] since the last reset.  Such
+ * a cell adds to these counters and to nothing else. */
+int xlbhip_stats_read(xlbhip_stats* stats, int64_t capacity, double* sums, int64_t* samples, double* max_u2, int64_t nonfinite[2]);
+/* zero the sums, the sample count and the watchdog (enqueued) */
+int xlbhip_stats_reset(xlbhip_stats* stats);
 
 /* ---- slab decomposition over ranks (one process per GPU) ------------------ */
 /* semantics reference: xlb/distribute/distribute.py:18-48 (ring exchange of the

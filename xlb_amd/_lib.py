@@ -114,6 +114,11 @@ SIGNATURES = {
     "xlbhip_ibm_forces": [_p, _i64, _p],
     "xlbhip_ibm_iterations": [_p, C.POINTER(_i)],
     "xlbhip_ibm_footprint": [_p, C.POINTER(_i64), _i64, _p],
+    "xlbhip_stats_create": [_p, _i, _i, _i, _i, _i, _i, _i, _p, _pp],
+    "xlbhip_stats_destroy": [_p],
+    "xlbhip_stats_sample": [_p, _p, _p],
+    "xlbhip_stats_read": [_p, _i64, _p, C.POINTER(_i64), C.POINTER(_d), _p],
+    "xlbhip_stats_reset": [_p],
 }
 
 _lib = None
@@ -672,6 +677,47 @@ class IBM:
     def free(self):
         if self._h:
             load().xlbhip_ibm_destroy(self._h)
+            self._h = _p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Stats:
+    """Native flow-statistics object (xlbhip_stats_create): running sums [channel][bin] and the watchdog's counters."""
+
+    def __init__(self, ctx, lattice_id, compute_code, shape3, keep_mask, order, exclude_ids):
+        self.ctx = ctx
+        bits = np.zeros(8, np.uint32)
+        for v in exclude_ids:
+            bits[int(v) >> 5] |= np.uint32(1 << (int(v) & 31))
+        self.samples = 0
+        self._h = _p()
+        check(load().xlbhip_stats_create(ctx.handle, lattice_id, compute_code, int(shape3[0]), int(shape3[1]), int(shape3[2]), int(keep_mask), int(order),
+                                         bits.ctypes.data, C.byref(self._h)))
+
+    def sample(self, f, bc_mask):
+        # (read-only: through .handle, which flushes work deferred on the fields, without invalidating what is cached on them)
+        check(load().xlbhip_stats_sample(self._h, f.handle, None if bc_mask is None else bc_mask.handle))
+        self.samples += 1
+
+    def read(self, n_sums):
+        """(sums, samples, max u.u of the last sample, non-finite cells of the last sample, ... since the last reset); synchronises."""
+        sums = np.zeros(int(n_sums), np.float64)
+        samples, umax, bad = _i64(), _d(), np.zeros(2, np.int64)
+        check(load().xlbhip_stats_read(self._h, sums.size, sums.ctypes.data, C.byref(samples), C.byref(umax), bad.ctypes.data))
+        return sums, samples.value, umax.value, int(bad[0]), int(bad[1])
+
+    def reset(self):
+        check(load().xlbhip_stats_reset(self._h))
+        self.samples = 0
+
+    def free(self):
+        if self._h:
+            load().xlbhip_stats_destroy(self._h)
             self._h = _p()
 
     def __del__(self):
