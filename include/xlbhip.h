@@ -348,6 +348,40 @@ int xlbhip_ibm_iterations(xlbhip_ibm* ibm, int* sweeps);
 /* size of the footprint and, with cells != NULL, its linear cell indices ((x * ny + y) * nz + z, in slot order).  Synchronous. */
 int xlbhip_ibm_footprint(xlbhip_ibm* ibm, int64_t* n_cells, int64_t capacity, uint32_t* cells);
 
+/* -- rigid bodies with prescribed motion, and the loads on them --
+ * replaces: the `rotate_rotor` kernel of examples/ibm/wind_turbine_ibm.py:160-199, which turns the rotor's vertices and sets their
+ * velocities on the device after every step; the call order is that of xlb/operator/stepper/ibm_stepper.py:379-476 with the markers
+ * placed first.  The per-body force and torque have no counterpart in the reference (its drivers sum marker forces on the host).
+ *
+ * A body is a range [first, first + count) of the markers; bodies are disjoint, at most 64.  moving[i] != 0: before every step
+ * marker k of body i is placed at X = c + R (X0 - centre0_i) and given U = v + w x (X - c), with X0 the position last UPLOADED
+ * (the reference position), and (R, c, w, v) the body's pose at that timestep: 18 doubles, R row-major first.  fp64 in the order
+ * X_a = ((R_a0 d_0 + R_a1 d_1) + R_a2 d_2) + c_a, rounded to float32; U is evaluated on the rounded X.  The uploaded velocities of
+ * such markers are ignored.  Markers of bodies at rest and of no body are never touched.  When at least one body moves the
+ * footprint is rebuilt every step; bodies at rest alone leave the step's launches as they are and only add the loads.
+ * After the coupling of every step: loads[i] = (-sum_k A_k F_k, -sum_k A_k (X_k - c_i) x F_k) over the body's markers, every
+ * factor a double before any product, summed over chunks of 256 consecutive markers with a fixed tree and the chunks in index order
+ * (no floating-point atomics: bit-identical from run to run); c_i is the step's pose centre, centre0_i while no body moves.
+ * Replaces any earlier declaration; n_bodies = 0 returns to the plain stepper.  Waits for the stream (set-up call).  The number of
+ * markers cannot change while bodies are declared. */
+int xlbhip_ibm_set_bodies(xlbhip_ibm* ibm, int n_bodies, const int64_t* first, const int64_t* count, const int* moving,
+                          const double* centre0);
+/* the poses [n_steps][n_bodies][18] of timesteps first_timestep .. first_timestep + n_steps - 1 (every body, also those at rest),
+ * replacing what was staged before; at most XLBHIP_IBM_POSE_BYTES at once.  Copied through a pinned buffer by hipMemcpyAsync on the
+ * compute stream, behind the steps already enqueued; the host waits only for the previous copy out of that buffer.  While a body
+ * moves, xlbhip_ibm_step / _run fail BEFORE enqueuing anything when a timestep of theirs is not staged (the message names it). */
+#define XLBHIP_IBM_POSE_BYTES (1 << 20)
+int xlbhip_ibm_stage_poses(xlbhip_ibm* ibm, int64_t first_timestep, int64_t n_steps, const double* poses);
+/* the loads of the last step, [n_bodies][6] (zero before the first).  Synchronous. */
+int xlbhip_ibm_loads(xlbhip_ibm* ibm, int n_bodies, double* loads);
+/* from now on every step also writes its loads to the next of n_rows rows of a device buffer (n_rows = 0: stop; steps beyond the
+ * last row are not recorded); _loads_history reads the first n_rows rows recorded so far, [n_rows][n_bodies][6], and is asked
+ * before the recording is stopped or restarted.  Synchronous. */
+int xlbhip_ibm_record_loads(xlbhip_ibm* ibm, int64_t n_rows);
+int xlbhip_ibm_loads_history(xlbhip_ibm* ibm, int64_t n_rows, double* loads);
+/* the markers as the device holds them now (after the last step's move), (n, 3) float32 each; NULL: skipped.  Synchronous. */
+int xlbhip_ibm_download_markers(xlbhip_ibm* ibm, int64_t n, float* positions, float* velocities);
+
 /* ---- flow statistics ------------------------------------------------------- */
 /* No counterpart in the reference: its drivers copy whole fields to the host and reduce them in NumPy (e.g.
  * examples/cfd/turbulent_channel_3d.py).  The object keeps running fp64 sums on the device of, per sampled cell: 1 (count), rho,

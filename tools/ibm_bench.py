@@ -7,7 +7,15 @@ D3Q27 KBC FP32FP32, radius 25, about one marker per cell of surface).
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/ibm_bench.py --trace-steps 20      # the coupling kernels and their launch sizes
 
 Prints one JSON line: the per-round times, their medians, the footprint and the bytes the coupling moves per step (counted from the
-shapes: see coupling_bytes)."""
+shapes: see coupling_bytes).
+
+    python tools/ibm_bench.py --moving [--steps 100 --rounds 5]     # the same sphere spinning about its own axis
+    python tools/ibm_bench.py --moving --counted-only               # no GPU: what move / rebuild / loads add per step, from the shapes
+
+--moving times, interleaved, (a) the loop the host drives — NumPy kinematics, markers.update(vertices, velocities) and one call per
+step —, (b) the native run with the sphere declared as a body with a RigidMotion and (c) the native run with the markers at rest, and
+reports (a) and (b) in ms/step and (b - c) / b, the share of the step that moving the markers, rebuilding the footprint and summing
+the loads take."""
 
 import argparse
 import json
@@ -37,6 +45,79 @@ def coupling_bytes(n_markers, n_slots, q, sweeps, store=4, compute=4):
     return n_slots * per_slot + 64 * n_markers * per_pair + n_markers * per_marker
 
 
+def moving_counts(n_markers, n_slots, n_bodies=1, compute=4, cap=None):
+    """Launches and bytes one step of a MOVING body adds to the call, from the shapes (csrc/ibm.hip: ibm_move, ibm_build_footprint,
+    ibm_body_loads).  move: per marker 12 (X0) + 4 (body id) read, 12 + 12 written.  rebuild: k_ibm_clear 8 per slot in use; three
+    memsets over the slot CAPACITY (wbits 4, W 8, acc 24 per slot) and one of 4 bytes; mark / wmax / weights per marker-candidate
+    pair 4 + (4 + 4) + (4 + 4 + 8), per slot in use 8 (list, map), per marker 3 x 12 (positions).  loads: per marker 3 T + 4 + 12
+    read, per chunk of 256 markers 48 written and read, per body 48 written (twice when a history is recorded).  Poses: 144 bytes
+    per body and step cross the host link, one copy per chunk of up to 256 steps."""
+    cap = min(64 * n_markers, cap) if cap else 64 * n_markers
+    chunks = n_bodies * -(-(n_markers // n_bodies) // 256)
+    move = {"launches": 1, "bytes": n_markers * 40}
+    rebuild = {"launches": 8, "kernels": 4, "memsets": 4, "bytes": n_slots * 8 + cap * 36 + 4 + 64 * n_markers * 28 + n_slots * 8 + n_markers * 36,
+               "of_which_memsets_over_the_capacity": cap * 36}
+    loads = {"launches": 2, "bytes": n_markers * (3 * compute + 16) + chunks * 96 + n_bodies * 96}
+    return {"move": move, "rebuild": rebuild, "loads": loads, "launches_added": 11, "bytes_added": move["bytes"] + rebuild["bytes"] + loads["bytes"],
+            "pose_bytes_over_the_host_link": 144 * n_bodies}
+
+
+def bench_moving(args, ctx, ibm, make_fields, vertices, velocities, centre, omega):
+    from xlb_amd.helper.ibm_helper import IBMBody, RigidMotion
+
+    motion = RigidMotion(centre=centre, axis=(0.0, 0.0, 1.0), rate=args.rate)
+    f_0, f_1, bc_mask, missing_mask = make_fields()
+    markers = ibm._markers
+    x0 = vertices.astype(np.float64) - centre
+    clock = [0]
+
+    def host_loop(f_0, f_1, n):
+        for _ in range(n):
+            t = clock[0]
+            R, c, w, v = motion.at(t)
+            x = x0 @ R.T
+            markers.update(vertices=(x + c).astype(np.float32), velocities=(v + np.cross(w, x)).astype(np.float32))
+            ibm(f_0, f_1, markers, None, None, bc_mask, missing_mask, omega, t)
+            f_0, f_1 = f_1, f_0
+            clock[0] += 1
+        return f_0, f_1
+
+    def timed(fn):
+        import time
+
+        ctx.sync()
+        t0 = time.perf_counter()
+        out = fn()
+        ctx.sync()
+        return out, (time.perf_counter() - t0) * 1e3
+
+    def native(f_0, f_1, n, bodies):
+        markers.update(vertices=vertices, velocities=velocities)
+        ibm.set_bodies(bodies)
+        out = ibm.run(f_0, f_1, bc_mask, missing_mask, omega, n, first_timestep=clock[0])
+        clock[0] += n
+        return out
+
+    body = [IBMBody(markers=slice(0, len(vertices)), motion=motion)]
+    times = {"host_loop": [], "native": [], "at_rest": []}
+    f_0, f_1 = host_loop(f_0, f_1, args.warmup)
+    f_0, f_1 = native(f_0, f_1, args.warmup, body)
+    for _ in range(args.rounds):  # interleaved: whatever state the machine is in is shared by the three
+        ibm.set_bodies([])
+        (f_0, f_1), ms = timed(lambda: host_loop(f_0, f_1, args.steps))
+        times["host_loop"].append(ms / args.steps)
+        (f_0, f_1), ms = timed(lambda: native(f_0, f_1, args.steps, body))
+        times["native"].append(ms / args.steps)
+        (f_0, f_1), ms = timed(lambda: native(f_0, f_1, args.steps, []))
+        times["at_rest"].append(ms / args.steps)
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    slots = int(ibm.ibm_footprint().size)
+    return {"moving": True, "markers": len(vertices), "rate": args.rate, "footprint_cells": slots, "ms_per_step": times, "median_host_loop": med["host_loop"],
+            "median_native": med["native"], "median_at_rest": med["at_rest"], "native_over_host_loop": med["native"] / med["host_loop"],
+            "move_rebuild_loads_share_of_step": (med["native"] - med["at_rest"]) / med["native"], "counted": moving_counts(len(vertices), slots),
+            "finite": bool(np.isfinite(f_0.numpy()).all())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nx", type=int, default=525)
@@ -49,7 +130,19 @@ def main():
     ap.add_argument("--sweeps", type=int, default=4)
     ap.add_argument("--trace-steps", type=int, default=0, help="only run this many IBM steps (for a profiler run)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--moving", action="store_true", help="the sphere spins about its own axis: host-driven loop against the native run")
+    ap.add_argument("--rate", type=float, default=0.002, help="--moving: radians per step (surface speed = rate x radius)")
+    ap.add_argument("--counted-only", action="store_true", help="--moving: print what is counted from the shapes and stop (no GPU needed)")
+    ap.add_argument("--footprint-cells", type=int, default=43316, help="--counted-only: the footprint (profiles/ibm_coupling.md has the bench case's)")
     args = ap.parse_args()
+
+    if args.moving and args.counted_only:
+        subdivisions = 0
+        while 4.0 * np.pi * args.radius**2 / (10 * 4**subdivisions + 2) > 1.0 and subdivisions < 7:
+            subdivisions += 1
+        print(json.dumps({"markers": 10 * 4**subdivisions + 2, "footprint_cells": args.footprint_cells,
+                          "counted": moving_counts(10 * 4**subdivisions + 2, args.footprint_cells, cap=args.nx * args.ny * args.nz)}))
+        return
 
     policy = PrecisionPolicy.FP32FP32
     lattice = xlb.velocity_set.D3Q27(precision_policy=policy, compute_backend=ComputeBackend.HIP)
@@ -69,13 +162,21 @@ def main():
     while 4.0 * np.pi * args.radius**2 / (10 * 4**subdivisions + 2) > 1.0 and subdivisions < 7:
         subdivisions += 1
     unit, faces = icosphere(subdivisions)
-    vertices = (unit * args.radius + np.array([args.nx / 4 + 0.3, args.ny / 2 + 0.2, args.nz / 2 - 0.1])).astype(np.float32)
+    centre = np.array([args.nx / 4 + 0.3, args.ny / 2 + 0.2, args.nz / 2 - 0.1])
+    vertices = (unit * args.radius + centre).astype(np.float32)
     areas = calculate_voronoi_areas(vertices, faces)
     velocities = np.zeros_like(vertices)
 
     ibm = IBMStepper(grid=grid, boundary_conditions=bcs, collision_type="KBC", ibm_max_iterations=args.sweeps, ibm_tolerance=0.0)
     f_0, f_1, bc_mask, missing_mask = ibm.prepare_fields()
     ibm.markers(vertices, areas, velocities)
+    if args.moving:
+        line = json.dumps(bench_moving(args, ctx, ibm, lambda: (f_0, f_1, bc_mask, missing_mask), vertices, velocities, centre, omega))
+        print(line)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     if args.trace_steps:
         ibm.run(f_0, f_1, bc_mask, missing_mask, omega, args.trace_steps)
         ctx.sync()

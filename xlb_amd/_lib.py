@@ -114,6 +114,12 @@ SIGNATURES = {
     "xlbhip_ibm_forces": [_p, _i64, _p],
     "xlbhip_ibm_iterations": [_p, C.POINTER(_i)],
     "xlbhip_ibm_footprint": [_p, C.POINTER(_i64), _i64, _p],
+    "xlbhip_ibm_set_bodies": [_p, _i, _p, _p, _p, _p],
+    "xlbhip_ibm_stage_poses": [_p, _i64, _i64, _p],
+    "xlbhip_ibm_loads": [_p, _i, _p],
+    "xlbhip_ibm_record_loads": [_p, _i64],
+    "xlbhip_ibm_loads_history": [_p, _i64, _p],
+    "xlbhip_ibm_download_markers": [_p, _i64, _p, _p],
     "xlbhip_stats_create": [_p, _i, _i, _i, _i, _i, _i, _i, _p, _pp],
     "xlbhip_stats_destroy": [_p],
     "xlbhip_stats_sample": [_p, _p, _p],
@@ -626,6 +632,7 @@ class IBM:
         self.ctx = ctx
         self._stepper = stepper  # (kept alive: the native object calls into it)
         self.n = 0
+        self.n_bodies = 0
         self._h = _p()
         check(load().xlbhip_ibm_create(ctx.handle, stepper._h, lattice_id, compute_code, store_code, int(shape3[0]), int(shape3[1]), int(shape3[2]),
                                        int(max_iterations), float(tolerance), float(relaxation), C.byref(self._h)))
@@ -673,6 +680,41 @@ class IBM:
         if n.value:
             check(load().xlbhip_ibm_footprint(self._h, C.byref(n), cells.size, cells.ctypes.data))
         return cells
+
+    POSE_BYTES = 1 << 20  # XLBHIP_IBM_POSE_BYTES: what stage_poses takes at once
+
+    def set_bodies(self, first, count, moving, centre0):
+        """Ranges [first, first + count) of the markers, which of them move, their reference points (n_bodies, 3)."""
+        first, count = np.ascontiguousarray(first, np.int64), np.ascontiguousarray(count, np.int64)
+        moving, centre0 = np.ascontiguousarray(moving, np.int32), np.ascontiguousarray(centre0, np.float64)
+        check(load().xlbhip_ibm_set_bodies(self._h, len(first), first.ctypes.data, count.ctypes.data, moving.ctypes.data, centre0.ctypes.data))
+        self.n_bodies = len(first)
+
+    def stage_poses(self, first_timestep, poses):
+        """(n_steps, n_bodies, 18) float64: R | c | w | v of timesteps first_timestep ..."""
+        poses = np.ascontiguousarray(poses, np.float64)
+        if poses.ndim != 3 or poses.shape[1:] != (self.n_bodies, 18):
+            raise ValueError(f"poses of shape {poses.shape}, expected (n_steps, {self.n_bodies}, 18)")
+        check(load().xlbhip_ibm_stage_poses(self._h, int(first_timestep), poses.shape[0], poses.ctypes.data))
+
+    def loads(self):
+        out = np.zeros((self.n_bodies, 6), np.float64)
+        check(load().xlbhip_ibm_loads(self._h, self.n_bodies, out.ctypes.data))
+        return out
+
+    def record_loads(self, n_rows):
+        check(load().xlbhip_ibm_record_loads(self._h, int(n_rows)))
+
+    def loads_history(self, n_rows):
+        out = np.zeros((int(n_rows), self.n_bodies, 6), np.float64)
+        check(load().xlbhip_ibm_loads_history(self._h, int(n_rows), out.ctypes.data))
+        return out
+
+    def download_markers(self, positions=True, velocities=True):
+        p = np.zeros((self.n, 3), np.float32) if positions else None
+        v = np.zeros((self.n, 3), np.float32) if velocities else None
+        check(load().xlbhip_ibm_download_markers(self._h, self.n, *(None if x is None else x.ctypes.data for x in (p, v))))
+        return p, v
 
     def free(self):
         if self._h:

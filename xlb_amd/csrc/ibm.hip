@@ -8,6 +8,7 @@
 
 #include "api_internal.hpp"
 #include "ibm_kernels.hpp"
+#include "ibm_motion_kernels.hpp"
 
 using namespace xlb;
 
@@ -37,6 +38,27 @@ struct xlbhip_ibm {
   // per marker, compute dtype [n][3]
   DeviceBuf dk, F;
   DeviceBuf ctl;  // IbmControl
+  // rigid bodies (xlbhip_ibm_set_bodies): disjoint ranges of the markers; the ones that move are placed by k_ibm_move before every step
+  int n_bodies = 0;
+  bool any_moving = false;
+  DeviceBuf pos0;       // float [n][3]: the reference positions X0 the poses are applied to
+  bool pos0_valid = false;  // false: `pos` still holds them (nothing has moved the markers since they were uploaded)
+  DeviceBuf move_id;    // int32 [n]: body of the marker when that body moves, else -1
+  DeviceBuf centre0;    // double [n_bodies][3]
+  DeviceBuf rest_pose;  // double [n_bodies][18]: R = 1, c = centre0, w = v = 0 — what the loads read while no body moves
+  // poses of the staged timesteps pose_first .. pose_first + pose_count - 1, [step][body][18]; staged through pose_pin, which pose_ev guards
+  DeviceBuf pose;
+  PinnedBuf pose_pin;
+  hipEvent_t pose_ev = nullptr;
+  int64_t pose_first = 0, pose_count = 0;
+  // loads
+  int64_t n_chunks = 0;
+  DeviceBuf chunks;   // IbmLoadChunk [n_chunks], body after body
+  DeviceBuf chunk0;   // int32 [n_bodies + 1]: first chunk of every body
+  DeviceBuf partial;  // double [n_chunks][6]
+  DeviceBuf loads;    // double [n_bodies][6]
+  DeviceBuf hist;     // double [hist_rows][n_bodies][6], row hist_next is the next step's
+  int64_t hist_rows = 0, hist_next = 0;
   size_t csize() const { return cdt == XLBHIP_F32 ? 4 : 8; }
   size_t cells() const { return (size_t)nx * ny * nz; }
 };
@@ -68,6 +90,7 @@ static int ibm_resize(xlbhip_ibm* b, int64_t n) {
   b->n = 0;
   b->cap = 0;
   b->host_pos.clear();
+  b->pos0_valid = false;
   if (n == 0) return 0;
   const int64_t cap = (int64_t)std::min<size_t>((size_t)n * 64, b->cells());
   const size_t cs = b->csize();
@@ -164,6 +187,52 @@ static int ibm_couple(xlbhip_ibm* b, xlbhip_field* f) {
   return 0;
 }
 
+// ---- rigid bodies ---------------------------------------------------------------------------------------------------------------
+// the poses [body][18] the kernels of timestep t read: the rest poses while no body moves, else t's staged row (nullptr: not staged)
+static const double* ibm_pose_at(const xlbhip_ibm* b, int64_t t) {
+  if (!b->any_moving) return b->rest_pose.get<double>();
+  if (t < b->pose_first || t >= b->pose_first + b->pose_count) return nullptr;
+  return b->pose.get<double>() + (size_t)(t - b->pose_first) * b->n_bodies * IBM_POSE_DOUBLES;
+}
+
+static int ibm_require_poses(const xlbhip_ibm* b, int64_t t0, int64_t n) {
+  if (!b->any_moving) return 0;
+  for (int64_t k = 0; k < n; ++k)
+    XLB_REQUIRE(ibm_pose_at(b, t0 + k), "the poses of the bodies at timestep %lld are not staged (xlbhip_ibm_stage_poses)", (long long)(t0 + k));
+  return 0;
+}
+
+// the markers of the moving bodies to their place at timestep t, then the footprint of the new positions
+static int ibm_move(xlbhip_ibm* b, int64_t t) {
+  if (!b->any_moving) return 0;
+  hipLaunchKernelGGL(k_ibm_move, blocks_for((size_t)b->n), 256, 0, b->ctx->stream, b->pos0.get<float>(), b->move_id.get<int32_t>(), ibm_pose_at(b, t),
+                     b->centre0.get<double>(), b->n, b->pos.get<float>(), b->vel.get<float>());
+  XLB_HIP(hipGetLastError());
+  b->host_pos.clear();  // the device holds other positions than the caller passed last: the next ones are never "the same"
+  return ibm_build_footprint(b);
+}
+
+// force and torque on every body from the forces the coupling left, to `loads` and to the next row of a recorded history
+static int ibm_body_loads(xlbhip_ibm* b, int64_t t) {
+  if (b->n_bodies == 0) return 0;
+  hipStream_t st = b->ctx->stream;
+  const double* pose = ibm_pose_at(b, t);
+  double* row = nullptr;
+  if (b->hist_next < b->hist_rows) row = b->hist.get<double>() + (size_t)b->hist_next++ * b->n_bodies * 6;
+  return by_compute(b->cdt, [&](auto T) {
+    using TT = decltype(T);
+    if (b->n_chunks > 0) {
+      hipLaunchKernelGGL((k_ibm_loads<TT>), (unsigned)b->n_chunks, IBM_LOADS_CHUNK, 0, st, b->chunks.get<IbmLoadChunk>(), b->F.get<TT>(), b->area.get<float>(),
+                         b->pos.get<float>(), pose, b->partial.get<double>());
+      XLB_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_ibm_loads_combine, blocks_for((size_t)b->n_bodies * 6), 256, 0, st, b->chunk0.get<int32_t>(), b->partial.get<double>(), b->n_bodies,
+                       b->loads.get<double>(), row);
+    XLB_HIP(hipGetLastError());
+    return 0;
+  });
+}
+
 static int ibm_check_field(const xlbhip_ibm* b, const xlbhip_field* f) {
   XLB_REQUIRE(f, "null field");
   XLB_REQUIRE(f->halo == 0, "the immersed-boundary stepper does not run on slab-decomposed fields (ghost planes)");
@@ -208,6 +277,8 @@ int xlbhip_ibm_create(xlbhip_ctx* c, xlbhip_stepper* stepper, int lattice, int c
   XLB_HIP(hipMemsetAsync(b->ctl.get(), 0, sizeof(IbmControl), c->stream));
   XLB_HIP(hipEventCreateWithFlags(&b->pin_ev, hipEventDisableTiming));
   XLB_HIP(hipEventRecord(b->pin_ev, c->stream));
+  XLB_HIP(hipEventCreateWithFlags(&b->pose_ev, hipEventDisableTiming));
+  XLB_HIP(hipEventRecord(b->pose_ev, c->stream));
   *out = b.release();
   return 0;
 }
@@ -217,6 +288,7 @@ int xlbhip_ibm_destroy(xlbhip_ibm* b) {
   (void)hipSetDevice(b->ctx->device);
   (void)hipStreamSynchronize(b->ctx->stream);  // copies may still read the pinned buffer
   if (b->pin_ev) (void)hipEventDestroy(b->pin_ev);
+  if (b->pose_ev) (void)hipEventDestroy(b->pose_ev);
   delete b;
   return 0;
 }
@@ -227,6 +299,7 @@ int xlbhip_ibm_set_markers(xlbhip_ibm* b, int64_t n, const float* positions, con
   xlbhip_ctx* c = b->ctx;
   XLB_HIP(hipSetDevice(c->device));
   if (n != b->n) {
+    XLB_REQUIRE(b->n_bodies == 0, "the number of markers (%lld -> %lld) cannot change while bodies are declared: clear them first", (long long)b->n, (long long)n);
     XLB_REQUIRE(n == 0 || (positions && areas && velocities), "a new number of markers needs positions, areas and velocities");
     if (int rc = ibm_clear_footprint(b)) return rc;
     XLB_HIP(hipStreamSynchronize(c->stream));
@@ -238,11 +311,15 @@ int xlbhip_ibm_set_markers(xlbhip_ibm* b, int64_t n, const float* positions, con
   const size_t n3 = (size_t)n * 3 * sizeof(float);
   bool moved = false;
   if (positions) {
+    // (k_ibm_move empties host_pos: after the device has moved the markers, no array the caller passes counts as "the same")
     moved = b->host_pos.size() != (size_t)n * 3 || std::memcmp(b->host_pos.data(), positions, n3) != 0;
     if (moved) {
       b->host_pos.assign(positions, positions + (size_t)n * 3);
       std::memcpy(pin, positions, n3);
       XLB_HIP(hipMemcpyAsync(b->pos.get(), pin, n3, hipMemcpyHostToDevice, c->stream));
+      // they are the new reference positions of the bodies
+      if (b->any_moving) XLB_HIP(hipMemcpyAsync(b->pos0.get(), pin, n3, hipMemcpyHostToDevice, c->stream));
+      b->pos0_valid = b->any_moving;
     }
   }
   if (areas) {
@@ -263,13 +340,17 @@ int xlbhip_ibm_step(xlbhip_ibm* b, const xlbhip_field* f_src, xlbhip_field* f_ds
   XLB_REQUIRE(b, "null argument");
   if (int rc = ibm_check_field(b, f_src)) return rc;
   if (int rc = ibm_check_field(b, f_dst)) return rc;
+  if (int rc = ibm_require_poses(b, timestep, 1)) return rc;
+  if (int rc = ibm_move(b, timestep)) return rc;
   if (int rc = xlbhip_step(b->stepper, f_src, f_dst, bc_mask, missing_mask, omega, timestep)) return rc;
-  return ibm_couple(b, f_dst);
+  if (int rc = ibm_couple(b, f_dst)) return rc;
+  return ibm_body_loads(b, timestep);
 }
 
 int xlbhip_ibm_run(xlbhip_ibm* b, xlbhip_field* f_a, xlbhip_field* f_b, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, double omega,
                    int64_t first_timestep, int64_t n_steps, int* result_in_b) {
   XLB_REQUIRE(b && result_in_b && n_steps >= 0, "bad argument");
+  if (int rc = ibm_require_poses(b, first_timestep, n_steps)) return rc;  // (before anything is enqueued)
   xlbhip_field* cur = f_a;
   xlbhip_field* oth = f_b;
   for (int64_t i = 0; i < n_steps; ++i) {
@@ -317,6 +398,128 @@ int xlbhip_ibm_footprint(xlbhip_ibm* b, int64_t* n_cells, int64_t capacity, uint
     XLB_REQUIRE(capacity >= count, "xlbhip_ibm_footprint: room for %lld cells, the footprint has %d", (long long)capacity, count);
     XLB_HIP(hipMemcpy(cells, b->list.get(), (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost));
   }
+  return 0;
+}
+
+int xlbhip_ibm_set_bodies(xlbhip_ibm* b, int n_bodies, const int64_t* first, const int64_t* count, const int* moving, const double* centre0) {
+  XLB_REQUIRE(b && n_bodies >= 0, "bad argument");
+  XLB_REQUIRE(n_bodies <= IBM_MAX_BODIES, "%d bodies, at most %d are supported", n_bodies, IBM_MAX_BODIES);
+  XLB_REQUIRE(n_bodies == 0 || (first && count && moving && centre0), "null argument");
+  for (int i = 0; i < n_bodies; ++i) {
+    XLB_REQUIRE(first[i] >= 0 && count[i] >= 0 && first[i] + count[i] <= b->n, "body %d: markers %lld .. %lld are out of bounds (%lld markers)", i,
+                (long long)first[i], (long long)(first[i] + count[i]), (long long)b->n);
+    for (int j = 0; j < i; ++j)
+      XLB_REQUIRE(first[i] >= first[j] + count[j] || first[j] >= first[i] + count[i], "bodies %d and %d overlap", j, i);
+  }
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipStreamSynchronize(c->stream));  // queued steps read the tables replaced below
+  b->n_bodies = 0;
+  b->any_moving = false;
+  b->n_chunks = b->pose_count = 0;
+  b->hist_rows = b->hist_next = 0;
+  if (n_bodies == 0) return 0;
+  std::vector<int32_t> move_id((size_t)b->n, -1), chunk0((size_t)n_bodies + 1, 0);
+  std::vector<IbmLoadChunk> chunks;
+  std::vector<double> rest((size_t)n_bodies * IBM_POSE_DOUBLES, 0.0);
+  bool any_moving = false;
+  for (int i = 0; i < n_bodies; ++i) {
+    if (moving[i]) {
+      any_moving = any_moving || count[i] > 0;
+      std::fill(move_id.begin() + first[i], move_id.begin() + first[i] + count[i], (int32_t)i);
+    }
+    chunk0[i] = (int32_t)chunks.size();
+    for (int64_t o = 0; o < count[i]; o += IBM_LOADS_CHUNK)
+      chunks.push_back(IbmLoadChunk{(int32_t)i, (int32_t)(first[i] + o), (int32_t)std::min<int64_t>(IBM_LOADS_CHUNK, count[i] - o)});
+    double* P = rest.data() + (size_t)i * IBM_POSE_DOUBLES;
+    P[0] = P[4] = P[8] = 1.0;
+    for (int a = 0; a < 3; ++a) P[9 + a] = centre0[3 * i + a];
+  }
+  chunk0[n_bodies] = (int32_t)chunks.size();
+  if (int rc = upload_bytes(move_id.data(), move_id.size() * sizeof(int32_t), b->move_id)) return rc;
+  if (int rc = upload_bytes(chunk0.data(), chunk0.size() * sizeof(int32_t), b->chunk0)) return rc;
+  if (int rc = upload_bytes(chunks.data(), chunks.size() * sizeof(IbmLoadChunk), b->chunks)) return rc;
+  if (int rc = upload_bytes(centre0, (size_t)n_bodies * 3 * sizeof(double), b->centre0)) return rc;
+  if (int rc = upload_bytes(rest.data(), rest.size() * sizeof(double), b->rest_pose)) return rc;
+  XLB_HIP(b->partial.alloc(std::max<size_t>(chunks.size(), 1) * 6 * sizeof(double)));
+  XLB_HIP(b->loads.alloc((size_t)n_bodies * 6 * sizeof(double)));
+  XLB_HIP(hipMemsetAsync(b->loads.get(), 0, (size_t)n_bodies * 6 * sizeof(double), c->stream));
+  if (any_moving) {
+    if (!b->pose) XLB_HIP(b->pose.alloc(XLBHIP_IBM_POSE_BYTES));
+    if (!b->pose_pin) XLB_HIP(b->pose_pin.alloc(XLBHIP_IBM_POSE_BYTES));
+    if (!b->pos0_valid) {  // nothing has moved the markers since they were uploaded: `pos` holds the reference positions
+      XLB_HIP(b->pos0.alloc((size_t)b->n * 3 * sizeof(float)));
+      XLB_HIP(hipMemcpyAsync(b->pos0.get(), b->pos.get(), (size_t)b->n * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+      b->pos0_valid = true;
+    }
+  }
+  b->n_bodies = n_bodies;
+  b->any_moving = any_moving;
+  b->n_chunks = (int64_t)chunks.size();
+  return 0;
+}
+
+int xlbhip_ibm_stage_poses(xlbhip_ibm* b, int64_t first_timestep, int64_t n_steps, const double* poses) {
+  XLB_REQUIRE(b && n_steps >= 0 && (n_steps == 0 || poses), "bad argument");
+  XLB_REQUIRE(b->any_moving, "xlbhip_ibm_stage_poses: no body moves (xlbhip_ibm_set_bodies)");
+  const size_t bytes = (size_t)n_steps * b->n_bodies * IBM_POSE_DOUBLES * sizeof(double);
+  XLB_REQUIRE(bytes <= XLBHIP_IBM_POSE_BYTES, "%lld steps x %d bodies of poses are %zu bytes, at most %d are staged at once", (long long)n_steps, b->n_bodies,
+              bytes, XLBHIP_IBM_POSE_BYTES);
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  b->pose_count = 0;
+  if (n_steps == 0) return 0;
+  XLB_HIP(hipEventSynchronize(b->pose_ev));  // the previous copy out of the pinned buffer (not the kernels)
+  std::memcpy(b->pose_pin.get(), poses, bytes);
+  // (in stream order behind the steps that read the rows staged before)
+  XLB_HIP(hipMemcpyAsync(b->pose.get(), b->pose_pin.get(), bytes, hipMemcpyHostToDevice, c->stream));
+  XLB_HIP(hipEventRecord(b->pose_ev, c->stream));
+  b->pose_first = first_timestep;
+  b->pose_count = n_steps;
+  return 0;
+}
+
+int xlbhip_ibm_loads(xlbhip_ibm* b, int n_bodies, double* loads) {
+  XLB_REQUIRE(b && n_bodies == b->n_bodies && (n_bodies == 0 || loads), "xlbhip_ibm_loads: expected room for %d bodies", b ? b->n_bodies : 0);
+  if (n_bodies == 0) return 0;
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipMemcpyAsync(loads, b->loads.get(), (size_t)n_bodies * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  XLB_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int xlbhip_ibm_record_loads(xlbhip_ibm* b, int64_t n_rows) {
+  XLB_REQUIRE(b && n_rows >= 0, "bad argument");
+  XLB_REQUIRE(n_rows == 0 || b->n_bodies > 0, "xlbhip_ibm_record_loads: no bodies are declared");
+  XLB_HIP(hipSetDevice(b->ctx->device));
+  b->hist_rows = b->hist_next = 0;
+  if (n_rows == 0) return 0;
+  XLB_HIP(b->hist.alloc((size_t)n_rows * b->n_bodies * 6 * sizeof(double)));
+  b->hist_rows = n_rows;
+  return 0;
+}
+
+int xlbhip_ibm_loads_history(xlbhip_ibm* b, int64_t n_rows, double* loads) {
+  XLB_REQUIRE(b && n_rows >= 0 && (n_rows == 0 || loads), "bad argument");
+  XLB_REQUIRE(n_rows <= b->hist_next, "xlbhip_ibm_loads_history: %lld rows asked for, %lld were recorded", (long long)n_rows, (long long)b->hist_next);
+  if (n_rows == 0) return 0;
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipMemcpyAsync(loads, b->hist.get(), (size_t)n_rows * b->n_bodies * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  XLB_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int xlbhip_ibm_download_markers(xlbhip_ibm* b, int64_t n, float* positions, float* velocities) {
+  XLB_REQUIRE(b && n == b->n, "xlbhip_ibm_download_markers: expected room for %lld markers", b ? (long long)b->n : 0LL);
+  if (n == 0) return 0;
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  const size_t n3 = (size_t)n * 3 * sizeof(float);
+  if (positions) XLB_HIP(hipMemcpyAsync(positions, b->pos.get(), n3, hipMemcpyDeviceToHost, c->stream));
+  if (velocities) XLB_HIP(hipMemcpyAsync(velocities, b->vel.get(), n3, hipMemcpyDeviceToHost, c->stream));
+  XLB_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
 

@@ -1,7 +1,11 @@
 """Set-up helpers of the immersed-boundary stepper (reference xlb/helper/ibm_helper.py:11-24 and :118-205).
 
 Mesh subdivision (the reference's ``prepare_immersed_boundary`` goes through trimesh) is not part of this backend: bring markers
-that are about one cell apart."""
+that are about one cell apart.
+
+``RigidMotion`` and ``IBMBody`` describe bodies with prescribed motion for ``IBMStepper.set_bodies`` (the reference's
+examples/ibm/wind_turbine_ibm.py:160-199 turns its rotor with a kernel of its own; here the host evaluates poses and the stepper's
+native code applies them)."""
 
 import numpy as np
 
@@ -61,3 +65,49 @@ def icosphere(subdivisions=2):
             out += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
         faces = out
     return np.array(verts), np.array(faces, dtype=np.int64)
+
+
+class RigidMotion:
+    """Constant rotation about ``axis`` through ``centre`` by ``rate`` radians per step, plus a constant translation of the centre by
+    ``velocity`` per step; ``phase`` is the angle at timestep 0.
+
+    ``at(timestep)`` -> ``(R (3, 3), c (3,), w (3,), v (3,))`` in float64: the rotation by the TOTAL angle phase + rate * timestep
+    (Rodrigues' formula on that one angle, never a product of per-step rotations, so it cannot drift), the centre
+    centre + velocity * timestep, the angular velocity rate * axis / |axis| and the velocity of the centre.  Any object with such an
+    ``at`` is a motion as far as ``IBMStepper`` is concerned (an oscillating cylinder, a pitching foil, a spin-up ramp, ...)."""
+
+    def __init__(self, centre, axis, rate, velocity=(0.0, 0.0, 0.0), phase=0.0):
+        self.centre = np.array(centre, dtype=np.float64).reshape(3)
+        axis = np.array(axis, dtype=np.float64).reshape(3)
+        norm = float(np.sqrt((axis * axis).sum()))
+        if not norm > 0.0:
+            raise ValueError("RigidMotion: the axis must not be zero")
+        self.axis = axis / norm
+        self.rate = float(rate)
+        self.velocity = np.array(velocity, dtype=np.float64).reshape(3)
+        self.phase = float(phase)
+
+    def at(self, timestep):
+        angle = self.phase + self.rate * float(timestep)
+        x, y, z = self.axis
+        K = np.array([[0.0, -z, y], [z, 0.0, -x], [-y, x, 0.0]])
+        R = np.eye(3) + np.sin(angle) * K + (1.0 - np.cos(angle)) * (K @ K)
+        return R, self.centre + self.velocity * float(timestep), self.rate * self.axis, self.velocity.copy()
+
+
+class IBMBody:
+    """A contiguous range of an IBMStepper's markers that moves as one rigid body.
+
+    ``markers``  slice(a, b) into the marker arrays (step 1)
+    ``motion``   a RigidMotion, any object with its ``at(timestep)``, or None for a body at rest (whose loads are still summed)
+    ``centre0``  the point the uploaded vertices refer to: marker k sits at c(t) + R(t) (X0_k - centre0).  Default: motion.at(0)[1],
+                 or the mean of the body's markers for a body at rest (there it is the point the torque is taken about)."""
+
+    def __init__(self, markers, motion=None, centre0=None):
+        if not isinstance(markers, slice):
+            raise TypeError("IBMBody: markers must be a slice of the marker arrays")
+        if motion is not None and not callable(getattr(motion, "at", None)):
+            raise TypeError("IBMBody: motion must be None or have an at(timestep) method")
+        self.markers = markers
+        self.motion = motion
+        self.centre0 = None if centre0 is None else np.array(centre0, dtype=np.float64).reshape(3)

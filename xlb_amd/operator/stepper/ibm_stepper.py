@@ -22,11 +22,28 @@ the coupling kernels of csrc/ibm_kernels.hpp on the cells within two cells of a 
 early exit of the sweep loop is taken by the kernels themselves, ``lag_forces`` is read when somebody asks for its values
 (``lag_forces.numpy()``: the forces of the LAST call) and so is ``stepper.ibm_iterations_used``.
 
+Bodies that move.  A rigid body with PRESCRIBED motion is declared once and moved on the device (the reference's
+examples/ibm/wind_turbine_ibm.py:160-199 does the same with a kernel of its own, ``rotate_rotor``):
+
+    stepper.set_bodies([IBMBody(markers=slice(0, 600), motion=RigidMotion(centre, axis, rate)), IBMBody(markers=slice(600, 900))])
+    f_0, f_1, history = stepper.run(f_0, f_1, bc_mask, missing_mask, omega, n, record_loads=True)    # (n, n_bodies, 6)
+
+The call with timestep t places marker k of body b at X_k(t) = c_b(t) + R_b(t) (X0_k - c0_b) with velocity
+U_k(t) = v_b(t) + w_b(t) x (X_k(t) - c_b(t)), where X0 are the vertices last uploaded (``markers.update(vertices=...)`` replaces
+them), c0_b is the body's ``centre0`` and (R, c, w, v) = ``motion.at(t)``.  The ``velocities`` uploaded for the markers of a moving
+body are IGNORED.  A body with ``motion=None`` is at rest; markers in no body stay as uploaded.  ``body_loads()`` is the force and
+the torque on every body in the last call.  Free (force-driven) rigid-body dynamics are out of scope: the motion is prescribed.
+
+The host evaluates the poses (18 doubles per step and body) and stages them ahead of the steps, as it does for time-dependent
+walls: ``run`` works in chunks of at most POSE_CHUNK_STEPS = 256 steps and at most 1 MiB of poses (113 steps with 64 bodies); the
+poses of the next chunk are evaluated while the device runs the current one, and nothing inside a chunk waits for the device.
+
 3-D lattices, fp32 / fp64 storage, one rank."""
 
 import numpy as np
 
 from ... import _lib
+from ...helper.ibm_helper import IBMBody, RigidMotion  # noqa: F401  (re-exported: they are this stepper's vocabulary)
 from ...compute_backend import ComputeBackend
 from ...precision_policy import Precision
 from ..operator import Operator
@@ -43,11 +60,20 @@ class IBMMarkers:
         return self._stepper._ibm_native().n
 
     def update(self, vertices=None, areas=None, velocities=None):
-        """Replace any of the three arrays (same number of markers), or all three with a new number of markers."""
+        """Replace any of the three arrays (same number of markers), or all three with a new number of markers (not while bodies are
+        declared).  ``vertices`` are the reference positions of the bodies that move; their ``velocities`` are ignored."""
         given = [a for a in (vertices, areas, velocities) if a is not None]
         n = len(given[0]) if given else len(self)
         self._stepper._ibm_native().set_markers(n, vertices, areas, velocities)
         return self
+
+    def positions(self):
+        """The positions the device holds now — after the last call's move — as (n, 3) float32.  Synchronous."""
+        return self._stepper._ibm_native().download_markers(velocities=False)[0]
+
+    def velocities(self):
+        """The velocities the device holds now, (n, 3) float32.  Synchronous."""
+        return self._stepper._ibm_native().download_markers(positions=False)[1]
 
 
 class LagrangianForces:
@@ -85,6 +111,8 @@ class IBMStepper(IncompressibleNavierStokesStepper):
         if self.ibm_tolerance < 0:
             raise ValueError("ibm_tolerance must not be negative")
         self._ibm = None
+        self._bodies = []
+        self._any_moving = False
         self._markers = IBMMarkers(self)
         self.s_lagr_forces = LagrangianForces(self)
 
@@ -107,25 +135,115 @@ class IBMStepper(IncompressibleNavierStokesStepper):
             return
         self._markers.update(vertices, areas, velocities)
 
+    # -- rigid bodies -----------------------------------------------------------------------------------------------
+    MAX_BODIES = 64
+    POSE_CHUNK_STEPS = 256  # steps whose poses run() evaluates and stages at once, further capped by _lib.IBM.POSE_BYTES
+
+    def set_bodies(self, bodies):
+        """Declare the rigid bodies: a list of IBMBody over disjoint contiguous ranges of the markers uploaded before (``[]``: none,
+        today's plain stepper; markers a device has moved stay where they are).  Raises ValueError naming the body for a range that
+        is out of bounds or overlaps another, and for more than 64 bodies."""
+        bodies = list(bodies)
+        if len(bodies) > self.MAX_BODIES:
+            raise ValueError(f"set_bodies: {len(bodies)} bodies, at most {self.MAX_BODIES} are supported")
+        ibm = self._ibm_native()
+        n = ibm.n
+        ranges = []
+        for i, body in enumerate(bodies):
+            if not isinstance(body, IBMBody):
+                raise TypeError(f"set_bodies: body {i} is not an IBMBody")
+            sl = body.markers
+            a, b = (0 if sl.start is None else sl.start), (n if sl.stop is None else sl.stop)
+            if sl.step not in (None, 1):
+                raise ValueError(f"set_bodies: body {i}: the markers must be a contiguous range (slice step {sl.step})")
+            if not 0 <= a <= b <= n:
+                raise ValueError(f"set_bodies: body {i}: markers {a}:{b} are out of bounds for {n} markers")
+            for j, (c, d) in enumerate(ranges):
+                if a < d and c < b:
+                    raise ValueError(f"set_bodies: bodies {j} and {i} overlap (markers {c}:{d} and {a}:{b})")
+            ranges.append((a, b))
+        centre0 = np.zeros((len(bodies), 3))
+        uploaded = None
+        for i, (body, (a, b)) in enumerate(zip(bodies, ranges)):
+            if body.centre0 is not None:
+                centre0[i] = body.centre0
+            elif body.motion is not None:
+                centre0[i] = np.asarray(body.motion.at(0)[1], dtype=np.float64)
+            elif b > a:
+                uploaded = self._markers.positions() if uploaded is None else uploaded
+                centre0[i] = uploaded[a:b].astype(np.float64).mean(axis=0)
+        ibm.set_bodies([a for a, _ in ranges], [b - a for a, b in ranges], [body.motion is not None for body in bodies], centre0)
+        self._bodies = bodies
+        self._body_centre0 = centre0
+        self._any_moving = any(body.motion is not None and b > a for body, (a, b) in zip(bodies, ranges))
+
+    def _poses(self, t_first, n):
+        """(n, n_bodies, 18) float64: R (row-major) | c | w | v of every body at t_first .. t_first + n - 1."""
+        out = np.zeros((n, len(self._bodies), 18))
+        for i, body in enumerate(self._bodies):
+            if body.motion is None:
+                out[:, i, 0] = out[:, i, 4] = out[:, i, 8] = 1.0
+                out[:, i, 9:12] = self._body_centre0[i]
+                continue
+            for k in range(n):
+                R, c, w, v = body.motion.at(int(t_first) + k)
+                row = out[k, i]
+                row[0:9] = np.asarray(R, dtype=np.float64).reshape(9)
+                row[9:12], row[12:15], row[15:18] = c, w, v
+        return out
+
+    def _pose_chunk(self):
+        return max(1, min(self.POSE_CHUNK_STEPS, _lib.IBM.POSE_BYTES // (18 * 8 * len(self._bodies))))
+
+    def body_loads(self):
+        """(n_bodies, 6) float64 of the LAST call, read from the device now: columns 0-2 the force on the body, -sum_k A_k F_k,
+        columns 3-5 the torque on it about the body's centre c_b at that step, -sum_k A_k (X_k - c_b) x F_k."""
+        return self._ibm_native().loads()
+
     @Operator.register_backend(ComputeBackend.HIP)
     def hip_implementation(self, f_0, f_1, vertices, areas, velocities, bc_mask, missing_mask, omega, timestep):
         self._set_markers(vertices, areas, velocities)
         self._stage(timestep, 1)
+        if self._any_moving:
+            self._ibm_native().stage_poses(timestep, self._poses(timestep, 1))
         self._ibm_native().step(f_0, f_1, bc_mask, missing_mask, omega, timestep)
         return f_0, f_1, self.s_lagr_forces
 
-    def run(self, f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep=0):
-        """``n_steps`` x (step with the coupling, swap) in native code with the markers as they are; returns (f_current, f_other)."""
+    def run(self, f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep=0, record_loads=False):
+        """``n_steps`` x (move the bodies, step with the coupling, loads, swap) in native code; returns (f_current, f_other), and with
+        ``record_loads`` also the loads of every step, (n_steps, n_bodies, 6), written on the device and read once after the run."""
         ibm = self._ibm_native()
+        n_steps, first_timestep = int(n_steps), int(first_timestep)
+        record = bool(record_loads) and len(self._bodies) > 0 and n_steps > 0
+        if record:
+            ibm.record_loads(n_steps)
+        cur, oth = f_0, f_1
         if self._time_dependent_bcs():
-            cur, oth = f_0, f_1
-            for k in range(int(n_steps)):
+            for k in range(n_steps):
                 self._stage(first_timestep + k, 1)
+                if self._any_moving:
+                    ibm.stage_poses(first_timestep + k, self._poses(first_timestep + k, 1))
                 ibm.step(cur, oth, bc_mask, missing_mask, omega, first_timestep + k)
                 cur, oth = oth, cur
+        elif self._any_moving:
+            chunk, done = self._pose_chunk(), 0
+            poses = self._poses(first_timestep, min(chunk, n_steps))
+            while done < n_steps:
+                m = len(poses)
+                ibm.stage_poses(first_timestep + done, poses)
+                if ibm.run(cur, oth, bc_mask, missing_mask, omega, first_timestep + done, m):
+                    cur, oth = oth, cur
+                done += m
+                if done < n_steps:  # (the device is busy with the chunk just enqueued)
+                    poses = self._poses(first_timestep + done, min(chunk, n_steps - done))
+        elif ibm.run(f_0, f_1, bc_mask, missing_mask, omega, first_timestep, n_steps):
+            cur, oth = f_1, f_0
+        if not record_loads:
             return cur, oth
-        in_b = ibm.run(f_0, f_1, bc_mask, missing_mask, omega, first_timestep, n_steps)
-        return (f_1, f_0) if in_b else (f_0, f_1)
+        history = ibm.loads_history(n_steps) if record else np.zeros((n_steps, len(self._bodies), 6))
+        if record:
+            ibm.record_loads(0)
+        return cur, oth, history
 
     def run_timed(self, f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep=0):
         """As :meth:`run`; also returns the wall-clock milliseconds between two synchronisations."""
