@@ -400,3 +400,52 @@ def test_two_step_kernel_with_do_nothing_outlet(steps):
         assert np.array_equal(a.numpy(), exp)
     finally:
         ctx.set_option("fuse2", 1)
+
+
+def test_end_plane_pairs_follow_the_mask_of_each_run():
+    """Whether a pair takes the end-plane path is decided per run from the masks it is given, not from whatever the stepper was asked
+    last: ONE stepper (Zou-He inlet and outlet, fuse2 = 2) runs with mask A (both BCs on the planes x = 0 and x = nx - 1: pairs, end
+    planes through the single-step kernel), then with mask B (the same BCs, some inlet cells also on the interior plane x = 5:
+    single steps), then with mask A again (5 steps: two pairs and a single step).  Every leg starts from the same populations and
+    ends with the bits of the same leg under fuse2 = 0.  (16, 8, 64) is the smallest domain the end-plane path takes."""
+    from xlb_amd.default_config import get_context
+
+    shape = (16, 8, 64)
+    vs, pp = init_hip("D3Q19")
+    lat = orc.Lattice("D3Q19")
+    grid = grid_factory(shape)
+    box_ne = grid.bounding_box_indices(remove_edges=True)
+    left, right = box_ne["left"], box_ne["right"]
+    # plane x = 5 on the face y = 0: not strictly interior, so the masker tags these cells like the others
+    left_b = [left[0] + [5] * 4, left[1] + [0] * 4, left[2] + [10, 11, 12, 13]]
+    b_in = ZouHeBC("velocity", prescribed_value=(0.03, 0.0, 0.0), indices=left)
+    b_out = ZouHeBC("pressure", prescribed_value=1.0, indices=right)
+    f_np = orc.perturbed_init(shape, lat, seed=57)
+    ctx = get_context()
+
+    def sequence(fuse2):
+        ctx.set_option("fuse2", fuse2)
+        b_in.indices, b_out.indices = left, right  # (the masker drops them once consumed)
+        stepper = IncompressibleNavierStokesStepper(grid=grid, boundary_conditions=[b_in, b_out])
+        f_0, f_1, bm_a, mm_a = stepper.prepare_fields()
+        _, _, _, mm_b, bm_b = create_nse_fields(shape)
+        b_in.indices, b_out.indices = left_b, right
+        bm_b, mm_b = IndicesBoundaryMasker(grid=grid)([b_in, b_out], bm_b, mm_b)
+        assert int((bm_b.numpy()[0, 5] == b_in.id).sum()) == 4 and not (bm_a.numpy()[0, 1:-1] == b_in.id).any()
+        native = stepper._native_stepper()
+        legs = []
+        for bm, mm, steps, pairs in ((bm_a, mm_a, 4, True), (bm_b, mm_b, 4, False), (bm_a, mm_a, 5, True)):
+            if fuse2 == 2 and len(legs) < 2:
+                assert bool(native.step2_eligible(f_0, f_1, bm, mm)) == pairs
+            f_0.assign(f_np)
+            f_0, f_1 = stepper.run(f_0, f_1, bm, mm, 1.3, steps)
+            legs.append(f_0.numpy().view(np.uint32))
+        return legs
+
+    try:
+        exp = sequence(0)
+        got = sequence(2)
+    finally:
+        ctx.set_option("fuse2", 1)
+    for k, (g, e) in enumerate(zip(got, exp)):
+        assert np.array_equal(g, e), f"leg {k}: {int((g != e).sum())} values differ from the single-step path"

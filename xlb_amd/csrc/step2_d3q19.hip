@@ -4,14 +4,14 @@
 namespace xlb {
 
 // f(t) in p.src -> f(t+2) in p.dst on (8 x 64) tiles (step2_plan.hpp: step2_tile)
-int launch_step2_d3q19_bgk(const StepLaunch& p) {
+int launch_step2_d3q19_bgk(const Step2Launch& p) {
   XLB_REQUIRE(p.tile_ty == 8 && p.tile_tz == 64, "two-step kernel: only the (8 x 64) tile is built");
   if (p.halo) return p.has_bc ? launch2<D3Q19, 1, 8, 64, true>(p) : launch2<D3Q19, 0, 8, 64, true>(p);
   return p.has_bc ? launch2<D3Q19, 1, 8, 64, false>(p) : launch2<D3Q19, 0, 8, 64, false>(p);
 }
 
 // per-block "no boundary cell in this work item" flags for the launch geometry of p (n = tiles x effective segments bytes)
-int step2_build_clean(const StepLaunch& p, uint8_t* out) {
+int step2_build_clean(const Step2Launch& p, uint8_t* out) {
   XLB_REQUIRE(p.meta && out && p.tile_ty == 8 && (p.tile_tz == 64 || (p.tile_tz == 48 && p.halo == 0)), "clean flags: (8 x 64) / (8 x 48) tiles with meta words only");
   const size_t ghost = (size_t)p.halo * p.ny * p.nz;
   const unsigned tiles = (unsigned)(p.ny / 8) * (unsigned)(p.nz / p.tile_tz);
@@ -28,7 +28,7 @@ int step2_build_clean(const StepLaunch& p, uint8_t* out) {
   XLB_HIP(hipGetLastError());
   return 0;
 }
-int step2_items(const StepLaunch& p) { return (p.ny / p.tile_ty) * (p.nz / p.tile_tz) * step2_eff_segments(p); }
+int step2_items(const Step2Launch& p) { return (p.ny / p.tile_ty) * (p.nz / p.tile_tz) * step2_eff_segments(p); }
 
 }  // namespace xlb
 

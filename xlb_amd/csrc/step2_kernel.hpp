@@ -190,8 +190,7 @@ __device__ __forceinline__ void step2_seg_range(int x_begin, int x_count, int n_
 
 // The body of the kernel for one block; the LDS arrays belong to the __global__ wrapper below (so that the wrapper can
 // run either boundary-condition form of the body in the same allocation).
-// STRIPS (D3Q19 / (TY x 64) tiles): bit 0 = phase A reads the halo columns of its grown tile from the source field's STRIP buffer,
-// bit 1 = phase B also writes the destination field's strips.  See "Strip buffers" below.
+// STRIPS (D3Q19 / (TY x 64) tiles): the strips mode, documented at the static_assert below.
 template <class L, class T, class S, int COLL, int HASBC, int TY, int TZ, bool SLAB, int GMAX, bool PIN, bool FAST, bool SLACK = false, int STRIPS = 0>
 __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsigned* ldsmeta, T* bcval, S* strip_stage = nullptr) {
   using G = S2Geom<L, HASBC, TY, TZ>;
@@ -200,6 +199,12 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
   constexpr int Q = L::Q, NE = G::NE, EZ = G::EZ;
   constexpr unsigned ES = sizeof(S);
   constexpr bool SR = (STRIPS & 1) != 0, SW = (STRIPS & 2) != 0;
+  // STRIPS takes the values of enum Strips (step_launch.hpp).  Bit 0 = phase A reads the halo columns of its grown tile from the
+  // source field's STRIP buffer, bit 1 = phase B also writes the destination field's strips (see "Strip buffers" below):
+  //   none = 0        no strip buffers
+  //   write = 2       phase B writes the destination's strips; the source has none that are valid
+  //   read_write = 3  phase A reads the source's, phase B writes the destination's
+  //   rowmap = 4      row-aligned lanes in both bodies of the BC kernel WITHOUT strip buffers ("fuse2_rowmap", a measurement option)
   static_assert(STRIPS == 0 || STRIPS == 2 || STRIPS == 3 || STRIPS == 4, "STRIPS: 0, 2 (write), 3 (read + write) or 4 (row-aligned lanes only)");
   static_assert(STRIPS == 0 || (TZ == 64 && sizeof(S) == 4), "strip buffers: (TY x 64) tiles, 4-byte store type");
   // f(t+1) lives in LDS in the STORE type: the single-step kernel rounds it to that type on its way through memory, so the
@@ -258,7 +263,7 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
   // piece per pull instead of the tail of one row + the head of the next), the last wave the two halo columns of all rows
   // Row-aligned lanes are the mapping of the stand-alone BC-free kernel (two barriers per plane): periodic 512^3 2.28 -> 2.11-2.16
   // ms/step in round 3's A/B (round 2 measured -2...3 %); the bodies of the BC kernel lose 0-3 % with it and keep the dense mapping.
-  // (STRIPS & 4: row-aligned lanes for this body WITHOUT strip buffers — the run-time A/B of stepper.hip's "fuse2_rowmap" option)
+  // (STRIPS & 4: Strips::rowmap, above)
   constexpr bool ROWMAP = (SR || (STRIPS & 4) != 0 || (HASBC == 0 && !SLACK)) && TZ == 64;
   // strip buffers: the last wave holds the 2 x EY halo-column cells of the grown tile (ROWMAP) and pulls for them from the
   // strips — the same instructions as every other wave, with the strip buffer's geometry in place of the field's

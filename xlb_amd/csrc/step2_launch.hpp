@@ -6,28 +6,28 @@
 namespace xlb {
 
 // effective launch geometry (shared by the kernel launch and the clean-flag pass: both must map blocks alike)
-inline int step2_eff_segments(const StepLaunch& p) { return (p.x_segments > 1 && p.x_count >= 8 * p.x_segments) ? p.x_segments : 1; }
+inline int step2_eff_segments(const Step2Launch& p) { return (p.x_segments > 1 && p.x_count >= 8 * p.x_segments) ? p.x_segments : 1; }
 // thin end segments need >= 3 segments and inner segments of at least 8 planes
-inline int step2_eff_cap(const StepLaunch& p) {
+inline int step2_eff_cap(const Step2Launch& p) {
   const int n = step2_eff_segments(p);
   return (p.x_cap > 0 && n >= 3 && p.x_count - 2 * p.x_cap >= 8 * (n - 2)) ? p.x_cap : 0;
 }
-inline int step2_eff_swizzle(const StepLaunch& p, unsigned tiles) { return (p.xcd_swizzle && tiles % 8u == 0u) ? 1 : 0; }
+inline int step2_eff_swizzle(const Step2Launch& p, unsigned tiles) { return (p.xcd_swizzle && tiles % 8u == 0u) ? 1 : 0; }
 
 template <class L, int HASBC, int TY, int TZ, bool SLAB, bool FAST, class T = float, int COLL = XLBHIP_BGK, int STRIPS = 0>
-static int launch2f(const StepLaunch& p);
+static int launch2f(const Step2Launch& p);
 
 // fast_bgk = 1 (opt-in): the tolerance-graded fast BGK body (cell.hpp: bgk_fast).  Measured: 20 % fewer VALU instructions buy
 // 2-4 % (profiles/r02/step2_sweeps.txt) — the kernel is bound by its real memory traffic, not by VALU issue — so the
 // bit-exact body stays the default.
 template <class L, int HASBC, int TY, int TZ, bool SLAB>
-static int launch2(const StepLaunch& p) {
+static int launch2(const Step2Launch& p) {
   return p.fast_bgk ? launch2f<L, HASBC, TY, TZ, SLAB, true>(p) : launch2f<L, HASBC, TY, TZ, SLAB, false>(p);
 }
 
 // T / COLL: compute type and collision (cell.hpp collide<>) of the instantiation; the store type is always fp32
 template <class L, int HASBC, int TY, int TZ, bool SLAB, bool FAST, class T, int COLL, int STRIPS>
-static int launch2f(const StepLaunch& p) {
+static int launch2f(const Step2Launch& p) {
   static_assert(HASBC == 0 || (sizeof(T) == 4 && COLL == XLBHIP_BGK), "boundary-condition tables of the two-step kernel are fp32 / BGK");
   StepArgs<T, float> a;
   // SLAB: pointers advanced to interior plane 0 (the kernel addresses the ghost planes with negative indices)

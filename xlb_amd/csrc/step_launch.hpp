@@ -11,16 +11,6 @@ struct StepLaunch {
   void* dst;
   const uint8_t* bc;
   const uint32_t* miss;
-  const uint32_t* meta;  // two-step kernel only
-  const uint32_t* tile_order;  // two-step kernel only
-  const uint8_t* clean;        // two-step kernel only: per-block "no boundary cells" flags for THIS launch geometry, or nullptr
-  const void* strips_src;      // two-step kernel only: strip buffers of the source / destination field (storage plane 0), or nullptr
-  void* strips_dst;
-  int strips;                  // two-step kernel only: 0 = none, 3 = phase A reads + phase B writes them, 2 = phase B writes them only
-  int x_segments;              // two-step kernel only
-  int x_cap;                   // two-step kernel only: thin first / last segment (planes), 0 = uniform cuts
-  int tile_oy, tile_oz;        // two-step kernel only: periodic origin shift of the tiling (0 .. tile - 1)
-  int tile_ty, tile_tz;        // two-step kernel only: tile of the (y, z) plane a block owns
   const uint8_t* tab_kind;
   const void* tab_values;  // compute dtype [256][27]
   const uint32_t* prof_keys;  // profile table of Zou-He / Regularized BCs (sorted storage cell indices), or nullptr
@@ -41,14 +31,30 @@ struct StepLaunch {
   int compute_dtype, store_dtype;
   int vec;     // requested cells per thread (1, 2, 4); must divide nz
   int has_bc;  // 0: no BCs; 1: basic kinds; 2: + Zou-He / Regularized
-  int edge_ext;  // has_bc == 2 but every extended-kind cell sits in plane 0 or nx - 1 (two-step kernel: interior planes only)
   int flags;   // bit 0: non-temporal stores
   int block_threads;  // 0 = default (256)
   int block_tz;       // threads along z per block, 0 = as many as fit
   int xcd_swizzle;
-  int fast_bgk;   // two-step kernel only: 1 = tolerance-graded fast BGK body (opt-in)
   int fast_math;  // 1: tolerance-graded fast collision where one is built (fp64 KBC: cell.hpp kbc_fast); 0: bit-exact builds only
   hipStream_t stream;
+};
+
+// the strips mode of a two-step launch; the values are those of k_step2's STRIPS template parameter (documented there: step2_kernel.hpp)
+enum class Strips : int { none = 0, write = 2, read_write = 3, rowmap = 4 };
+
+// A launch of the two-steps-per-pass kernel: what a single step needs plus the two-step kernel's own geometry and tables
+struct Step2Launch : StepLaunch {
+  const uint32_t* meta = nullptr;        // id | missing << 8 per cell, or nullptr
+  const uint32_t* tile_order = nullptr;  // block -> tile, or nullptr
+  const uint8_t* clean = nullptr;        // per-block "no boundary cells" flags for THIS launch geometry, or nullptr
+  const void* strips_src = nullptr;      // strip buffers of the source / destination field (storage plane 0), or nullptr
+  void* strips_dst = nullptr;
+  Strips strips = Strips::none;
+  int x_segments = 1;
+  int x_cap = 0;                 // thin first / last segment (planes), 0 = uniform cuts
+  int tile_oy = 0, tile_oz = 0;  // periodic origin shift of the tiling (0 .. tile - 1)
+  int tile_ty = 0, tile_tz = 0;  // tile of the (y, z) plane a block owns
+  int fast_bgk = 0;              // 1 = tolerance-graded fast BGK body (opt-in)
 };
 
 // which (T, S, VEC) combinations exist: fp32 compute -> VEC in {1, 2, 4}; fp64 compute -> {1, 2}
@@ -73,12 +79,6 @@ int launch_typed(const StepLaunch& p) {
   a.dst = static_cast<S*>(p.dst);
   a.bc = p.bc;
   a.miss = p.miss;
-  a.meta = nullptr;
-  a.clean = nullptr;
-  a.tile_order = nullptr;
-  a.x_segments = 1;
-  a.x_cap = 0;
-  a.tile_oy = a.tile_oz = 0;
   a.bc_kind = p.tab_kind;
   a.bc_values = static_cast<const T*>(p.tab_values);
   a.prof_keys = p.prof_keys;
@@ -194,13 +194,12 @@ int launch_step_f64(const StepLaunch& p) {
 // defined one per translation unit (step_<lattice>_<collision>.hip)
 int launch_step_d3q27_kbc_fast64(const StepLaunch& p);
 // two steps per pass (step2_kernel.hpp): f(t) in src -> f(t+2) in dst
-int launch_step2_d3q19_bgk(const StepLaunch& p);
-int launch_step2_d3q19_bgk_strips(const StepLaunch& p);  // p.strips != 0 (step2_d3q19_strips.hip)
-
-int launch_step2_d3q27_bgk(const StepLaunch& p);
-int launch_step2_d3q27_kbc(const StepLaunch& p);
-int step2_build_clean(const StepLaunch& p, uint8_t* out);
-int step2_items(const StepLaunch& p);
+int launch_step2_d3q19_bgk(const Step2Launch& p);
+int launch_step2_d3q19_bgk_strips(const Step2Launch& p);  // p.strips != Strips::none (step2_d3q19_strips.hip)
+int launch_step2_d3q27_bgk(const Step2Launch& p);
+int launch_step2_d3q27_kbc(const Step2Launch& p);
+int step2_build_clean(const Step2Launch& p, uint8_t* out);
+int step2_items(const Step2Launch& p);
 int launch_step_d2q9_ext(const StepLaunch& p, int coll);
 int launch_step_d3q19_ext(const StepLaunch& p, int coll);
 int launch_step_d3q27_ext(const StepLaunch& p, int coll);

@@ -1,15 +1,13 @@
 // libxlbhip: the stepper.  Its tables and caches, the launches of one step and of a fused pair of steps, the slab halo protocol,
-// the fuse decision (step2_plan.hpp), the per-timestep profile tables, and the stepper's C entry points.
-#include <algorithm>
+// the fuse decision (step2_plan.hpp), and the stepper's C entry points.  The profile tables have their own owner (profile_tables.hpp).
 #include <array>
-#include <cstring>
 #include <map>
 #include <memory>
 #include <vector>
 
 #include "api_internal.hpp"
 #include "comm.hpp"
-#include "prof_ring.hpp"
+#include "profile_tables.hpp"
 #include "step_launch.hpp"
 
 using namespace xlb;
@@ -29,69 +27,70 @@ struct MetaKey {
   bool operator==(const MetaKey& o) const { return bc == o.bc && miss == o.miss && external_halo == o.external_halo; }
 };
 
-// The stepper owns its device tables through DeviceBuf members: the destructor releases them, a rebuild re-allocates in place.
-// Its caches and when each is rebuilt or dropped:
-//   meta words      rebuilt when either mask's address or contents version, or the external_halo option, differs from meta_key,
-//                   or the cell count changed (prepare_fuse2)
-//   tile order      rebuilt when the tile counts (tys, tzs) of the (y, z) plane change (prepare_fuse2)
-//   clean flags     per launch geometry; all dropped whenever the meta words or the tile order are rebuilt
-//   edge-kind scan  redone when the bc mask's address or contents version differs from scan_key (can_fuse2)
-//   scratch field   re-created when the population fields' shape or dtype differs (can_fuse2)
-//   strip buffers   (the fields' own, common.hpp) valid iff strips_version == version && strips_oz == the launch's tile_oz
-//   profile ring    dropped whenever the profile table's layout changes (upload_prof_table)
-struct xlbhip_stepper {
-  xlbhip_ctx* ctx = nullptr;
-  int lattice = 0, collision = 0, cdt = 0, sdt = 0;
+// The boundary conditions of a stepper: their kinds and values by id, and what the kernels look up in their arguments
+struct BcTables {
   int n_bc = 0;
   bool needs_missing = false;
   bool extended_bcs = false;
-  bool has_outflow = false;  // ExtrapolationOutflowBC present: k_outflow_aux runs after every step
-  // two-step kernel with extended BCs on the x end planes only (inlet / outlet): the end planes go through the
-  // single-step kernel twice via this third population field
-  xlbhip_field* scratch = nullptr;
-  bool edge_ext_ok = false;
+  bool has_outflow = false;     // ExtrapolationOutflowBC present: k_outflow_aux runs after every step
   bool has_edge_kinds = false;  // kinds the two-step kernel does not evaluate itself: Zou-He family, outflow, do-nothing
-  // result of the last "are all such cells in the x end planes" scan, and the bc_mask it holds for
-  FieldKey scan_key;
-  int scan_flag = 1;
-  DeviceBuf tile_order;  // two-step kernel: uint32 block -> tile, hull tiles first (step2_tile_order)
-  int order_ty = 0, order_tz = 0;
-  DeviceBuf meta;  // two-step kernel: uint32 id | missing << 8 per cell
-  size_t meta_cells = 0;
-  // the masks the meta words were built from: xlbhip_step2 called per pair (the Python stepper pairing reference-style
-  // calls) must not rebuild them every time
-  MetaKey meta_key;
-  // two-step kernel: per launch geometry (x_begin, x_count, segments) the per-block "no boundary cell" flags
-  std::map<std::array<int, 3>, DeviceBuf> clean_cache;
-  bool forced = false;
-  double force[3] = {0, 0, 0};
-  double smag_cs = 0.17;
-  DeviceBuf tab_kind;  // uint8 [256]
+  DeviceBuf tab_kind;           // uint8 [256]
   unsigned long long ids_packed = 0;
   unsigned kinds_packed = 0;
   unsigned moving_mask = 0;  // slots (first 8 BCs) whose halfway wall has a non-zero moving-wall term
   DeviceBuf tab_values;      // [256][27] compute dtype
-  // per-cell prescribed values of Zou-He / Regularized BCs built with a profile: host map (storage cell -> 3 values)
-  // and its sorted device image
-  std::map<uint32_t, std::array<double, 3>> prof_host;
-  DeviceBuf prof_keys;  // uint32 [n_prof]
-  DeviceBuf prof_vals;  // compute dtype [n_prof][3]
-  int n_prof = 0;
-  // time-dependent wall velocities (HalfwayBounceBackBC / HybridBC with profile(cells, timestep)): their cells are entries of
-  // the same table, declared once (td_cells, in declaration order; td_pos = their rows in the sorted table).  Every timestep
-  // gets a full image of the table in one slot of a device ring (prof_ring.hpp keeps the books).  Images are staged through
-  // pinned host rows (one per slot, static entries written once), each guarded by the event of its last copy.  A stepper
-  // without time-dependent BCs has no ring and keeps its single table.
-  std::vector<uint32_t> td_cells;
-  std::vector<int> td_pos;
-  bool td_contiguous = false;        // td_pos[i] == td_pos[0] + i: the rows are one block of the table
-  std::array<uint8_t, 256> td_bc{};  // bc ids with time-dependent cells
-  std::vector<char> prof_image;      // host copy of the table (compute dtype): the static entries of every image
-  ProfRing ring_book;
-  DeviceBuf ring;      // [slots][n_prof][3] compute dtype
-  PinnedBuf ring_pin;  // same layout
-  std::vector<hipEvent_t> ring_ev;
-  std::vector<uint8_t> ring_pin_ready;  // pinned row holds the static entries
+};
+
+// What the two-step kernel needs beyond the fields, cached between pairs (rules: the comment block below)
+struct Step2Caches {
+  DeviceBuf tile_order;  // uint32 block -> tile, hull tiles first (step2_tile_order)
+  int order_ty = 0, order_tz = 0;
+  DeviceBuf meta;  // uint32 id | missing << 8 per cell
+  size_t meta_cells = 0;
+  // the masks the meta words were built from: xlbhip_step2 called per pair (the Python stepper pairing reference-style
+  // calls) must not rebuild them every time
+  MetaKey meta_key;
+  // per launch geometry (x_begin, x_count, segments) the per-block "no boundary cell" flags
+  std::map<std::array<int, 3>, DeviceBuf> clean_cache;
+  // result of the last "are all edge-kind cells in the x end planes" scan, and the bc_mask it holds for
+  FieldKey scan_key;
+  int scan_flag = 1;
+  // extended BCs on the x end planes only (inlet / outlet): the end planes go through the single-step kernel twice via this
+  // third population field
+  xlbhip_field* scratch = nullptr;
+
+  // (stream-ordered: the flags' last readers were enqueued before this point and hipFree synchronises)
+  void drop_clean() { clean_cache.clear(); }
+  // forget the meta words: the buffer (the transports may hold a registration of it), what it was built from, and the flags
+  // computed from it
+  void forget_meta(xlbhip_ctx* c) {
+    if (meta) comm_forget_buffer(c, meta.get());
+    (void)meta.reset();
+    meta_cells = 0;
+    meta_key = MetaKey();
+    drop_clean();
+  }
+};
+
+// The stepper owns its device tables through DeviceBuf members: the destructor releases them, a rebuild re-allocates in place.
+// Its caches and when each is rebuilt or dropped:
+//   meta words      rebuilt when either mask's address or contents version, or the external_halo option, differs from meta_key,
+//                   or the cell count changed (prepare_fuse2, Step2Caches::forget_meta)
+//   tile order      rebuilt when the tile counts (tys, tzs) of the (y, z) plane change (prepare_fuse2)
+//   clean flags     per launch geometry; all dropped whenever the meta words or the tile order are rebuilt (Step2Caches::drop_clean)
+//   edge-kind scan  redone when the bc mask's address or contents version differs from scan_key (can_fuse2)
+//   scratch field   re-created when the population fields' shape or dtype differs (can_fuse2)
+//   strip buffers   (the fields' own, common.hpp) valid iff strips_version == version && strips_oz == the launch's tile_oz
+//   profile ring    dropped whenever the profile table's layout changes (ProfileTables::rebuild)
+struct xlbhip_stepper {
+  xlbhip_ctx* ctx = nullptr;
+  int lattice = 0, collision = 0, cdt = 0, sdt = 0;
+  BcTables bc;
+  Step2Caches pairs;
+  ProfileTables prof;  // per-cell prescribed values and per-timestep wall velocities (profile_tables.hpp)
+  bool forced = false;
+  double force[3] = {0, 0, 0};
+  double smag_cs = 0.17;
   // wall-distance weights of HybridBC cells (mesh maskers): host map (storage cell -> q weights) and its sorted device image
   std::map<uint32_t, std::array<float, 27>> dist_host;
   DeviceBuf dist_keys;  // uint32 [n_dist]
@@ -123,100 +122,36 @@ static int check_step_fields(const xlbhip_stepper* s, const xlbhip_field* a, con
   XLB_REQUIRE(a->card == q && b->card == q, "population fields must have cardinality %d", q);
   XLB_REQUIRE(a->dtype == s->sdt && b->dtype == s->sdt, "population fields must have the stepper's store dtype %d", s->sdt);
   XLB_REQUIRE(same_grid(a, b) && a->halo == b->halo && a->plane_stride == b->plane_stride, "f_0 and f_1 layouts differ");
-  if (s->n_bc > 0) {
+  if (s->bc.n_bc > 0) {
     XLB_REQUIRE(bcm, "this stepper has boundary conditions: bc_mask is required");
   }
   if (bcm) {
     XLB_REQUIRE(bcm->dtype == XLBHIP_U8 && bcm->card == 1 && same_grid(bcm, a) && bcm->halo == a->halo, "bad bc_mask field");
   }
-  if (s->needs_missing) {
+  if (s->bc.needs_missing) {
     XLB_REQUIRE(miss && miss->dtype == XLBHIP_MISSING && same_grid(miss, a) && miss->halo == a->halo,
                 "halfway bounce-back needs a missing_mask field on the same grid");
   }
   return 0;
 }
 
-// ---- per-timestep profile tables (time-dependent wall velocities) ----
-static bool has_td(const xlbhip_stepper* s) { return !s->td_cells.empty(); }
-static size_t prof_image_bytes(const xlbhip_stepper* s) { return (size_t)s->n_prof * 3 * (s->cdt == XLBHIP_F32 ? 4 : 8); }
-
-// the profile table the launches of timestep t read: the single table, or t's slot of the ring (nullptr: t is not staged)
-static const void* prof_table_at(const xlbhip_stepper* s, int64_t t) {
-  if (!has_td(s)) return s->prof_vals.get();
-  const int k = s->ring_book.find(t);
-  return k < 0 ? nullptr : s->ring.get<char>() + (size_t)k * prof_image_bytes(s);
-}
-
-// the tables of the timesteps t0 .. t0 + n - 1 are all resident: checked before anything of a call is enqueued
-static int require_staged(const xlbhip_stepper* s, int64_t t0, int64_t n) {
-  if (!has_td(s)) return 0;
-  for (int64_t k = 0; k < n; ++k)
-    XLB_REQUIRE(prof_table_at(s, t0 + k), "the time-dependent wall velocities of timestep %lld are not staged (xlbhip_stepper_stage_bc_profiles)",
-                (long long)(t0 + k));
-  return 0;
-}
-
-// (the stream must be drained: copies may still read the pinned rows)
-static void free_ring(xlbhip_stepper* s) {
-  for (hipEvent_t e : s->ring_ev) (void)hipEventDestroy(e);
-  (void)s->ring.reset();
-  (void)s->ring_pin.reset();
-  s->ring_ev.clear();
-  s->ring_pin_ready.clear();
-  s->ring_book.reset(0);
-}
-
-static int ensure_ring(xlbhip_stepper* s) {
-  if (s->ring) return 0;
-  const int slots = prof_ring_slot_count(prof_image_bytes(s));
-  const size_t bytes = (size_t)slots * prof_image_bytes(s);
-  XLB_HIP(s->ring.alloc(bytes));
-  if (hipError_t e = s->ring_pin.alloc(bytes); e != hipSuccess) {
-    free_ring(s);
-    XLB_FAIL("hipHostMalloc(%zu bytes) for the profile ring failed: %s", bytes, hipGetErrorString(e));
-  }
-  s->ring_book.reset(slots);
-  s->ring_ev.assign((size_t)slots, nullptr);
-  s->ring_pin_ready.assign((size_t)slots, 0);
-  for (int k = 0; k < slots; ++k) {
-    if (hipError_t e = hipEventCreateWithFlags(&s->ring_ev[k], hipEventDisableTiming); e != hipSuccess) {
-      s->ring_ev.resize((size_t)k);
-      free_ring(s);
-      XLB_FAIL("hipEventCreate: %s", hipGetErrorString(e));
-    }
-    XLB_HIP(hipEventRecord(s->ring_ev[k], s->ctx->stream));  // (every row starts out "copied")
-  }
-  return 0;
-}
-
+// what a single step src -> dst at timestep t needs (a pair adds its own: make_launch2)
 static StepLaunch make_launch(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
                               double omega, int64_t t) {
   xlbhip_ctx* c = s->ctx;
   StepLaunch p;
   p.src = src->data;
   p.dst = dst->data;
-  p.bc = (s->n_bc > 0 && bcm) ? static_cast<const uint8_t*>(bcm->data) : nullptr;
+  p.bc = (s->bc.n_bc > 0 && bcm) ? static_cast<const uint8_t*>(bcm->data) : nullptr;
   p.miss = miss ? static_cast<const uint32_t*>(miss->data) : nullptr;
-  p.meta = nullptr;
-  p.clean = nullptr;
-  p.strips_src = nullptr;
-  p.strips_dst = nullptr;
-  p.strips = 0;
-  p.tile_order = nullptr;
-  p.x_segments = 1;
-  p.x_cap = 0;
-  p.tile_oy = p.tile_oz = 0;
-  const Step2Tile tile = step2_tile(s->lattice, s->collision, p.bc != nullptr);
-  p.tile_ty = tile.ty;
-  p.tile_tz = tile.tz;
-  p.tab_kind = s->tab_kind.get<uint8_t>();
-  p.ids_packed = s->ids_packed;
-  p.kinds_packed = s->kinds_packed;
-  p.n_bc = s->n_bc;
-  p.tab_values = s->tab_values.get();
-  p.prof_keys = s->prof_keys.get<uint32_t>();
-  p.prof_vals = prof_table_at(s, t);  // (time-dependent walls: t's slot of the ring, checked resident by the caller)
-  p.n_prof = s->n_prof;
+  p.tab_kind = s->bc.tab_kind.get<uint8_t>();
+  p.ids_packed = s->bc.ids_packed;
+  p.kinds_packed = s->bc.kinds_packed;
+  p.n_bc = s->bc.n_bc;
+  p.tab_values = s->bc.tab_values.get();
+  p.prof_keys = s->prof.keys.get<uint32_t>();
+  p.prof_vals = s->prof.table_at(t);  // (time-dependent walls: t's slot of the ring, checked resident by the caller)
+  p.n_prof = s->prof.n;
   p.dist_keys = s->dist_keys.get<uint32_t>();
   p.dist_vals = s->dist_vals.get<float>();
   p.n_dist = s->n_dist;
@@ -233,24 +168,23 @@ static StepLaunch make_launch(xlbhip_stepper* s, const xlbhip_field* src, xlbhip
   p.compute_dtype = s->cdt;
   p.store_dtype = s->sdt;
   p.vec = (int)opt(c, "vec", 0);
-  p.has_bc = p.bc != nullptr ? (s->extended_bcs ? 2 : 1) : 0;
-  p.edge_ext = s->edge_ext_ok ? 1 : 0;
+  p.has_bc = p.bc != nullptr ? (s->bc.extended_bcs ? 2 : 1) : 0;
   p.flags = (opt(c, "nt_store", 1) ? 1 : 0) | (int)(opt(c, "nt_load", 0) << 1);
   p.block_threads = (int)opt(c, "block_threads", 256);
   p.block_tz = (int)opt(c, "block_tz", 0);
   p.xcd_swizzle = (int)opt(c, "xcd_swizzle", 0);
   p.fast_math = opt(c, "exact_math", 0) ? 0 : 1;
-  p.fast_bgk = (opt(c, "fast_bgk", 0) && !opt(c, "exact_math", 0)) ? 1 : 0;
   p.stream = c->stream;
   p.x_begin = 0;
   p.x_count = src->nx;
   return p;
 }
 
-// the inputs of the two-step plan (step2_plan.hpp)
-static Step2Case plan_case(const xlbhip_stepper* s, const StepLaunch& p) {
-  return {s->lattice, s->collision, p.compute_dtype, p.store_dtype, p.fast_math, p.nx, p.ny, p.nz, p.halo,
-          p.has_bc, p.edge_ext, p.n_bc, p.kinds_packed, s->needs_missing ? 1 : 0};
+// the inputs of the two-step plan (step2_plan.hpp) for population fields laid out like f.  has_bc: the launches read a bc mask;
+// edge_ext: every edge-kind cell sits in the x end planes (can_fuse2's scan)
+static Step2Case plan_case(const xlbhip_stepper* s, const xlbhip_field* f, bool has_bc, bool edge_ext) {
+  return {s->lattice, s->collision, s->cdt, s->sdt, opt(s->ctx, "exact_math", 0) ? 0 : 1, f->nx, f->ny, f->nz, f->halo,
+          has_bc ? (s->bc.extended_bcs ? 2 : 1) : 0, edge_ext ? 1 : 0, s->bc.n_bc, s->bc.kinds_packed, s->bc.needs_missing ? 1 : 0};
 }
 
 // CUs the work items of the two-step kernel are to fill
@@ -259,48 +193,73 @@ static long fill_cus(const xlbhip_ctx* c) {
   return o > 0 ? (long)o : (c->compute_units > 0 ? c->compute_units : 256);
 }
 
-static int fuse2_segments(const xlbhip_stepper* s, const StepLaunch& p) {
-  return step2_segments(plan_case(s, p), p.x_count, fill_cus(s->ctx), (int)opt(s->ctx, "fuse2_xseg", 0), opt(s->ctx, "fuse2_clean", 1) != 0);
+static int fuse2_segments(const xlbhip_stepper* s, const Step2Case& pc, int x_count) {
+  return step2_segments(pc, x_count, fill_cus(s->ctx), (int)opt(s->ctx, "fuse2_xseg", 0), opt(s->ctx, "fuse2_clean", 1) != 0);
+}
+
+// the launch of a pair of steps src -> dst over all of x: the single step's part plus the two-step kernel's tables and geometry
+static Step2Launch make_launch2(xlbhip_stepper* s, const Step2Case& pc, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm,
+                                const xlbhip_field* miss, double omega, int64_t t) {
+  xlbhip_ctx* c = s->ctx;
+  Step2Launch p;
+  static_cast<StepLaunch&>(p) = make_launch(s, src, dst, bcm, miss, omega, t);
+  p.meta = s->pairs.meta.get<uint32_t>();
+  // hull tiles first pays when they are much more expensive than fluid tiles (halfway walls: redirected loads) and
+  // with clean work items; otherwise (fullway / equilibrium boundaries alone) the XCD-compact patch is faster
+  const bool clean_on = p.has_bc && opt(c, "fuse2_clean", 1) != 0;
+  p.tile_order = (p.has_bc && (s->bc.needs_missing || clean_on)) ? s->pairs.tile_order.get<uint32_t>() : nullptr;
+  p.x_segments = fuse2_segments(s, pc, p.x_count);
+  p.x_cap = clean_on ? 8 : 0;  // thin first / last x-segments: with walls on the x faces the inner segments are free of them
+  const Step2Tile tile = step2_tile(s->lattice, s->collision, p.has_bc != 0);
+  p.tile_ty = tile.ty;
+  p.tile_tz = tile.tz;
+  if (p.has_bc) {  // half-tile shift: both walls of an axis in one (wrapping) tile row
+    p.tile_oy = p.tile_ty / 2;
+    p.tile_oz = p.tile_tz / 2;
+  }
+  p.fast_bgk = (opt(c, "fast_bgk", 0) && !opt(c, "exact_math", 0)) ? 1 : 0;
+  p.xcd_swizzle = 1;
+  return p;
 }
 
 // assemble_auxiliary_data of the ExtrapolationOutflowBC cells after a step src -> dst (nse_stepper.py:270-272)
 static int outflow_aux(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
                        int64_t t) {
-  if (!s->has_outflow) return 0;
+  if (!s->bc.has_outflow) return 0;
   xlbhip_ctx* c = s->ctx;
   const size_t n = dst->cells();
-  const void* pv = prof_table_at(s, t);
-  XLB_REQUIRE(s->n_prof == 0 || pv, "outflow pass without its profile table (timestep %lld not staged)", (long long)t);
+  const void* pv = s->prof.table_at(t);
+  XLB_REQUIRE(s->prof.n == 0 || pv, "outflow pass without its profile table (timestep %lld not staged)", (long long)t);
   return by_lattice(s->lattice, [&](auto L) {
     return by_compute(s->cdt, [&](auto T) {
       using TT = decltype(T);
       hipLaunchKernelGGL((k_outflow_aux<decltype(L), TT>), blocks_for(n), 256, 0, c->stream, view(src), view(dst), view(bcm), view(miss), dims(dst),
-                         s->tab_kind.get<uint8_t>(), s->tab_values.get<const TT>(), s->prof_keys.get<uint32_t>(), static_cast<const TT*>(pv),
-                         s->n_prof);
+                         s->bc.tab_kind.get<uint8_t>(), s->bc.tab_values.get<const TT>(), s->prof.keys.get<uint32_t>(), static_cast<const TT*>(pv),
+                         s->prof.n);
       XLB_HIP(hipGetLastError());
       return 0;
     });
   });
 }
 
-static int launch_step2(xlbhip_stepper* s, StepLaunch p) {
+static int launch_step2(xlbhip_stepper* s, Step2Launch p) {
   if (s->lattice == XLBHIP_D3Q27 && s->collision == XLBHIP_KBC) return launch_step2_d3q27_kbc(p);
   p.clean = nullptr;
   if (p.has_bc && p.meta && opt(s->ctx, "fuse2_clean", 1)) {
     // what the block -> (tile, x-segment) mapping depends on and may differ between the launches of one stepper (tile, shift and
     // order are the stepper's; x_cap follows fuse2_clean): the flags say "no boundary cell in THIS block's item"
     const std::array<int, 3> key = {p.x_begin, p.x_count, p.x_segments};
-    auto it = s->clean_cache.find(key);
-    if (it == s->clean_cache.end()) {
+    auto it = s->pairs.clean_cache.find(key);
+    if (it == s->pairs.clean_cache.end()) {
       DeviceBuf flags;
       XLB_HIP(flags.alloc((size_t)step2_items(p)));
       if (int rc = step2_build_clean(p, flags.get<uint8_t>())) return rc;
-      it = s->clean_cache.emplace(key, std::move(flags)).first;
+      it = s->pairs.clean_cache.emplace(key, std::move(flags)).first;
     }
     p.clean = it->second.get<uint8_t>();
   }
   if (s->lattice == XLBHIP_D3Q27) return launch_step2_d3q27_bgk(p);
-  return p.strips ? launch_step2_d3q19_bgk_strips(p) : launch_step2_d3q19_bgk(p);
+  return p.strips != Strips::none ? launch_step2_d3q19_bgk_strips(p) : launch_step2_d3q19_bgk(p);
 }
 
 // strip buffer of a population field (1 / 32 of it): allocated on first use; false (and no error) when there is no memory for it
@@ -322,30 +281,30 @@ static bool ensure_strips(xlbhip_field* f) {
 // cell (its f(t+1) on the planes 1 and nx-2 only PULLS from the end planes), and the four end planes go through the
 // single-step kernel twice with a third population field holding their f(t+1).  The first of those launches reads the
 // profile table of timestep t, the second that of t + 1 (time-dependent walls on the end planes).
-static int step_twice_edge_ext(xlbhip_stepper* s, StepLaunch p, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm,
+static int step_twice_edge_ext(xlbhip_stepper* s, const Step2Case& pc, Step2Launch p, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm,
                                const xlbhip_field* miss, double omega, int64_t t) {
-  XLB_REQUIRE(s->scratch && s->scratch->plane_stride == src->plane_stride, "scratch field missing (can_fuse2 allocates it)");
+  XLB_REQUIRE(s->pairs.scratch && s->pairs.scratch->plane_stride == src->plane_stride, "scratch field missing (can_fuse2 allocates it)");
   const int nx = src->nx;
   p.x_begin = 2;
   p.x_count = nx - 4;
-  p.x_segments = fuse2_segments(s, p);
-  if (int rc = launch_step2_d3q19_bgk(p)) return rc;
+  p.x_segments = fuse2_segments(s, pc, p.x_count);
+  if (int rc = launch_step2_d3q19_bgk(p)) return rc;  // (directly: no clean flags, no strips)
   // end planes, step 1: f(t+1) on the planes nx-3 .. nx-1 and 0 .. 2 -> scratch
-  StepLaunch q = make_launch(s, src, s->scratch, bcm, miss, omega, t);
+  StepLaunch q = make_launch(s, src, s->pairs.scratch, bcm, miss, omega, t);
   q.x_begin = nx - 3;
   q.x_count = 3;
   if (int rc = launch_any(s, q)) return rc;
   q.x_begin = 0;
   if (int rc = launch_any(s, q)) return rc;
-  if (int rc = outflow_aux(s, src, s->scratch, bcm, miss, t)) return rc;
+  if (int rc = outflow_aux(s, src, s->pairs.scratch, bcm, miss, t)) return rc;
   // step 2: f(t+2) on the planes nx-2, nx-1, 0, 1 -> dst
-  StepLaunch r = make_launch(s, s->scratch, dst, bcm, miss, omega, t + 1);
+  StepLaunch r = make_launch(s, s->pairs.scratch, dst, bcm, miss, omega, t + 1);
   r.x_begin = nx - 2;
   r.x_count = 2;
   if (int rc = launch_any(s, r)) return rc;
   r.x_begin = 0;
   if (int rc = launch_any(s, r)) return rc;
-  return outflow_aux(s, s->scratch, dst, bcm, miss, t + 1);
+  return outflow_aux(s, s->pairs.scratch, dst, bcm, miss, t + 1);
 }
 
 // the compute stream waits for the halo exchange; with the telemetry on, the wait is bracketed by two timing events
@@ -396,25 +355,20 @@ static int slab_pass(xlbhip_ctx* c, int lattice, xlbhip_field* src, int depth, i
   return launch(src->nx - edge, edge, SlabRole::edge);
 }
 
-// two steps in one pass (a -> scratch-free: src -> dst holds f(t+2)); caller checked eligibility
-static int step_twice(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
-                      double omega, int64_t t) {
-  StepLaunch p = make_launch(s, src, dst, bcm, miss, omega, t);
-  p.meta = s->meta.get<uint32_t>();
-  // hull tiles first pays when they are much more expensive than fluid tiles (halfway walls: redirected loads) and
-  // with clean work items; otherwise (fullway / equilibrium boundaries alone) the XCD-compact patch is faster
-  const bool clean_on = p.has_bc && opt(s->ctx, "fuse2_clean", 1) != 0;
-  p.tile_order = (p.has_bc && (s->needs_missing || clean_on)) ? s->tile_order.get<uint32_t>() : nullptr;
-  p.x_segments = fuse2_segments(s, p);
-  p.x_cap = clean_on ? 8 : 0;  // thin first / last x-segments: with walls on the x faces the inner segments are free of them
-  if (p.has_bc) {  // half-tile shift: both walls of an axis in one (wrapping) tile row
-    p.tile_oy = p.tile_ty / 2;
-    p.tile_oz = p.tile_tz / 2;
-  }
-  p.xcd_swizzle = 1;
+// what can_fuse2 decided for a pair of fields: whether pairs of steps go through the two-step kernel, and whether their x end
+// planes go through the single-step kernel (step_twice_edge_ext)
+struct Fuse2 {
+  bool fuse = false, edge_ext = false;
+};
+
+// two steps in one pass (a -> scratch-free: src -> dst holds f(t+2)); `how`: the caller's can_fuse2 of these fields (how.fuse)
+static int step_twice(xlbhip_stepper* s, Fuse2 how, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm,
+                      const xlbhip_field* miss, double omega, int64_t t) {
+  const Step2Case pc = plan_case(s, src, s->bc.n_bc > 0 && bcm, how.edge_ext);
+  Step2Launch p = make_launch2(s, pc, src, dst, bcm, miss, omega, t);
   xlbhip_ctx* c = s->ctx;
   touch(dst);  // (new contents: whatever was cached on the old ones — its strip buffer — is stale)
-  if (s->edge_ext_ok) return step_twice_edge_ext(s, p, src, dst, bcm, miss, omega, t);
+  if (how.edge_ext) return step_twice_edge_ext(s, pc, p, src, dst, bcm, miss, omega, t);
   // strip buffers (step2_kernel.hpp): phase A's halo columns come from src's strips, phase B writes dst's.  D3Q19, the
   // bit-exact body, (8 x 64) tiles; a field whose strips are not those of its current contents gets them rebuilt first.
   xlbhip_field* srcw = const_cast<xlbhip_field*>(src);
@@ -428,14 +382,14 @@ static int step_twice(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* 
   // q writes dst's strips, and reads src's when they are those of src's current contents (all interior planes).  After anything but
   // a strip-writing pass wrote src — a single step, an upload — the first pass only WRITES strips (no separate rebuild pass: at 512^3
   // that would cost 1.5 ms, a third of a pair, inside e.g. the driver's 20-step timed region after its 5 warm-up steps).
-  auto read_strips = [&](StepLaunch& q) {
+  auto read_strips = [&](Step2Launch& q) {
     const bool valid = srcw->strips_version == srcw->version && srcw->strips_oz == q.tile_oz;
-    q.strips = valid ? 3 : 2;
+    q.strips = valid ? Strips::read_write : Strips::write;
     q.strips_src = valid ? srcw->strips : nullptr;
     q.strips_dst = dst->strips;
   };
   const bool rowmap_only = !strips && opt(c, "fuse2_rowmap", 0) != 0 && p.has_bc && s->lattice == XLBHIP_D3Q19 && !p.fast_bgk && p.tile_ty == 8 && p.tile_tz == 64;
-  if (rowmap_only) p.strips = 4;
+  if (rowmap_only) p.strips = Strips::rowmap;
   auto dst_strips_done = [&]() {  // every interior plane of dst was written by strip-writing launches
     dst->strips_version = dst->version;
     dst->strips_oz = p.tile_oz;
@@ -451,14 +405,14 @@ static int step_twice(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* 
   // from the fresh ghosts).
   const bool overlap = opt(c, "overlap", 1) != 0 && src->nx >= 16;
   auto launch = [&](int x_begin, int x_count, SlabRole role) -> int {
-    StepLaunch q = p;
+    Step2Launch q = p;
     q.x_begin = x_begin;
     q.x_count = x_count;
-    q.x_segments = role == SlabRole::edge ? 1 : fuse2_segments(s, q);
+    q.x_segments = role == SlabRole::edge ? 1 : fuse2_segments(s, pc, x_count);
     if (strips && role == SlabRole::interior) {
       read_strips(q);
     } else if (strips) {  // launches whose phase A pulls from ghost planes (no strips there) only WRITE strips
-      q.strips = 2;
+      q.strips = Strips::write;
       q.strips_dst = dst->strips;
     }
     return launch_step2(s, q);
@@ -468,78 +422,80 @@ static int step_twice(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* 
   return 0;
 }
 
-static bool can_fuse2(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss) {
+// Whether pairs of steps on these fields go through the two-step kernel.  May run the edge-kind scan of bcm and allocate the
+// scratch field; changes nothing else of the stepper.
+static Fuse2 can_fuse2(xlbhip_stepper* s, const xlbhip_field* src, const xlbhip_field* bcm) {
   const int64_t mode = opt(s->ctx, "fuse2", 1);
-  if (mode == 0 || s->forced) return false;
-  s->edge_ext_ok = false;
-  if (s->has_edge_kinds) {
+  if (mode == 0 || s->forced) return {};
+  bool edge_ext = false;
+  if (s->bc.has_edge_kinds) {
     // Zou-He / Regularized / outflow / do-nothing cells: fine when they all sit in the two x end planes (scan of bc_mask, 1 B / cell)
-    if (!bcm || src->halo != 0 || src->nx < 16 || s->lattice != XLBHIP_D3Q19) return false;
+    if (!bcm || src->halo != 0 || src->nx < 16 || s->lattice != XLBHIP_D3Q19) return {};
     xlbhip_ctx* c = s->ctx;
-    if (!(s->scan_key == FieldKey(bcm))) {  // one scan per (stepper, bc_mask contents), not per run
+    if (!(s->pairs.scan_key == FieldKey(bcm))) {  // one scan per (stepper, bc_mask contents), not per run
       DeviceBuf dflag;
       int flag = 1;
-      if (dflag.alloc(sizeof(int)) != hipSuccess) return false;
+      if (dflag.alloc(sizeof(int)) != hipSuccess) return {};
       (void)hipMemsetAsync(dflag.get(), 0, sizeof(int), c->stream);
-      hipLaunchKernelGGL(k_ext_interior_scan, blocks_for(bcm->cells()), 256, 0, c->stream, view(bcm), s->tab_kind.get<uint8_t>(), dims(bcm),
+      hipLaunchKernelGGL(k_ext_interior_scan, blocks_for(bcm->cells()), 256, 0, c->stream, view(bcm), s->bc.tab_kind.get<uint8_t>(), dims(bcm),
                          dflag.get<int>());
       if (hipMemcpyAsync(&flag, dflag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
         flag = 1;
-      s->scan_key = FieldKey(bcm);
-      s->scan_flag = flag;
+      s->pairs.scan_key = FieldKey(bcm);
+      s->pairs.scan_flag = flag;
     }
-    if (s->scan_flag != 0) return false;
+    if (s->pairs.scan_flag != 0) return {};
     // the end planes need a third population field; without the memory for it the stepper stays on single steps
-    if (!s->scratch || s->scratch->nx != src->nx || s->scratch->ny != src->ny || s->scratch->nz != src->nz || s->scratch->dtype != src->dtype) {
-      if (s->scratch) xlbhip_field_destroy(s->scratch);
-      s->scratch = nullptr;
-      if (xlbhip_field_create(c, src->card, src->nx, src->ny, src->nz, src->dtype, src->halo, 0.0, &s->scratch) != 0 ||
-          s->scratch->plane_stride != src->plane_stride) {
-        if (s->scratch) xlbhip_field_destroy(s->scratch);
-        s->scratch = nullptr;
+    if (!s->pairs.scratch || s->pairs.scratch->nx != src->nx || s->pairs.scratch->ny != src->ny || s->pairs.scratch->nz != src->nz || s->pairs.scratch->dtype != src->dtype) {
+      if (s->pairs.scratch) xlbhip_field_destroy(s->pairs.scratch);
+      s->pairs.scratch = nullptr;
+      if (xlbhip_field_create(c, src->card, src->nx, src->ny, src->nz, src->dtype, src->halo, 0.0, &s->pairs.scratch) != 0 ||
+          s->pairs.scratch->plane_stride != src->plane_stride) {
+        if (s->pairs.scratch) xlbhip_field_destroy(s->pairs.scratch);
+        s->pairs.scratch = nullptr;
         (void)hipGetLastError();
-        return false;
+        return {};
       }
     }
-    s->edge_ext_ok = true;
+    edge_ext = true;
   }
-  const StepLaunch p = make_launch(s, src, dst, bcm, miss, 1.0, 0);  // (the plan's inputs only: no launch)
-  return step2_fuse(plan_case(s, p), (int)mode, fill_cus(s->ctx), (int)opt(s->ctx, "fuse2_xseg", 0), opt(s->ctx, "fuse2_clean", 1) != 0);
+  const Step2Case pc = plan_case(s, src, s->bc.n_bc > 0 && bcm, edge_ext);
+  const bool fuse = step2_fuse(pc, (int)mode, fill_cus(s->ctx), (int)opt(s->ctx, "fuse2_xseg", 0), opt(s->ctx, "fuse2_clean", 1) != 0);
+  return {fuse, fuse && edge_ext};
 }
 
 // per-run tables of the two-step kernel: the meta words (bc kind | slot | missing bits per cell, ghost planes
 // included) and the hull-first tile order
 static int prepare_fuse2(xlbhip_stepper* s, const xlbhip_field* bcm, const xlbhip_field* miss) {
-  if (!(s->n_bc > 0 && bcm)) return 0;
+  if (!(s->bc.n_bc > 0 && bcm)) return 0;
   xlbhip_ctx* c = s->ctx;
   const size_t cells = bcm->cells_with_halo();
-  if (s->meta_cells != cells) {
-    if (s->meta) comm_forget_buffer(c, s->meta.get());
-    XLB_HIP(s->meta.alloc(cells * sizeof(uint32_t)));
-    s->meta_cells = cells;
-    s->meta_key = MetaKey();  // (contents gone: rebuild below)
+  if (s->pairs.meta_cells != cells) {
+    s->pairs.forget_meta(c);  // (contents gone: rebuilt below)
+    XLB_HIP(s->pairs.meta.alloc(cells * sizeof(uint32_t)));
+    s->pairs.meta_cells = cells;
   }
   const Step2Tile tile = step2_tile(s->lattice, s->collision, true);
   const int tys = bcm->ny / tile.ty, tzs = bcm->nz / tile.tz;
-  if (s->order_ty != tys || s->order_tz != tzs) {
+  if (s->pairs.order_ty != tys || s->pairs.order_tz != tzs) {
     const std::vector<uint32_t> order = step2_tile_order(tys, tzs);
-    s->clean_cache.clear();  // the flags were computed for the old block -> tile mapping
-    if (int rc = upload_bytes(order.data(), order.size() * sizeof(uint32_t), s->tile_order)) return rc;
-    s->order_ty = tys;
-    s->order_tz = tzs;
+    s->pairs.drop_clean();  // the flags were computed for the old block -> tile mapping
+    if (int rc = upload_bytes(order.data(), order.size() * sizeof(uint32_t), s->pairs.tile_order)) return rc;
+    s->pairs.order_ty = tys;
+    s->pairs.order_tz = tzs;
   }
   const MetaKey key{FieldKey(bcm), FieldKey(miss), opt(c, "external_halo", 0) != 0};
-  if (s->meta_key == key) return 0;  // meta words, tile order and clean flags are those of these very masks
-  s->meta_key = key;
-  s->clean_cache.clear();  // (stream-ordered: the flags' last readers were enqueued before this point and hipFree synchronises)
+  if (s->pairs.meta_key == key) return 0;  // meta words, tile order and clean flags are those of these very masks
+  s->pairs.meta_key = key;
+  s->pairs.drop_clean();
   hipLaunchKernelGGL(k_build_meta, blocks_for(cells), 256, 0, c->stream, static_cast<const uint8_t*>(bcm->data),
-                     miss ? static_cast<const uint32_t*>(miss->data) : nullptr, s->meta.get<uint32_t>(), cells, s->ids_packed, s->kinds_packed,
-                     s->moving_mask, s->lattice == XLBHIP_D3Q27 ? 1 : 0);
+                     miss ? static_cast<const uint32_t*>(miss->data) : nullptr, s->pairs.meta.get<uint32_t>(), cells, s->bc.ids_packed, s->bc.kinds_packed,
+                     s->bc.moving_mask, s->lattice == XLBHIP_D3Q27 ? 1 : 0);
   XLB_HIP(hipGetLastError());
   // slab decomposition: phase A also runs on the ghost planes -1 and nx, so it needs the neighbours' boundary
   // information there.  Host-staged transports (external_halo) fill the ghost planes of the masks themselves.
   if (bcm->halo > 0 && !opt(c, "external_halo", 0))
-    return plane_exchange_on(c, s->meta.get(), sizeof(uint32_t), bcm->nx, bcm->ny, bcm->nz, bcm->halo, c->stream);
+    return plane_exchange_on(c, s->pairs.meta.get(), sizeof(uint32_t), bcm->nx, bcm->ny, bcm->nz, bcm->halo, c->stream);
   return 0;
 }
 
@@ -619,47 +575,28 @@ int xlbhip_stepper_create(xlbhip_ctx* c, int lattice, int collision, int cdt, in
   s->collision = collision;
   s->cdt = cdt;
   s->sdt = sdt;
-  s->n_bc = n_bc;
-  s->needs_missing = needs_missing;
-  s->extended_bcs = extended;
-  s->has_outflow = has_outflow;
-  s->has_edge_kinds = has_edge_kinds;
-  s->ids_packed = ids_packed;
-  s->kinds_packed = kinds_packed;
-  s->moving_mask = moving_mask;
-  if (int rc = upload_bytes(kind.data(), 256, s->tab_kind)) return rc;
-  if (int rc = upload_values(cdt, vals, s->tab_values)) return rc;
+  s->bc.n_bc = n_bc;
+  s->bc.needs_missing = needs_missing;
+  s->bc.extended_bcs = extended;
+  s->bc.has_outflow = has_outflow;
+  s->bc.has_edge_kinds = has_edge_kinds;
+  s->prof.ctx = c;
+  s->prof.cdt = cdt;
+  s->bc.ids_packed = ids_packed;
+  s->bc.kinds_packed = kinds_packed;
+  s->bc.moving_mask = moving_mask;
+  if (int rc = upload_bytes(kind.data(), 256, s->bc.tab_kind)) return rc;
+  if (int rc = upload_values(cdt, vals, s->bc.tab_values)) return rc;
   *out = s.release();
   return 0;
 }
 
 }  // extern "C"
 
-// the sorted device image of the merged table (std::map iterates in key order), its host copy, the rows of the time-dependent
-// cells in it, and the PROF_FLAG of bc_id; drops the ring (its images have the old layout).  The stream is drained.
-static int upload_prof_table(xlbhip_stepper* s, int bc_id) {
-  std::vector<uint32_t> keys;
-  std::vector<double> v64;
-  keys.reserve(s->prof_host.size());
-  v64.reserve(3 * s->prof_host.size());
-  for (const auto& kv : s->prof_host) {
-    keys.push_back(kv.first);
-    v64.insert(v64.end(), kv.second.begin(), kv.second.end());
-  }
-  s->n_prof = (int)keys.size();
-  if (int rc = upload_keys(keys, s->prof_keys)) return rc;
-  if (int rc = upload_values(s->cdt, v64, s->prof_vals)) return rc;
-  // flag the BC: its prescribed values come from the table (cell.hpp: PROF_FLAG)
+// flag the BC: its prescribed values come from the profile table (cell.hpp: PROF_FLAG)
+static int flag_profile_bc(xlbhip_stepper* s, int bc_id) {
   const std::vector<char> one = compute_image(s->cdt, {1.0});
-  XLB_HIP(hipMemcpy(s->tab_values.get<char>() + ((size_t)bc_id * 27 + PROF_FLAG) * one.size(), one.data(), one.size(), hipMemcpyHostToDevice));
-  if (s->td_cells.empty() && !s->ring) return 0;
-  s->prof_image = compute_image(s->cdt, v64);
-  s->td_pos.resize(s->td_cells.size());
-  for (size_t i = 0; i < s->td_cells.size(); ++i)
-    s->td_pos[i] = (int)(std::lower_bound(keys.begin(), keys.end(), s->td_cells[i]) - keys.begin());
-  s->td_contiguous = true;
-  for (size_t i = 0; i < s->td_pos.size(); ++i) s->td_contiguous = s->td_contiguous && s->td_pos[i] == s->td_pos[0] + (int)i;
-  free_ring(s);
+  XLB_HIP(hipMemcpy(s->bc.tab_values.get<char>() + ((size_t)bc_id * 27 + PROF_FLAG) * one.size(), one.data(), one.size(), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -668,86 +605,35 @@ extern "C" {
 int xlbhip_stepper_set_bc_profile(xlbhip_stepper* s, int bc_id, int64_t n, const uint32_t* storage_cells, const double* values) {
   XLB_REQUIRE(s && bc_id >= 1 && bc_id <= 255, "bad argument");
   XLB_REQUIRE(n == 0 || (storage_cells && values), "null table");
-  xlbhip_ctx* c = s->ctx;
-  XLB_HIP(hipSetDevice(c->device));
-  XLB_HIP(hipStreamSynchronize(c->stream));
-  for (int64_t i = 0; i < n; ++i) s->prof_host[storage_cells[i]] = {values[3 * i], values[3 * i + 1], values[3 * i + 2]};
-  return upload_prof_table(s, bc_id);
+  XLB_HIP(hipSetDevice(s->ctx->device));
+  if (int rc = s->prof.add_static(n, storage_cells, values)) return rc;
+  return flag_profile_bc(s, bc_id);
 }
 
 int xlbhip_stepper_set_bc_profile_cells(xlbhip_stepper* s, int bc_id, int64_t n, const uint32_t* storage_cells) {
   XLB_REQUIRE(s && bc_id >= 1 && bc_id <= 255, "bad argument");
   XLB_REQUIRE(n == 0 || storage_cells, "null cell list");
-  xlbhip_ctx* c = s->ctx;
-  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipSetDevice(s->ctx->device));
   uint8_t kind = 0;
-  XLB_HIP(hipMemcpy(&kind, s->tab_kind.get<uint8_t>() + bc_id, 1, hipMemcpyDeviceToHost));
+  XLB_HIP(hipMemcpy(&kind, s->bc.tab_kind.get<uint8_t>() + bc_id, 1, hipMemcpyDeviceToHost));
   XLB_REQUIRE((kind >= XLBHIP_BC_HYBRID_BB_REGULARIZED && kind <= XLBHIP_BC_HYBRID_NEQ_REGULARIZED) || kind == XLBHIP_BC_HALFWAY_BB_PROFILE,
               "time-dependent wall velocities: bc %d is of kind %d (HybridBC / HalfwayBounceBackBC with a profile)", bc_id, (int)kind);
-  XLB_HIP(hipStreamSynchronize(c->stream));
-  for (int64_t i = 0; i < n; ++i)
-    XLB_REQUIRE(s->prof_host.find(storage_cells[i]) == s->prof_host.end(), "cell %u has a profile table entry already", storage_cells[i]);
-  for (int64_t i = 0; i < n; ++i) {
-    s->prof_host[storage_cells[i]] = {0.0, 0.0, 0.0};  // (placeholder: every image carries this timestep's value)
-    s->td_cells.push_back(storage_cells[i]);
-  }
-  if (n > 0) s->td_bc[bc_id] = 1;
-  return upload_prof_table(s, bc_id);
+  if (int rc = s->prof.declare_time_dependent(bc_id, n, storage_cells)) return rc;
+  return flag_profile_bc(s, bc_id);
 }
 
 int xlbhip_stepper_profile_slots(xlbhip_stepper* s, int* slots) {
   XLB_REQUIRE(s && slots, "null argument");
-  *slots = has_td(s) ? prof_ring_slot_count(prof_image_bytes(s)) : 0;
+  *slots = s->prof.slot_count();
   return 0;
 }
 
 int xlbhip_stepper_stage_bc_profiles(xlbhip_stepper* s, int64_t t_first, int64_t n_steps, const double* values) {
   XLB_REQUIRE(s, "stepper is null");
-  XLB_REQUIRE(has_td(s), "this stepper has no time-dependent wall velocities (xlbhip_stepper_set_bc_profile_cells)");
+  XLB_REQUIRE(s->prof.has_td(), "this stepper has no time-dependent wall velocities (xlbhip_stepper_set_bc_profile_cells)");
   XLB_REQUIRE(n_steps >= 0 && (n_steps == 0 || values), "bad argument");
-  xlbhip_ctx* c = s->ctx;
-  XLB_HIP(hipSetDevice(c->device));
-  if (int rc = ensure_ring(s)) return rc;
-  XLB_REQUIRE(n_steps <= s->ring_book.slots(), "%lld tables staged at once, the ring holds %d (xlbhip_stepper_profile_slots)", (long long)n_steps,
-              s->ring_book.slots());
-  const size_t img = prof_image_bytes(s), nt = s->td_cells.size();
-  char* pin = s->ring_pin.get<char>();
-  int64_t r = 0;  // the image of timestep t_first + r goes next
-  for (const ProfRing::Run run : s->ring_book.take((int)n_steps)) {
-    const int64_t r_first = r;
-    for (int k = run.first; k < run.first + run.len; ++k, ++r) {
-      XLB_HIP(hipEventSynchronize(s->ring_ev[k]));  // the previous copy out of this pinned row (not the kernels)
-      char* row = pin + (size_t)k * img;
-      if (!s->ring_pin_ready[k]) {
-        std::memcpy(row, s->prof_image.data(), img);
-        s->ring_pin_ready[k] = 1;
-      }
-      const double* v = values + (size_t)r * nt * 3;
-      by_compute(s->cdt, [&](auto T) {
-        auto* d = reinterpret_cast<decltype(T)*>(row);
-        if (s->td_contiguous) {  // one time-dependent BC, or several whose cells are not interleaved with others: one block of the table
-          std::copy(v, v + 3 * nt, d + (size_t)s->td_pos[0] * 3);
-        } else {
-          for (size_t i = 0; i < nt; ++i)
-            for (int a = 0; a < 3; ++a) d[(size_t)s->td_pos[i] * 3 + a] = (decltype(T))v[i * 3 + a];
-        }
-        return 0;
-      });
-    }
-    // one copy per run of consecutive slots, on the compute stream: it lands after every kernel enqueued so far (those that still
-    // read an older image of these slots) and before every launch that looks these timesteps up.  A slot counts as resident only
-    // once its copy is enqueued; if that fails, nothing of the run is claimed.
-    const size_t off = (size_t)run.first * img;
-    XLB_HIP(hipMemcpyAsync(s->ring.get<char>() + off, pin + off, (size_t)run.len * img, hipMemcpyHostToDevice, c->stream));
-    for (int k = run.first; k < run.first + run.len; ++k) {
-      if (hipError_t e = hipEventRecord(s->ring_ev[k], c->stream); e != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);  // (no copy out of a pinned row may stay in flight behind a stale event)
-        XLB_FAIL("hipEventRecord: %s", hipGetErrorString(e));
-      }
-    }
-    s->ring_book.mark_resident(run, t_first + r_first);
-  }
-  return 0;
+  XLB_HIP(hipSetDevice(s->ctx->device));
+  return s->prof.stage(t_first, n_steps, values);
 }
 
 int xlbhip_stepper_momentum_transfer(xlbhip_stepper* s, int bc_id, const xlbhip_field* f_0, const xlbhip_field* bcm, const xlbhip_field* miss,
@@ -765,14 +651,12 @@ int xlbhip_stepper_momentum_transfer_at(xlbhip_stepper* s, int bc_id, int64_t ti
   XLB_REQUIRE(f_0->halo == 0, "momentum_transfer through the stepper's tables: fields without ghost planes (mesh / profile BCs live on one rank)");
   uint8_t kind = 0;
   XLB_HIP(hipSetDevice(c->device));
-  XLB_HIP(hipMemcpy(&kind, s->tab_kind.get<uint8_t>() + bc_id, 1, hipMemcpyDeviceToHost));
+  XLB_HIP(hipMemcpy(&kind, s->bc.tab_kind.get<uint8_t>() + bc_id, 1, hipMemcpyDeviceToHost));
   XLB_REQUIRE((kind >= XLBHIP_BC_HYBRID_BB_REGULARIZED && kind <= XLBHIP_BC_HYBRID_NEQ_REGULARIZED) || kind == XLBHIP_BC_HALFWAY_BB_PROFILE,
               "momentum_transfer through the stepper: bc %d is of kind %d (HybridBC / profile walls; plain walls use xlbhip_momentum_transfer)", bc_id,
               (int)kind);
-  // a time-dependent wall: the wall velocities of this timestep.  Any other BC: the single table (the kernel reads entries of bc_id's
-  // cells only, and every staged image carries the same static entries), whatever is staged.
-  const void* pv = s->td_bc[bc_id] ? prof_table_at(s, timestep) : s->prof_vals.get();
-  XLB_REQUIRE(s->n_prof == 0 || pv, "momentum_transfer: the time-dependent wall velocities of timestep %lld are not staged", (long long)timestep);
+  const void* pv = s->prof.table_for(bc_id, timestep);
+  XLB_REQUIRE(s->prof.n == 0 || pv, "momentum_transfer: the time-dependent wall velocities of timestep %lld are not staged", (long long)timestep);
   DeviceBuf dforce;
   XLB_HIP(dforce.alloc(3 * sizeof(double)));
   XLB_HIP(hipMemsetAsync(dforce.get(), 0, 3 * sizeof(double), c->stream));
@@ -781,8 +665,8 @@ int xlbhip_stepper_momentum_transfer_at(xlbhip_stepper* s, int bc_id, int64_t ti
     return by_compute(s->cdt, [&](auto T) {
       using TT = decltype(T);
       hipLaunchKernelGGL((k_momentum_transfer_tab<decltype(L), TT>), blocks_for(n), 256, 0, c->stream, view(f_0), view(bcm), view(miss), dims(f_0), bc_id,
-                         s->tab_kind.get<uint8_t>(), s->tab_values.get<const TT>(), s->prof_keys.get<uint32_t>(), static_cast<const TT*>(pv),
-                         s->n_prof, s->dist_keys.get<uint32_t>(), s->dist_vals.get<float>(), s->n_dist, dforce.get<double>());
+                         s->bc.tab_kind.get<uint8_t>(), s->bc.tab_values.get<const TT>(), s->prof.keys.get<uint32_t>(), static_cast<const TT*>(pv),
+                         s->prof.n, s->dist_keys.get<uint32_t>(), s->dist_vals.get<float>(), s->n_dist, dforce.get<double>());
       XLB_HIP(hipGetLastError());
       return 0;
     });
@@ -808,12 +692,7 @@ int xlbhip_stepper_set_bc_distances(xlbhip_stepper* s, int64_t n, const uint32_t
   }
   std::vector<uint32_t> keys;
   std::vector<float> vals;
-  keys.reserve(s->dist_host.size());
-  vals.reserve(s->dist_host.size() * (size_t)q);
-  for (const auto& kv : s->dist_host) {  // std::map iterates in key order
-    keys.push_back(kv.first);
-    vals.insert(vals.end(), kv.second.begin(), kv.second.begin() + q);
-  }
+  sorted_table(s->dist_host, (size_t)q, keys, vals);
   s->n_dist = (int)keys.size();
   if (int rc = upload_keys(keys, s->dist_keys)) return rc;
   return upload_bytes(vals.data(), vals.size() * sizeof(float), s->dist_vals);
@@ -836,9 +715,9 @@ int xlbhip_stepper_destroy(xlbhip_stepper* s) {
   if (!s) return 0;
   (void)hipSetDevice(s->ctx->device);
   (void)hipStreamSynchronize(s->ctx->stream);
-  free_ring(s);  // (explicitly here, after the drain: copies may still read the pinned rows)
-  if (s->meta) comm_forget_buffer(s->ctx, s->meta.get());
-  if (s->scratch) xlbhip_field_destroy(s->scratch);
+  s->prof.release();  // (explicitly here, after the drain: copies may still read the pinned rows)
+  s->pairs.forget_meta(s->ctx);
+  if (s->pairs.scratch) xlbhip_field_destroy(s->pairs.scratch);
   delete s;  // (the device tables go with their owners)
   return 0;
 }
@@ -847,7 +726,7 @@ int xlbhip_step(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, c
                 double omega, int64_t timestep) {
   // the timestep selects the wall velocities of time-dependent profiles (nse_stepper.py:370-378 passes it to every BC functional)
   if (int rc = check_step_fields(s, src, dst, bcm, miss)) return rc;
-  if (int rc = require_staged(s, timestep, 1)) return rc;
+  if (int rc = s->prof.require_staged(timestep, 1)) return rc;
   return step_once(s, src, dst, bcm, miss, omega, timestep);
 }
 
@@ -857,7 +736,7 @@ static int run_steps(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const 
                      int64_t t0, int64_t n, bool fixed_placement, int* result_in_b) {
   XLB_REQUIRE(n >= 0, "n_steps < 0");
   if (int rc = check_step_fields(s, a, b, bcm, miss)) return rc;
-  if (int rc = require_staged(s, t0, n)) return rc;
+  if (int rc = s->prof.require_staged(t0, n)) return rc;
   // With two-step fusion ("fuse2") a pair of steps is ONE pass a -> b: pairs alternate direction (a -> b, b -> a, ...).
   // Under the fixed placement contract a trailing half pair (buffer parity) is fixed up by single steps.
   int64_t i = 0;
@@ -865,22 +744,22 @@ static int run_steps(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const 
   xlbhip_field* oth = b;
   // (a host-staged transport refills the ghosts between calls: it drives pairs through xlbhip_step2 itself)
   const bool caller_fills_ghosts = a->halo > 0 && opt(s->ctx, "external_halo", 0) != 0;
-  bool fuse = n >= 2 && !caller_fills_ghosts && can_fuse2(s, a, b, bcm, miss);
+  Fuse2 how = (n >= 2 && !caller_fills_ghosts) ? can_fuse2(s, a, bcm) : Fuse2();
   if (n >= 2 && a->halo > 0 && !caller_fills_ghosts && comm_ranks(s->ctx) > 1) {
     // pairs and single steps post different message sets (depth-2 / depth-1 exchange, meta planes): every rank must take
     // the same decision, and uneven slabs may sit on either side of the chip-filling rule -> MIN over the ranks
     int all = 0;
-    if (int rc = comm_all_min(s->ctx, fuse ? 1 : 0, &all)) return rc;
-    fuse = all != 0;
+    if (int rc = comm_all_min(s->ctx, how.fuse ? 1 : 0, &all)) return rc;
+    how.fuse = all != 0;
   }
-  if (fuse) {
+  if (how.fuse) {
     if (int rc = prepare_fuse2(s, bcm, miss)) return rc;
     // choose the number of pairs so that the remaining single steps land the result in the right buffer:
     // after P pairs the data sits in (P odd ? b : a); then r = n - 2P single steps flip r more times.
     // P + r must be congruent to n (mod 2)  <=>  P even.  Use the largest even P with 2P <= n.
     int64_t pairs = fixed_placement ? ((n / 2) & ~int64_t(1)) : n / 2;
     for (int64_t k = 0; k < pairs; ++k) {
-      if (int rc = step_twice(s, cur, oth, bcm, miss, omega, t0 + 2 * k)) return rc;
+      if (int rc = step_twice(s, how, cur, oth, bcm, miss, omega, t0 + 2 * k)) return rc;
       xlbhip_field* tmp = cur;
       cur = oth;
       oth = tmp;
@@ -910,16 +789,17 @@ int xlbhip_run_any(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const xl
 
 int xlbhip_step2_eligible(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss) {
   if (check_step_fields(s, src, dst, bcm, miss)) return 0;
-  return can_fuse2(s, src, dst, bcm, miss) ? 1 : 0;
+  return can_fuse2(s, src, bcm).fuse ? 1 : 0;
 }
 
 int xlbhip_step2(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
                  double omega, int64_t timestep) {
   if (int rc = check_step_fields(s, src, dst, bcm, miss)) return rc;
-  if (int rc = require_staged(s, timestep, 2)) return rc;
-  XLB_REQUIRE(can_fuse2(s, src, dst, bcm, miss), "this stepper / field layout has no two-step kernel (see xlbhip_step2_eligible)");
+  if (int rc = s->prof.require_staged(timestep, 2)) return rc;
+  const Fuse2 how = can_fuse2(s, src, bcm);
+  XLB_REQUIRE(how.fuse, "this stepper / field layout has no two-step kernel (see xlbhip_step2_eligible)");
   if (int rc = prepare_fuse2(s, bcm, miss)) return rc;
-  return step_twice(s, src, dst, bcm, miss, omega, timestep);
+  return step_twice(s, how, src, dst, bcm, miss, omega, timestep);
 }
 
 int xlbhip_run_timed(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const xlbhip_field* bcm, const xlbhip_field* miss, double omega,
