@@ -353,7 +353,8 @@ int xlbhip_ibm_footprint(xlbhip_ibm* ibm, int64_t* n_cells, int64_t capacity, ui
  * velocities on the device after every step; the call order is that of xlb/operator/stepper/ibm_stepper.py:379-476 with the markers
  * placed first.  The per-body force and torque have no counterpart in the reference (its drivers sum marker forces on the host).
  *
- * A body is a range [first, first + count) of the markers; bodies are disjoint, at most 64.  moving[i] != 0: before every step
+ * A body is a range [first, first + count) of the markers; bodies are disjoint, at most 64.  moving[i] is 0 (at rest), 1 (prescribed:
+ * staged poses) or 2 (dynamic: see "free rigid bodies" below).  moving[i] != 0: before every step
  * marker k of body i is placed at X = c + R (X0 - centre0_i) and given U = v + w x (X - c), with X0 the position last UPLOADED
  * (the reference position), and (R, c, w, v) the body's pose at that timestep: 18 doubles, R row-major first.  fp64 in the order
  * X_a = ((R_a0 d_0 + R_a1 d_1) + R_a2 d_2) + c_a, rounded to float32; U is evaluated on the rounded X.  The uploaded velocities of
@@ -381,6 +382,31 @@ int xlbhip_ibm_record_loads(xlbhip_ibm* ibm, int64_t n_rows);
 int xlbhip_ibm_loads_history(xlbhip_ibm* ibm, int64_t n_rows, double* loads);
 /* the markers as the device holds them now (after the last step's move), (n, 3) float32 each; NULL: skipped.  Synchronous. */
 int xlbhip_ibm_download_markers(xlbhip_ibm* ibm, int64_t n, float* positions, float* velocities);
+
+/* -- free (force-driven) rigid bodies --
+ * No counterpart in the reference (examples/ibm/wind_turbine_ibm.py prescribes its rotor's rate).  moving[i] == 2 in
+ * xlbhip_ibm_set_bodies declares body i DYNAMIC: its pose is not staged but advanced on the device, once per step and after the
+ * loads of that step, by the explicit scheme stated in csrc/ibm_dynamics_kernels.hpp (symplectic Euler for the centre, a Cayley
+ * update of a unit quaternion for the rotation; fp64, dt = 1, one stated operation order).  A dynamic body counts as moving: its
+ * markers are placed by the same rule as a prescribed body's and the footprint is rebuilt every step.  Staged poses are demanded
+ * only while a PRESCRIBED body moves; the rows staged for dynamic bodies are ignored.
+ *
+ * _set_dynamics: for every declared body (the entries of bodies that are not dynamic are ignored) the rotation mode — 0 locked,
+ * 1 about a fixed world axis, 2 free — 32 doubles of parameters and 16 doubles of initial state:
+ *   params: 0 1/mass | 1-3 translate (0. or 1. per world axis) | 4-6 force | 7-9 torque | 10-12 spring anchor | 13-15 stiffness |
+ *           16-18 damping | 19-27 inverse body-frame inertia, row-major | 28-30 axis (unit) | 31 1 / (inertia about the axis)
+ *   state:  0-2 c | 3-5 v | 6-9 unit quaternion (w, x, y, z) | 10-12 world-frame angular momentum (axis mode: [10] is the rate) | 0 0 0
+ * Called after xlbhip_ibm_set_bodies and before the first step (steps fail until it is); calling it again resets the state and
+ * clears the status word.  Waits for the stream (set-up call). */
+int xlbhip_ibm_set_dynamics(xlbhip_ibm* ibm, int n_bodies, const int* rotate, const double* params, const double* state);
+/* the poses [n_bodies][18] (R | c | w | v) the NEXT step would read — the state of the dynamic bodies, the rest pose of every
+ * other body (the caller knows the prescribed ones) — and the sticky status word: bit i set = a new state of body i had a component
+ * that was not finite and was not stored; the body has stood still since.  Synchronous. */
+int xlbhip_ibm_body_poses(xlbhip_ibm* ibm, int n_bodies, double* poses, uint64_t* status);
+/* as _record_loads / _loads_history for the poses that the move and the loads of every step read, [n_rows][n_bodies][18]: the
+ * state of dynamic bodies, the staged rows of prescribed ones, the rest poses of bodies at rest. */
+int xlbhip_ibm_record_poses(xlbhip_ibm* ibm, int64_t n_rows);
+int xlbhip_ibm_poses_history(xlbhip_ibm* ibm, int64_t n_rows, double* poses);
 
 /* ---- flow statistics ------------------------------------------------------- */
 /* No counterpart in the reference: its drivers copy whole fields to the host and reduce them in NumPy (e.g.

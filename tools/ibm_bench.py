@@ -15,7 +15,14 @@ shapes: see coupling_bytes).
 --moving times, interleaved, (a) the loop the host drives — NumPy kinematics, markers.update(vertices, velocities) and one call per
 step —, (b) the native run with the sphere declared as a body with a RigidMotion and (c) the native run with the markers at rest, and
 reports (a) and (b) in ms/step and (b - c) / b, the share of the step that moving the markers, rebuilding the footprint and summing
-the loads take."""
+the loads take.
+
+    python tools/ibm_bench.py --dynamics [--steps 100 --rounds 5]   # the --moving sphere as a FREE body against the prescribed one
+    python tools/ibm_bench.py --dynamics --counted-only             # no GPU: the two launches a free body adds, and their bytes
+
+--dynamics times, interleaved round by round (the bodies are declared before the clock starts), the native run of the sphere as a
+body with a RigidMotion (what --moving calls "native") and the native run of the same sphere declared with a RigidDynamics (heavy, spinning at --rate, so that it moves as the
+prescribed one does), and reports both medians, the spread of each and their difference: what k_ibm_pose and k_ibm_integrate cost."""
 
 import argparse
 import json
@@ -60,6 +67,69 @@ def moving_counts(n_markers, n_slots, n_bodies=1, compute=4, cap=None):
     loads = {"launches": 2, "bytes": n_markers * (3 * compute + 16) + chunks * 96 + n_bodies * 96}
     return {"move": move, "rebuild": rebuild, "loads": loads, "launches_added": 11, "bytes_added": move["bytes"] + rebuild["bytes"] + loads["bytes"],
             "pose_bytes_over_the_host_link": 144 * n_bodies}
+
+
+def dynamics_counts(n_bodies=1, recorded=False):
+    """Launches and bytes one step of a run with FREE bodies adds on top of moving_counts (csrc/ibm.hip: ibm_live_pose,
+    ibm_integrate), per body.  k_ibm_pose: 8 (kind, rotate) + 128 (state) + 256 (parameters) read — or 144 of a staged / rest row —,
+    144 written (twice when a history is recorded).  k_ibm_integrate: 8 + 256 + 128 + 48 (loads) read, 104 written (13 doubles of
+    state).  No pose crosses the host link."""
+    pose = {"launches": 1, "blocks": 1, "threads": 64, "bytes": n_bodies * (8 + 128 + 256 + 144 * (2 if recorded else 1))}
+    integrate = {"launches": 1, "blocks": 1, "threads": 64, "bytes": n_bodies * (8 + 256 + 128 + 48 + 104)}
+    return {"pose": pose, "integrate": integrate, "launches_added": 2, "bytes_added": pose["bytes"] + integrate["bytes"], "pose_bytes_over_the_host_link": 0}
+
+
+def bench_dynamics(args, ctx, ibm, make_fields, vertices, velocities, centre, omega):
+    from xlb_amd.helper.ibm_helper import IBMBody, RigidDynamics, RigidMotion
+
+    f_0, f_1, bc_mask, missing_mask = make_fields()
+    markers = ibm._markers
+    clock = [0]
+
+    def timed(fn):
+        import time
+
+        ctx.sync()
+        t0 = time.perf_counter()
+        out = fn()
+        ctx.sync()
+        return out, (time.perf_counter() - t0) * 1e3
+
+    def declare(bodies):  # set-up, outside the timed region: uploads, allocations and a stream synchronise that differ between the legs
+        markers.update(vertices=vertices, velocities=velocities)
+        ibm.set_bodies(bodies)
+
+    def native(f_0, f_1, n):
+        out = ibm.run(f_0, f_1, bc_mask, missing_mask, omega, n, first_timestep=clock[0])
+        clock[0] += n
+        return out
+
+    def prescribed():
+        return [IBMBody(markers=slice(0, len(vertices)), motion=RigidMotion(centre=centre, axis=(0.0, 0.0, 1.0), rate=args.rate))]
+
+    def free():
+        # heavy enough for the loads not to matter within a round: it spins on at --rate as the prescribed sphere does
+        volume = 4.0 / 3.0 * np.pi * args.radius**3
+        dyn = RigidDynamics(mass=1e3 * volume, inertia=1e3 * 0.4 * volume * args.radius**2, centre=centre, angular_velocity=(0.0, 0.0, args.rate))
+        return [IBMBody(markers=slice(0, len(vertices)), dynamics=dyn)]
+
+    times = {"prescribed": [], "dynamics": []}
+    for bodies in (prescribed(), free()):
+        declare(bodies)
+        f_0, f_1 = native(f_0, f_1, args.warmup)
+    for r in range(args.rounds):  # interleaved, the order alternating: whatever state the machine is in is shared by the two
+        for name in (("prescribed", "dynamics") if r % 2 == 0 else ("dynamics", "prescribed")):
+            declare(prescribed() if name == "prescribed" else free())
+            (f_0, f_1), ms = timed(lambda: native(f_0, f_1, args.steps))
+            times[name].append(ms / args.steps)
+    pose = ibm.body_poses()[0]
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    spread = {k: float(np.max(v) - np.min(v)) for k, v in times.items()}
+    slots = int(ibm.ibm_footprint().size)
+    return {"dynamics": True, "markers": len(vertices), "rate": args.rate, "footprint_cells": slots, "ms_per_step": times, "median_prescribed": med["prescribed"],
+            "median_dynamics": med["dynamics"], "spread_prescribed": spread["prescribed"], "spread_dynamics": spread["dynamics"],
+            "dynamics_minus_prescribed_ms": med["dynamics"] - med["prescribed"], "counted": dynamics_counts(), "final_rate": float(pose[14]),
+            "finite": bool(np.isfinite(f_0.numpy()).all())}
 
 
 def bench_moving(args, ctx, ibm, make_fields, vertices, velocities, centre, omega):
@@ -131,11 +201,15 @@ def main():
     ap.add_argument("--trace-steps", type=int, default=0, help="only run this many IBM steps (for a profiler run)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--moving", action="store_true", help="the sphere spins about its own axis: host-driven loop against the native run")
+    ap.add_argument("--dynamics", action="store_true", help="the --moving sphere as a free body: native run against the prescribed native run")
     ap.add_argument("--rate", type=float, default=0.002, help="--moving: radians per step (surface speed = rate x radius)")
     ap.add_argument("--counted-only", action="store_true", help="--moving: print what is counted from the shapes and stop (no GPU needed)")
     ap.add_argument("--footprint-cells", type=int, default=43316, help="--counted-only: the footprint (profiles/ibm_coupling.md has the bench case's)")
     args = ap.parse_args()
 
+    if args.dynamics and args.counted_only:
+        print(json.dumps({"bodies": 1, "counted": dynamics_counts(), "counted_with_a_recorded_history": dynamics_counts(recorded=True)}))
+        return
     if args.moving and args.counted_only:
         subdivisions = 0
         while 4.0 * np.pi * args.radius**2 / (10 * 4**subdivisions + 2) > 1.0 and subdivisions < 7:
@@ -170,6 +244,13 @@ def main():
     ibm = IBMStepper(grid=grid, boundary_conditions=bcs, collision_type="KBC", ibm_max_iterations=args.sweeps, ibm_tolerance=0.0)
     f_0, f_1, bc_mask, missing_mask = ibm.prepare_fields()
     ibm.markers(vertices, areas, velocities)
+    if args.dynamics:
+        line = json.dumps(bench_dynamics(args, ctx, ibm, lambda: (f_0, f_1, bc_mask, missing_mask), vertices, velocities, centre, omega))
+        print(line)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     if args.moving:
         line = json.dumps(bench_moving(args, ctx, ibm, lambda: (f_0, f_1, bc_mask, missing_mask), vertices, velocities, centre, omega))
         print(line)

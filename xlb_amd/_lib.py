@@ -120,6 +120,10 @@ SIGNATURES = {
     "xlbhip_ibm_record_loads": [_p, _i64],
     "xlbhip_ibm_loads_history": [_p, _i64, _p],
     "xlbhip_ibm_download_markers": [_p, _i64, _p, _p],
+    "xlbhip_ibm_set_dynamics": [_p, _i, _p, _p, _p],
+    "xlbhip_ibm_body_poses": [_p, _i, _p, C.POINTER(C.c_uint64)],
+    "xlbhip_ibm_record_poses": [_p, _i64],
+    "xlbhip_ibm_poses_history": [_p, _i64, _p],
     "xlbhip_stats_create": [_p, _i, _i, _i, _i, _i, _i, _i, _p, _pp],
     "xlbhip_stats_destroy": [_p],
     "xlbhip_stats_sample": [_p, _p, _p],
@@ -708,6 +712,31 @@ class IBM:
     def loads_history(self, n_rows):
         out = np.zeros((int(n_rows), self.n_bodies, 6), np.float64)
         check(load().xlbhip_ibm_loads_history(self._h, int(n_rows), out.ctypes.data))
+        return out
+
+    DYN_PARAM_DOUBLES, DYN_STATE_DOUBLES = 32, 16  # IBM_DYN_PARAM_DOUBLES, IBM_DYN_STATE_DOUBLES of csrc/ibm_dynamics_kernels.hpp
+
+    def set_dynamics(self, rotate, params, state):
+        """Rotation modes (n_bodies,), parameters (n_bodies, 32) and initial state (n_bodies, 16) of the dynamic bodies."""
+        rotate = np.ascontiguousarray(rotate, np.int32)
+        params, state = np.ascontiguousarray(params, np.float64), np.ascontiguousarray(state, np.float64)
+        if rotate.shape != (self.n_bodies,) or params.shape != (self.n_bodies, self.DYN_PARAM_DOUBLES) or state.shape != (self.n_bodies, self.DYN_STATE_DOUBLES):
+            raise ValueError(f"set_dynamics: expected ({self.n_bodies},), ({self.n_bodies}, 32) and ({self.n_bodies}, 16) arrays")
+        check(load().xlbhip_ibm_set_dynamics(self._h, self.n_bodies, rotate.ctypes.data, params.ctypes.data, state.ctypes.data))
+
+    def body_poses(self):
+        """-> ((n_bodies, 18) poses the next step would read, the status word)."""
+        out = np.zeros((self.n_bodies, 18), np.float64)
+        status = C.c_uint64(0)
+        check(load().xlbhip_ibm_body_poses(self._h, self.n_bodies, out.ctypes.data, C.byref(status)))
+        return out, int(status.value)
+
+    def record_poses(self, n_rows):
+        check(load().xlbhip_ibm_record_poses(self._h, int(n_rows)))
+
+    def poses_history(self, n_rows):
+        out = np.zeros((int(n_rows), self.n_bodies, 18), np.float64)
+        check(load().xlbhip_ibm_poses_history(self._h, int(n_rows), out.ctypes.data))
         return out
 
     def download_markers(self, positions=True, velocities=True):

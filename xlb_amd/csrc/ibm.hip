@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "api_internal.hpp"
+#include "ibm_dynamics_kernels.hpp"
 #include "ibm_kernels.hpp"
 #include "ibm_motion_kernels.hpp"
 
@@ -59,6 +60,21 @@ struct xlbhip_ibm {
   DeviceBuf loads;    // double [n_bodies][6]
   DeviceBuf hist;     // double [hist_rows][n_bodies][6], row hist_next is the next step's
   int64_t hist_rows = 0, hist_next = 0;
+  // free bodies (xlbhip_ibm_set_dynamics): integrated on the device from the loads of every step (ibm_dynamics_kernels.hpp)
+  bool any_prescribed = false;  // some body with markers follows staged poses
+  bool any_dynamic = false;
+  bool dynamics_set = false;    // the parameters and the initial state of the dynamic bodies have been uploaded
+  DeviceBuf kind;        // int32 [n_bodies]: IBM_BODY_*
+  DeviceBuf rotate;      // int32 [n_bodies]: IBM_ROTATE_*
+  DeviceBuf dyn_state;   // double [n_bodies][16]
+  DeviceBuf dyn_params;  // double [n_bodies][32]
+  DeviceBuf status;      // uint64: bit b set = body b met a state that was not finite (sticky)
+  DeviceBuf live_pose;   // double [n_bodies][18]: what k_ibm_pose wrote for the step under way
+  DeviceBuf pose_hist;   // double [pose_hist_rows][n_bodies][18], row pose_hist_next is the next step's
+  int64_t pose_hist_rows = 0, pose_hist_next = 0;
+  // the move and the loads read the live table (else the staged / rest rows directly: the launches of a run without free bodies and
+  // without a recorded pose history are exactly those of a stepper that has neither)
+  bool use_live() const { return any_dynamic || pose_hist_rows > 0; }
   size_t csize() const { return cdt == XLBHIP_F32 ? 4 : 8; }
   size_t cells() const { return (size_t)nx * ny * nz; }
 };
@@ -188,17 +204,45 @@ static int ibm_couple(xlbhip_ibm* b, xlbhip_field* f) {
 }
 
 // ---- rigid bodies ---------------------------------------------------------------------------------------------------------------
-// the poses [body][18] the kernels of timestep t read: the rest poses while no body moves, else t's staged row (nullptr: not staged)
-static const double* ibm_pose_at(const xlbhip_ibm* b, int64_t t) {
-  if (!b->any_moving) return b->rest_pose.get<double>();
+// the staged row [body][18] of timestep t (nullptr: not staged)
+static const double* ibm_staged_at(const xlbhip_ibm* b, int64_t t) {
   if (t < b->pose_first || t >= b->pose_first + b->pose_count) return nullptr;
   return b->pose.get<double>() + (size_t)(t - b->pose_first) * b->n_bodies * IBM_POSE_DOUBLES;
 }
 
+// the poses [body][18] the move and the loads of timestep t read: the table k_ibm_pose has written for t when there is one, else the
+// rest poses while no body moves, else t's staged row
+static const double* ibm_pose_at(const xlbhip_ibm* b, int64_t t) {
+  if (b->use_live()) return b->live_pose.get<double>();
+  if (!b->any_prescribed) return b->rest_pose.get<double>();
+  return ibm_staged_at(b, t);
+}
+
+// staged rows are demanded only while some prescribed body moves
 static int ibm_require_poses(const xlbhip_ibm* b, int64_t t0, int64_t n) {
-  if (!b->any_moving) return 0;
+  XLB_REQUIRE(!b->any_dynamic || b->dynamics_set, "bodies are declared dynamic but their parameters and state were never set (xlbhip_ibm_set_dynamics)");
+  if (!b->any_prescribed) return 0;
   for (int64_t k = 0; k < n; ++k)
-    XLB_REQUIRE(ibm_pose_at(b, t0 + k), "the poses of the bodies at timestep %lld are not staged (xlbhip_ibm_stage_poses)", (long long)(t0 + k));
+    XLB_REQUIRE(ibm_staged_at(b, t0 + k), "the poses of the bodies at timestep %lld are not staged (xlbhip_ibm_stage_poses)", (long long)(t0 + k));
+  return 0;
+}
+
+// the live pose table of timestep t (and the next row of a recorded pose history); staged == nullptr outside a step
+static int ibm_live_pose(xlbhip_ibm* b, const double* staged, bool record) {
+  double* row = nullptr;
+  if (record && b->pose_hist_next < b->pose_hist_rows) row = b->pose_hist.get<double>() + (size_t)b->pose_hist_next++ * b->n_bodies * IBM_POSE_DOUBLES;
+  hipLaunchKernelGGL(k_ibm_pose, 1, IBM_MAX_BODIES, 0, b->ctx->stream, b->kind.get<int32_t>(), b->rotate.get<int32_t>(), b->dyn_state.get<double>(),
+                     b->dyn_params.get<double>(), staged, b->rest_pose.get<double>(), b->n_bodies, b->live_pose.get<double>(), row);
+  XLB_HIP(hipGetLastError());
+  return 0;
+}
+
+// the dynamic bodies from the state of timestep t to that of t + 1, with the loads the step has just left
+static int ibm_integrate(xlbhip_ibm* b) {
+  if (!b->any_dynamic) return 0;
+  hipLaunchKernelGGL(k_ibm_integrate, 1, IBM_MAX_BODIES, 0, b->ctx->stream, b->kind.get<int32_t>(), b->rotate.get<int32_t>(), b->dyn_params.get<double>(),
+                     b->loads.get<double>(), b->n_bodies, b->dyn_state.get<double>(), b->status.get<unsigned long long>());
+  XLB_HIP(hipGetLastError());
   return 0;
 }
 
@@ -341,10 +385,13 @@ int xlbhip_ibm_step(xlbhip_ibm* b, const xlbhip_field* f_src, xlbhip_field* f_ds
   if (int rc = ibm_check_field(b, f_src)) return rc;
   if (int rc = ibm_check_field(b, f_dst)) return rc;
   if (int rc = ibm_require_poses(b, timestep, 1)) return rc;
+  if (b->use_live())
+    if (int rc = ibm_live_pose(b, b->any_prescribed ? ibm_staged_at(b, timestep) : nullptr, true)) return rc;
   if (int rc = ibm_move(b, timestep)) return rc;
   if (int rc = xlbhip_step(b->stepper, f_src, f_dst, bc_mask, missing_mask, omega, timestep)) return rc;
   if (int rc = ibm_couple(b, f_dst)) return rc;
-  return ibm_body_loads(b, timestep);
+  if (int rc = ibm_body_loads(b, timestep)) return rc;
+  return ibm_integrate(b);
 }
 
 int xlbhip_ibm_run(xlbhip_ibm* b, xlbhip_field* f_a, xlbhip_field* f_b, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, double omega,
@@ -418,14 +465,21 @@ int xlbhip_ibm_set_bodies(xlbhip_ibm* b, int n_bodies, const int64_t* first, con
   b->any_moving = false;
   b->n_chunks = b->pose_count = 0;
   b->hist_rows = b->hist_next = 0;
+  b->pose_hist_rows = b->pose_hist_next = 0;
+  b->any_prescribed = b->any_dynamic = b->dynamics_set = false;
   if (n_bodies == 0) return 0;
+  for (int i = 0; i < n_bodies; ++i)
+    XLB_REQUIRE(moving[i] >= IBM_BODY_REST && moving[i] <= IBM_BODY_DYNAMIC, "body %d: bad moving flag %d (0 at rest, 1 prescribed, 2 dynamic)", i, moving[i]);
+  std::vector<int32_t> kind(moving, moving + n_bodies), rotate((size_t)n_bodies, IBM_ROTATE_LOCKED);
   std::vector<int32_t> move_id((size_t)b->n, -1), chunk0((size_t)n_bodies + 1, 0);
   std::vector<IbmLoadChunk> chunks;
   std::vector<double> rest((size_t)n_bodies * IBM_POSE_DOUBLES, 0.0);
-  bool any_moving = false;
+  bool any_moving = false, any_prescribed = false, any_dynamic = false;
   for (int i = 0; i < n_bodies; ++i) {
     if (moving[i]) {
       any_moving = any_moving || count[i] > 0;
+      any_prescribed = any_prescribed || (moving[i] == IBM_BODY_PRESCRIBED && count[i] > 0);
+      any_dynamic = any_dynamic || moving[i] == IBM_BODY_DYNAMIC;
       std::fill(move_id.begin() + first[i], move_id.begin() + first[i] + count[i], (int32_t)i);
     }
     chunk0[i] = (int32_t)chunks.size();
@@ -441,12 +495,23 @@ int xlbhip_ibm_set_bodies(xlbhip_ibm* b, int n_bodies, const int64_t* first, con
   if (int rc = upload_bytes(chunks.data(), chunks.size() * sizeof(IbmLoadChunk), b->chunks)) return rc;
   if (int rc = upload_bytes(centre0, (size_t)n_bodies * 3 * sizeof(double), b->centre0)) return rc;
   if (int rc = upload_bytes(rest.data(), rest.size() * sizeof(double), b->rest_pose)) return rc;
+  if (int rc = upload_bytes(kind.data(), kind.size() * sizeof(int32_t), b->kind)) return rc;
+  if (int rc = upload_bytes(rotate.data(), rotate.size() * sizeof(int32_t), b->rotate)) return rc;
+  XLB_HIP(b->live_pose.alloc((size_t)n_bodies * IBM_POSE_DOUBLES * sizeof(double)));
+  XLB_HIP(b->dyn_state.alloc((size_t)n_bodies * IBM_DYN_STATE_DOUBLES * sizeof(double)));
+  XLB_HIP(b->dyn_params.alloc((size_t)n_bodies * IBM_DYN_PARAM_DOUBLES * sizeof(double)));
+  if (!b->status) XLB_HIP(b->status.alloc(sizeof(unsigned long long)));
+  XLB_HIP(hipMemsetAsync(b->dyn_state.get(), 0, (size_t)n_bodies * IBM_DYN_STATE_DOUBLES * sizeof(double), c->stream));
+  XLB_HIP(hipMemsetAsync(b->dyn_params.get(), 0, (size_t)n_bodies * IBM_DYN_PARAM_DOUBLES * sizeof(double), c->stream));
+  XLB_HIP(hipMemsetAsync(b->status.get(), 0, sizeof(unsigned long long), c->stream));
   XLB_HIP(b->partial.alloc(std::max<size_t>(chunks.size(), 1) * 6 * sizeof(double)));
   XLB_HIP(b->loads.alloc((size_t)n_bodies * 6 * sizeof(double)));
   XLB_HIP(hipMemsetAsync(b->loads.get(), 0, (size_t)n_bodies * 6 * sizeof(double), c->stream));
-  if (any_moving) {
+  if (any_prescribed) {
     if (!b->pose) XLB_HIP(b->pose.alloc(XLBHIP_IBM_POSE_BYTES));
     if (!b->pose_pin) XLB_HIP(b->pose_pin.alloc(XLBHIP_IBM_POSE_BYTES));
+  }
+  if (any_moving) {
     if (!b->pos0_valid) {  // nothing has moved the markers since they were uploaded: `pos` holds the reference positions
       XLB_HIP(b->pos0.alloc((size_t)b->n * 3 * sizeof(float)));
       XLB_HIP(hipMemcpyAsync(b->pos0.get(), b->pos.get(), (size_t)b->n * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
@@ -455,13 +520,69 @@ int xlbhip_ibm_set_bodies(xlbhip_ibm* b, int n_bodies, const int64_t* first, con
   }
   b->n_bodies = n_bodies;
   b->any_moving = any_moving;
+  b->any_prescribed = any_prescribed;
+  b->any_dynamic = any_dynamic;
   b->n_chunks = (int64_t)chunks.size();
+  return 0;
+}
+
+int xlbhip_ibm_set_dynamics(xlbhip_ibm* b, int n_bodies, const int* rotate, const double* params, const double* state) {
+  XLB_REQUIRE(b && rotate && params && state, "null argument");
+  XLB_REQUIRE(n_bodies == b->n_bodies && n_bodies > 0, "xlbhip_ibm_set_dynamics: %d bodies, %d are declared (xlbhip_ibm_set_bodies)", n_bodies, b->n_bodies);
+  XLB_REQUIRE(b->any_dynamic, "xlbhip_ibm_set_dynamics: no body is declared dynamic (moving flag 2 of xlbhip_ibm_set_bodies)");
+  std::vector<int32_t> modes(rotate, rotate + n_bodies);
+  for (int i = 0; i < n_bodies; ++i)
+    XLB_REQUIRE(modes[i] >= IBM_ROTATE_LOCKED && modes[i] <= IBM_ROTATE_FREE, "body %d: bad rotation mode %d (0 locked, 1 axis, 2 free)", i, modes[i]);
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipStreamSynchronize(c->stream));  // queued steps read the tables replaced below
+  if (int rc = upload_bytes(modes.data(), modes.size() * sizeof(int32_t), b->rotate)) return rc;
+  if (int rc = upload_bytes(params, (size_t)n_bodies * IBM_DYN_PARAM_DOUBLES * sizeof(double), b->dyn_params)) return rc;
+  if (int rc = upload_bytes(state, (size_t)n_bodies * IBM_DYN_STATE_DOUBLES * sizeof(double), b->dyn_state)) return rc;
+  XLB_HIP(hipMemsetAsync(b->status.get(), 0, sizeof(unsigned long long), c->stream));
+  b->dynamics_set = true;
+  return 0;
+}
+
+int xlbhip_ibm_body_poses(xlbhip_ibm* b, int n_bodies, double* poses, uint64_t* status) {
+  XLB_REQUIRE(b && n_bodies == b->n_bodies && status && (n_bodies == 0 || poses), "xlbhip_ibm_body_poses: expected room for %d bodies", b ? b->n_bodies : 0);
+  *status = 0;
+  if (n_bodies == 0) return 0;
+  XLB_REQUIRE(!b->any_dynamic || b->dynamics_set, "bodies are declared dynamic but their parameters and state were never set (xlbhip_ibm_set_dynamics)");
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  if (int rc = ibm_live_pose(b, nullptr, false)) return rc;
+  XLB_HIP(hipMemcpyAsync(poses, b->live_pose.get(), (size_t)n_bodies * IBM_POSE_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  XLB_HIP(hipMemcpyAsync(status, b->status.get(), sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  XLB_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int xlbhip_ibm_record_poses(xlbhip_ibm* b, int64_t n_rows) {
+  XLB_REQUIRE(b && n_rows >= 0, "bad argument");
+  XLB_REQUIRE(n_rows == 0 || b->n_bodies > 0, "xlbhip_ibm_record_poses: no bodies are declared");
+  XLB_HIP(hipSetDevice(b->ctx->device));
+  b->pose_hist_rows = b->pose_hist_next = 0;
+  if (n_rows == 0) return 0;
+  XLB_HIP(b->pose_hist.alloc((size_t)n_rows * b->n_bodies * IBM_POSE_DOUBLES * sizeof(double)));
+  b->pose_hist_rows = n_rows;
+  return 0;
+}
+
+int xlbhip_ibm_poses_history(xlbhip_ibm* b, int64_t n_rows, double* poses) {
+  XLB_REQUIRE(b && n_rows >= 0 && (n_rows == 0 || poses), "bad argument");
+  XLB_REQUIRE(n_rows <= b->pose_hist_next, "xlbhip_ibm_poses_history: %lld rows asked for, %lld were recorded", (long long)n_rows, (long long)b->pose_hist_next);
+  if (n_rows == 0) return 0;
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipMemcpyAsync(poses, b->pose_hist.get(), (size_t)n_rows * b->n_bodies * IBM_POSE_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  XLB_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
 
 int xlbhip_ibm_stage_poses(xlbhip_ibm* b, int64_t first_timestep, int64_t n_steps, const double* poses) {
   XLB_REQUIRE(b && n_steps >= 0 && (n_steps == 0 || poses), "bad argument");
-  XLB_REQUIRE(b->any_moving, "xlbhip_ibm_stage_poses: no body moves (xlbhip_ibm_set_bodies)");
+  XLB_REQUIRE(b->any_prescribed, "xlbhip_ibm_stage_poses: no body with prescribed motion moves (xlbhip_ibm_set_bodies)");
   const size_t bytes = (size_t)n_steps * b->n_bodies * IBM_POSE_DOUBLES * sizeof(double);
   XLB_REQUIRE(bytes <= XLBHIP_IBM_POSE_BYTES, "%lld steps x %d bodies of poses are %zu bytes, at most %d are staged at once", (long long)n_steps, b->n_bodies,
               bytes, XLBHIP_IBM_POSE_BYTES);

@@ -5,7 +5,7 @@ that are about one cell apart.
 
 ``RigidMotion`` and ``IBMBody`` describe bodies with prescribed motion for ``IBMStepper.set_bodies`` (the reference's
 examples/ibm/wind_turbine_ibm.py:160-199 turns its rotor with a kernel of its own; here the host evaluates poses and the stepper's
-native code applies them)."""
+native code applies them).  ``RigidDynamics`` describes a free body, which the stepper's native code integrates from its loads."""
 
 import numpy as np
 
@@ -95,19 +95,169 @@ class RigidMotion:
         return R, self.centre + self.velocity * float(timestep), self.rate * self.axis, self.velocity.copy()
 
 
+def _finite(name, value, shape=None):
+    a = np.array(value, dtype=np.float64)
+    if shape is not None:
+        try:
+            a = np.broadcast_to(a, shape).copy()
+        except ValueError:
+            raise ValueError(f"RigidDynamics: {name} must have shape {shape}") from None
+    if not np.isfinite(a).all():
+        raise ValueError(f"RigidDynamics: {name} is not finite")
+    return a
+
+
+class RigidDynamics:
+    """A FREE rigid body: its pose is not prescribed but integrated on the device, once per step, from the force and the torque the
+    coupling has just found for it (``IBMBody(markers, dynamics=RigidDynamics(...))``).
+
+    ``mass``              the effective mass the integrator divides by (> 0)
+    ``inertia``           the effective inertia tensor in the BODY frame, 3 x 3 symmetric positive definite; a scalar: that multiple
+                          of the identity
+    ``centre, velocity``  position and velocity of the centre at timestep 0 (lattice units)
+    ``orientation``       3 x 3 rotation at timestep 0 (default: the identity)
+    ``angular_velocity``  at timestep 0, a world-frame vector in radians per step
+    ``force, torque``     constant external loads in the world frame (the buoyancy-corrected weight goes here)
+    ``spring``            (anchor, stiffness, damping): a linear tether that adds -stiffness (c - anchor) - damping v per axis;
+                          stiffness and damping are 3-vectors or scalars
+    ``translate``         which world axes the centre may move along
+    ``rotate``            "free" (3-D rotation), ("axis", a) (about the fixed world direction a through the centre: a free-spinning
+                          rotor) or "locked"
+
+    The scheme is explicit with dt = 1 (csrc/ibm_dynamics_kernels.hpp states it to the operation): symplectic Euler for the centre,
+    v' = v + F / mass, c' = c + v', and for the rotation L' = L + T, w* = R Ib^-1 R^T L', q' = normalise(cay(w*) q) with the Cayley
+    map in place of the exponential.  Explicit coupling of this kind is unstable for bodies about as light as the fluid; see
+    ``sphere``.  There are no contact or lubrication forces, and a body must stay two cells inside the box (no periodic wrap)."""
+
+    ROTATE_LOCKED, ROTATE_AXIS, ROTATE_FREE = 0, 1, 2
+
+    def __init__(self, mass, inertia, centre, velocity=(0.0, 0.0, 0.0), orientation=None, angular_velocity=(0.0, 0.0, 0.0), force=(0.0, 0.0, 0.0),
+                 torque=(0.0, 0.0, 0.0), spring=None, translate=(True, True, True), rotate="free"):
+        self.mass = float(_finite("mass", mass, ()))
+        if not self.mass > 0.0:
+            raise ValueError("RigidDynamics: mass must be positive")
+        inertia = _finite("inertia", inertia)
+        if inertia.ndim == 0:
+            inertia = float(inertia) * np.eye(3)
+        if inertia.shape != (3, 3) or not np.array_equal(inertia, inertia.T) or not (np.linalg.eigvalsh(inertia) > 0.0).all():
+            raise ValueError("RigidDynamics: inertia must be a positive scalar or a 3 x 3 symmetric positive definite tensor")
+        self.inertia = inertia
+        self.centre = _finite("centre", centre, (3,))
+        self.velocity = _finite("velocity", velocity, (3,))
+        self.orientation = np.eye(3) if orientation is None else _finite("orientation", orientation, (3, 3))
+        if np.abs(self.orientation.T @ self.orientation - np.eye(3)).max() > 1e-12 or np.linalg.det(self.orientation) < 0.0:
+            raise ValueError("RigidDynamics: orientation must be a rotation matrix")
+        self.angular_velocity = _finite("angular_velocity", angular_velocity, (3,))
+        self.force = _finite("force", force, (3,))
+        self.torque = _finite("torque", torque, (3,))
+        if spring is None:
+            self.anchor, self.stiffness, self.damping = np.zeros(3), np.zeros(3), np.zeros(3)
+        else:
+            try:
+                anchor, stiffness, damping = spring
+            except (TypeError, ValueError):
+                raise ValueError("RigidDynamics: spring must be (anchor, stiffness, damping)") from None
+            self.anchor = _finite("spring", anchor, (3,))
+            self.stiffness = _finite("spring", stiffness, (3,))
+            self.damping = _finite("spring", damping, (3,))
+        translate = np.array(translate, dtype=bool)
+        if translate.shape != (3,):
+            raise ValueError("RigidDynamics: translate must be three booleans")
+        self.translate = translate
+        self.axis = np.zeros(3)
+        if isinstance(rotate, str) and rotate in ("free", "locked"):
+            self.rotate = self.ROTATE_FREE if rotate == "free" else self.ROTATE_LOCKED
+        elif isinstance(rotate, (tuple, list)) and len(rotate) == 2 and rotate[0] == "axis":
+            axis = _finite("axis", rotate[1], (3,))
+            norm = float(np.sqrt((axis * axis).sum()))
+            if not norm > 0.0:
+                raise ValueError("RigidDynamics: the axis must not be zero")
+            self.axis = axis / norm
+            self.rotate = self.ROTATE_AXIS
+        else:
+            raise ValueError('RigidDynamics: rotate must be "free", "locked" or ("axis", a)')
+
+    @classmethod
+    def sphere(cls, radius, density, centre, gravity=(0.0, 0.0, 0.0), **kw):
+        """A homogeneous sphere of ``density`` (the fluid's is 1) under ``gravity``, with Uhlmann's (J. Comput. Phys. 209 (2005) 448)
+        effective quantities: the fluid inside the marker surface is forced too and moves with the body, which leaves
+        mass = (density - 1) V, inertia = (density - 1) 2/5 V r^2 and force = (density - 1) V g for the integrator.
+
+        density <= 1.2 is refused: with the effective mass tending to zero the explicit scheme is unstable below about that ratio
+        (Uhlmann reports the limit); lighter bodies need an implicit or a virtual-mass treatment, which this stepper does not have."""
+        radius, density = float(radius), float(density)
+        if not radius > 0.0 or not np.isfinite(radius):
+            raise ValueError("RigidDynamics.sphere: radius must be positive")
+        if not density > 1.2:
+            raise ValueError("RigidDynamics.sphere: density must exceed 1.2 (the explicit coupling is unstable for lighter bodies)")
+        volume = 4.0 / 3.0 * np.pi * radius**3
+        excess = (density - 1.0) * volume
+        g = _finite("gravity", gravity, (3,))
+        return cls(mass=excess, inertia=excess * 0.4 * radius * radius, centre=centre, force=excess * g, **kw)
+
+    uhlmann = sphere
+
+    @staticmethod
+    def _quaternion(R):
+        """Unit quaternion (w, x, y, z) of a rotation matrix (the branch with the largest pivot)."""
+        t = np.array([R[0, 0] + R[1, 1] + R[2, 2], R[0, 0] - R[1, 1] - R[2, 2], R[1, 1] - R[0, 0] - R[2, 2], R[2, 2] - R[0, 0] - R[1, 1]])
+        k = int(np.argmax(t))
+        r = np.sqrt(1.0 + t[k])
+        if k == 0:
+            q = np.array([r * r, R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+        elif k == 1:
+            q = np.array([R[2, 1] - R[1, 2], r * r, R[0, 1] + R[1, 0], R[0, 2] + R[2, 0]])
+        elif k == 2:
+            q = np.array([R[0, 2] - R[2, 0], R[0, 1] + R[1, 0], r * r, R[1, 2] + R[2, 1]])
+        else:
+            q = np.array([R[1, 0] - R[0, 1], R[0, 2] + R[2, 0], R[1, 2] + R[2, 1], r * r])
+        q = q / (2.0 * r)
+        return q / np.sqrt((q * q).sum())
+
+    def native(self):
+        """-> (rotation mode, 32 parameters, 16 doubles of initial state) as xlbhip_ibm_set_dynamics takes them: the host passes
+        1 / mass, Ib^-1, 1 / I_a with I_a = a^T R0 Ib R0^T a, and L(0) = R0 Ib R0^T w0 (axis mode: the rate a . w0)."""
+        R0 = self.orientation
+        world = R0 @ self.inertia @ R0.T
+        params = np.zeros(32)
+        params[0] = 1.0 / self.mass
+        params[1:4] = self.translate.astype(np.float64)
+        params[4:7], params[7:10] = self.force, self.torque
+        params[10:13], params[13:16], params[16:19] = self.anchor, self.stiffness, self.damping
+        params[19:28] = np.linalg.inv(self.inertia).reshape(9)
+        state = np.zeros(16)
+        state[0:3], state[3:6] = self.centre, self.velocity
+        state[6:10] = self._quaternion(R0)
+        if self.rotate == self.ROTATE_AXIS:
+            params[28:31] = self.axis
+            params[31] = 1.0 / float(self.axis @ world @ self.axis)
+            state[10] = float(self.axis @ self.angular_velocity)
+        elif self.rotate == self.ROTATE_FREE:
+            state[10:13] = world @ self.angular_velocity
+        return self.rotate, params, state
+
+
 class IBMBody:
     """A contiguous range of an IBMStepper's markers that moves as one rigid body.
 
-    ``markers``  slice(a, b) into the marker arrays (step 1)
-    ``motion``   a RigidMotion, any object with its ``at(timestep)``, or None for a body at rest (whose loads are still summed)
-    ``centre0``  the point the uploaded vertices refer to: marker k sits at c(t) + R(t) (X0_k - centre0).  Default: motion.at(0)[1],
-                 or the mean of the body's markers for a body at rest (there it is the point the torque is taken about)."""
+    ``markers``   slice(a, b) into the marker arrays (step 1)
+    ``motion``    a RigidMotion, any object with its ``at(timestep)``, or None
+    ``dynamics``  a RigidDynamics: the body is free, moved by the loads on it; not together with ``motion``.  With neither the body
+                  is at rest (its loads are still summed)
+    ``centre0``   the point the uploaded vertices refer to: marker k sits at c(t) + R(t) (X0_k - centre0).  Default: motion.at(0)[1],
+                  dynamics.centre, or the mean of the body's markers for a body at rest (there it is the point the torque is taken
+                  about)."""
 
-    def __init__(self, markers, motion=None, centre0=None):
+    def __init__(self, markers, motion=None, centre0=None, dynamics=None):
         if not isinstance(markers, slice):
             raise TypeError("IBMBody: markers must be a slice of the marker arrays")
+        if motion is not None and dynamics is not None:
+            raise TypeError("IBMBody: motion and dynamics are mutually exclusive")
         if motion is not None and not callable(getattr(motion, "at", None)):
             raise TypeError("IBMBody: motion must be None or have an at(timestep) method")
+        if dynamics is not None and not isinstance(dynamics, RigidDynamics):
+            raise TypeError("IBMBody: dynamics must be None or a RigidDynamics")
         self.markers = markers
         self.motion = motion
+        self.dynamics = dynamics
         self.centre0 = None if centre0 is None else np.array(centre0, dtype=np.float64).reshape(3)

@@ -2,4 +2,4 @@
 
 from .stepper import Stepper as Stepper
 from .nse_stepper import IncompressibleNavierStokesStepper as IncompressibleNavierStokesStepper
-from .ibm_stepper import IBMStepper as IBMStepper, IBMBody as IBMBody, RigidMotion as RigidMotion
+from .ibm_stepper import IBMStepper as IBMStepper, IBMBody as IBMBody, RigidMotion as RigidMotion, RigidDynamics as RigidDynamics

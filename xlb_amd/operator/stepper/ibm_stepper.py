@@ -32,7 +32,21 @@ The call with timestep t places marker k of body b at X_k(t) = c_b(t) + R_b(t) (
 U_k(t) = v_b(t) + w_b(t) x (X_k(t) - c_b(t)), where X0 are the vertices last uploaded (``markers.update(vertices=...)`` replaces
 them), c0_b is the body's ``centre0`` and (R, c, w, v) = ``motion.at(t)``.  The ``velocities`` uploaded for the markers of a moving
 body are IGNORED.  A body with ``motion=None`` is at rest; markers in no body stay as uploaded.  ``body_loads()`` is the force and
-the torque on every body in the last call.  Free (force-driven) rigid-body dynamics are out of scope: the motion is prescribed.
+the torque on every body in the last call.
+
+Free bodies.  ``IBMBody(markers=..., dynamics=RigidDynamics(mass, inertia, centre, ...))`` declares a body whose motion is NOT
+prescribed: after the loads of every step one tiny kernel advances its centre, velocity, orientation and angular momentum from
+them (explicit, dt = 1; helper/ibm_helper.py and csrc/ibm_dynamics_kernels.hpp state the scheme), and the next step's move reads
+the new pose — a settling particle, a sphere on an elastic mount, a rotor the flow spins up.  The state lives on the device: a
+``run`` with free bodies and no prescribed mover is ONE native call with no pose staging, and nothing in it waits for the device or
+reads from it.  Free, prescribed and resting bodies mix in one ``set_bodies``; a new ``set_bodies`` resets the state to the declared
+initial values.  ``body_poses()`` is the pose (R | c | w | v, 18 doubles per body) the next call will use;
+``run(..., record_poses=True)`` also returns the poses every step used, row for row with ``record_loads``.  A body whose new state
+is not finite stops where it is and ``body_poses()`` raises, naming it.  The integration is explicit: ``set_bodies`` warns
+(RuntimeWarning) when a free body's mass is below ibm_max_iterations x the sum of its markers' areas, the added mass the coupling
+can load it with, beyond which the scheme diverges unless the sweeps end early.  Not covered: contact or lubrication forces between bodies
+or with walls; a body crossing a periodic face (the coupling does not wrap: keep bodies two cells inside the box); density ratios
+at or below about 1.2, which need an implicit or virtual-mass treatment; deformable bodies.
 
 The host evaluates the poses (18 doubles per step and body) and stages them ahead of the steps, as it does for time-dependent
 walls: ``run`` works in chunks of at most POSE_CHUNK_STEPS = 256 steps and at most 1 MiB of poses (113 steps with 64 bodies); the
@@ -40,10 +54,12 @@ poses of the next chunk are evaluated while the device runs the current one, and
 
 3-D lattices, fp32 / fp64 storage, one rank."""
 
+import warnings
+
 import numpy as np
 
 from ... import _lib
-from ...helper.ibm_helper import IBMBody, RigidMotion  # noqa: F401  (re-exported: they are this stepper's vocabulary)
+from ...helper.ibm_helper import IBMBody, RigidDynamics, RigidMotion  # noqa: F401  (re-exported: they are this stepper's vocabulary)
 from ...compute_backend import ComputeBackend
 from ...precision_policy import Precision
 from ..operator import Operator
@@ -55,6 +71,7 @@ class IBMMarkers:
 
     def __init__(self, stepper):
         self._stepper = stepper
+        self._areas = None  # host copy of the areas last uploaded (set_bodies checks the mass of free bodies against them)
 
     def __len__(self):
         return self._stepper._ibm_native().n
@@ -65,6 +82,8 @@ class IBMMarkers:
         given = [a for a in (vertices, areas, velocities) if a is not None]
         n = len(given[0]) if given else len(self)
         self._stepper._ibm_native().set_markers(n, vertices, areas, velocities)
+        if areas is not None:
+            self._areas = np.array(areas, dtype=np.float32).reshape(-1)
         return self
 
     def positions(self):
@@ -112,7 +131,9 @@ class IBMStepper(IncompressibleNavierStokesStepper):
             raise ValueError("ibm_tolerance must not be negative")
         self._ibm = None
         self._bodies = []
-        self._any_moving = False
+        self._any_moving = False  # some body with markers follows a prescribed motion: its poses are staged
+        self._any_dynamic = False
+        self._next_timestep = 0
         self._markers = IBMMarkers(self)
         self.s_lagr_forces = LagrangianForces(self)
 
@@ -169,16 +190,46 @@ class IBMStepper(IncompressibleNavierStokesStepper):
                 centre0[i] = body.centre0
             elif body.motion is not None:
                 centre0[i] = np.asarray(body.motion.at(0)[1], dtype=np.float64)
+            elif body.dynamics is not None:
+                centre0[i] = body.dynamics.centre
             elif b > a:
                 uploaded = self._markers.positions() if uploaded is None else uploaded
                 centre0[i] = uploaded[a:b].astype(np.float64).mean(axis=0)
-        ibm.set_bodies([a for a, _ in ranges], [b - a for a, b in ranges], [body.motion is not None for body in bodies], centre0)
+        kinds = [2 if body.dynamics is not None else int(body.motion is not None) for body in bodies]  # 0 at rest, 1 prescribed, 2 dynamic
+        ibm.set_bodies([a for a, _ in ranges], [b - a for a, b in ranges], kinds, centre0)
+        self._any_dynamic = 2 in kinds
+        if self._any_dynamic:
+            self._warn_light_bodies(bodies, ranges)
+            rotate, params, state = np.zeros(len(bodies), np.int32), np.zeros((len(bodies), 32)), np.zeros((len(bodies), 16))
+            for i, body in enumerate(bodies):
+                if body.dynamics is not None:
+                    rotate[i], params[i], state[i] = body.dynamics.native()
+            ibm.set_dynamics(rotate, params, state)
         self._bodies = bodies
         self._body_centre0 = centre0
+        self._next_timestep = 0  # (body_poses: a new declaration starts over, for prescribed bodies as for free ones)
         self._any_moving = any(body.motion is not None and b > a for body, (a, b) in zip(bodies, ranges))
 
+    def _warn_light_bodies(self, bodies, ranges):
+        """The marker force is the velocity deficit added up over the sweeps that ran, so a body that starts to move drags an added
+        mass of up to ibm_max_iterations x (sum of its markers' areas) along; the explicit integrator diverges when that exceeds
+        the body's mass.  Say so when the body is declared, not when its state has stopped being finite."""
+        areas = self._markers._areas
+        if areas is None:
+            return
+        for i, (body, (a, b)) in enumerate(zip(bodies, ranges)):
+            dyn = body.dynamics
+            if dyn is None or not dyn.translate.any():
+                continue
+            added = self.ibm_max_iterations * float(areas[a:b].astype(np.float64).sum())
+            if dyn.mass < added:
+                warnings.warn(f"set_bodies: body {i}: mass {dyn.mass:.4g} is below ibm_max_iterations x sum of marker areas = {added:.4g}, the added mass the "
+                              "coupling can load it with; the explicit integration of this body is unstable unless the sweeps end early "
+                              "(heavier body, fewer sweeps, or a smaller ibm_relaxation)", RuntimeWarning, stacklevel=3)
+
     def _poses(self, t_first, n):
-        """(n, n_bodies, 18) float64: R (row-major) | c | w | v of every body at t_first .. t_first + n - 1."""
+        """(n, n_bodies, 18) float64: R (row-major) | c | w | v of every body at t_first .. t_first + n - 1 (the rest pose for a
+        dynamic body, whose row the device ignores)."""
         out = np.zeros((n, len(self._bodies), 18))
         for i, body in enumerate(self._bodies):
             if body.motion is None:
@@ -200,6 +251,23 @@ class IBMStepper(IncompressibleNavierStokesStepper):
         columns 3-5 the torque on it about the body's centre c_b at that step, -sum_k A_k (X_k - c_b) x F_k."""
         return self._ibm_native().loads()
 
+    def body_poses(self):
+        """(n_bodies, 18) float64, R (row-major) | c | w | v of every body as the NEXT call will use it, read from the device now: the
+        integrated state of a free body, ``motion.at`` of the timestep after the last call's for a prescribed one, the rest pose
+        otherwise.  Raises RuntimeError naming the free bodies that met a state that was not finite (they have stood still since)."""
+        if not self._bodies:
+            return np.zeros((0, 18))
+        poses, status = self._ibm_native().body_poses()
+        if status:
+            bad = [i for i in range(len(self._bodies)) if status >> i & 1]
+            raise RuntimeError(f"body_poses: the state of bodies {bad} stopped being finite (loads too large for the explicit integrator?)")
+        if self._any_moving:
+            staged = self._poses(self._next_timestep, 1)[0]
+            for i, body in enumerate(self._bodies):
+                if body.motion is not None:
+                    poses[i] = staged[i]
+        return poses
+
     @Operator.register_backend(ComputeBackend.HIP)
     def hip_implementation(self, f_0, f_1, vertices, areas, velocities, bc_mask, missing_mask, omega, timestep):
         self._set_markers(vertices, areas, velocities)
@@ -207,43 +275,56 @@ class IBMStepper(IncompressibleNavierStokesStepper):
         if self._any_moving:
             self._ibm_native().stage_poses(timestep, self._poses(timestep, 1))
         self._ibm_native().step(f_0, f_1, bc_mask, missing_mask, omega, timestep)
+        self._next_timestep = int(timestep) + 1
         return f_0, f_1, self.s_lagr_forces
 
-    def run(self, f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep=0, record_loads=False):
-        """``n_steps`` x (move the bodies, step with the coupling, loads, swap) in native code; returns (f_current, f_other), and with
-        ``record_loads`` also the loads of every step, (n_steps, n_bodies, 6), written on the device and read once after the run."""
+    def run(self, f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep=0, record_loads=False, record_poses=False):
+        """``n_steps`` x (move the bodies, step with the coupling, loads, integrate the free bodies, swap) in native code; returns
+        (f_current, f_other), with ``record_loads`` also the loads of every step, (n_steps, n_bodies, 6), and with ``record_poses``
+        also the poses every step's move and loads read, (n_steps, n_bodies, 18) — in that order; both are written on the device and
+        read once after the run."""
         ibm = self._ibm_native()
         n_steps, first_timestep = int(n_steps), int(first_timestep)
         record = bool(record_loads) and len(self._bodies) > 0 and n_steps > 0
         if record:
             ibm.record_loads(n_steps)
+        record_p = bool(record_poses) and len(self._bodies) > 0 and n_steps > 0
+        if record_p:
+            ibm.record_poses(n_steps)
         cur, oth = f_0, f_1
-        if self._time_dependent_bcs():
-            for k in range(n_steps):
-                self._stage(first_timestep + k, 1)
-                if self._any_moving:
-                    ibm.stage_poses(first_timestep + k, self._poses(first_timestep + k, 1))
-                ibm.step(cur, oth, bc_mask, missing_mask, omega, first_timestep + k)
-                cur, oth = oth, cur
-        elif self._any_moving:
-            chunk, done = self._pose_chunk(), 0
-            poses = self._poses(first_timestep, min(chunk, n_steps))
-            while done < n_steps:
-                m = len(poses)
-                ibm.stage_poses(first_timestep + done, poses)
-                if ibm.run(cur, oth, bc_mask, missing_mask, omega, first_timestep + done, m):
+        try:
+            if self._time_dependent_bcs():
+                for k in range(n_steps):
+                    self._stage(first_timestep + k, 1)
+                    if self._any_moving:
+                        ibm.stage_poses(first_timestep + k, self._poses(first_timestep + k, 1))
+                    ibm.step(cur, oth, bc_mask, missing_mask, omega, first_timestep + k)
                     cur, oth = oth, cur
-                done += m
-                if done < n_steps:  # (the device is busy with the chunk just enqueued)
-                    poses = self._poses(first_timestep + done, min(chunk, n_steps - done))
-        elif ibm.run(f_0, f_1, bc_mask, missing_mask, omega, first_timestep, n_steps):
-            cur, oth = f_1, f_0
-        if not record_loads:
-            return cur, oth
-        history = ibm.loads_history(n_steps) if record else np.zeros((n_steps, len(self._bodies), 6))
-        if record:
-            ibm.record_loads(0)
-        return cur, oth, history
+            elif self._any_moving:
+                chunk, done = self._pose_chunk(), 0
+                poses = self._poses(first_timestep, min(chunk, n_steps))
+                while done < n_steps:
+                    m = len(poses)
+                    ibm.stage_poses(first_timestep + done, poses)
+                    if ibm.run(cur, oth, bc_mask, missing_mask, omega, first_timestep + done, m):
+                        cur, oth = oth, cur
+                    done += m
+                    if done < n_steps:  # (the device is busy with the chunk just enqueued)
+                        poses = self._poses(first_timestep + done, min(chunk, n_steps - done))
+            elif ibm.run(f_0, f_1, bc_mask, missing_mask, omega, first_timestep, n_steps):
+                cur, oth = f_1, f_0
+            self._next_timestep = first_timestep + n_steps
+            out = (cur, oth)
+            if record_loads:
+                out += (ibm.loads_history(n_steps) if record else np.zeros((n_steps, len(self._bodies), 6)),)
+            if record_poses:
+                out += (ibm.poses_history(n_steps) if record_p else np.zeros((n_steps, len(self._bodies), 18)),)
+        finally:  # also when a step was refused: a recording left on would add launches to every later run
+            if record:
+                ibm.record_loads(0)
+            if record_p:
+                ibm.record_poses(0)
+        return out
 
     def run_timed(self, f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep=0):
         """As :meth:`run`; also returns the wall-clock milliseconds between two synchronisations."""
