@@ -8,6 +8,7 @@ of --every steps is ONE native call with the poses recorded on the device.  Prin
 against time.
 
     python examples/settling_sphere_ibm_hip.py [--size 32] [--steps 60] [--every 5] [--density 8] [--gravity 2e-4] [--sweeps 2]
+    python examples/settling_sphere_ibm_hip.py --size 24 --density 1.15 --virtual-mass 8 --floor --drop 1.1 --gravity 2e-3 --steps 10000 --every 500
 
 The defaults run in seconds.  The coupling is explicit, so the body must be heavy against the fluid it drags along: the marker force
 of IBMStepper is the velocity deficit added up over the sweeps that ran, an added mass of about sweeps x (marker area) that has to
@@ -17,10 +18,13 @@ stay below the effective mass (density - 1) x volume.  Density 8 with 2 sweeps s
 For a validation run, ten Cate et al. (Phys. Fluids 14 (2002) 4012) measured a nylon sphere, d = 15 mm, rho_p = 1120 kg/m^3, settling
 in silicone oil in a 100 x 100 x 160 mm box from 120 mm above the bottom: case E1 rho_f = 970, mu = 0.373 Pa s, Re = 1.5,
 u_inf = 0.038 m/s; E2 965 / 0.212 / 4.1 / 0.060; E3 962 / 0.113 / 11.6 / 0.091; E4 960 / 0.058 / 31.9 / 0.128.  Their density ratios
-are 1.15 .. 1.17 — BELOW what this explicit scheme takes (RigidDynamics.sphere refuses ratios up to 1.2), so these cases need the
-implicit or virtual-mass treatment this stepper does not have; a heavier sphere at the same Reynolds number is what can be run today,
-e.g. --size 100 (d = 15 cells) --density 8 with --gravity and --viscosity chosen for the Reynolds number wanted.  The box is closed by
-bounce-back walls; there is no contact force, so stop before the sphere comes within two cells of the bottom."""
+are 1.15 .. 1.17 — BELOW what the explicit scheme alone takes (RigidDynamics.sphere refuses ratios up to 1.2 without a virtual
+mass).  --virtual-mass C_v adds the virtual-mass term of Schwarz, Kempe and Froehlich (J. Comput. Phys. 281 (2015) 591), C_v x the
+displaced mass, with which such a sphere runs (C_v = 8 in the second line above); nobody has compared a run with their curves yet,
+so this example is a demonstration and not a validation.  The box is closed by bounce-back walls.  Without --floor there is no
+contact force and the run stops before the sphere comes within two cells of the bottom; with --floor a plane three cells above the
+bottom repels the sphere (IBMStepper.set_contact: range 1 cell, wall stiffness --stiffness) and it comes to rest on it, still one
+native call per block of steps.  --drop H starts the sphere with its lowest point H cells above that plane."""
 
 import argparse
 import os
@@ -47,6 +51,10 @@ ap.add_argument("--gravity", type=float, default=2e-4, help="lattice units, alon
 ap.add_argument("--viscosity", type=float, default=1.0 / 6.0, help="lattice units (1/6: omega = 1)")
 ap.add_argument("--sweeps", type=int, default=2, help="ibm_max_iterations")
 ap.add_argument("--relaxation", type=float, default=0.5)
+ap.add_argument("--virtual-mass", type=float, default=0.0, help="virtual-mass coefficient C_v (0: none); lets --density go down to just above 1")
+ap.add_argument("--floor", action="store_true", help="a contact plane three cells above the bottom that the sphere lands on")
+ap.add_argument("--stiffness", type=float, default=1.0, help="wall stiffness of the floor's contact force")
+ap.add_argument("--drop", type=float, default=None, help="start with the sphere's lowest point this far above the floor plane")
 args = ap.parse_args()
 
 policy = PrecisionPolicy.FP32FP32
@@ -61,6 +69,9 @@ walls = np.unique(np.array(walls), axis=-1).tolist()
 
 radius = 0.15 * args.size
 centre = np.array([args.size / 2 + 0.3, args.size / 2 + 0.2, shape[2] - 2.0 * radius - 3.0])  # off the lattice on purpose
+FLOOR, RANGE = 3.0, 1.0  # the plane keeps the markers' supports (two cells) above the wall cells
+if args.drop is not None:
+    centre[2] = FLOOR + radius + args.drop
 subdivisions = 0
 while 4.0 * np.pi * radius**2 / (10 * 4**subdivisions + 2) > 1.0 and subdivisions < 7:
     subdivisions += 1
@@ -72,8 +83,12 @@ stepper = IBMStepper(grid=grid, boundary_conditions=[FullwayBounceBackBC(indices
                      ibm_tolerance=0.0, ibm_relaxation=args.relaxation)
 f_0, f_1, bc_mask, missing_mask = stepper.prepare_fields()
 stepper.markers(vertices, areas, np.zeros_like(vertices))
-body = RigidDynamics.sphere(radius, args.density, centre, gravity=(0.0, 0.0, -args.gravity), rotate="locked")
-stepper.set_bodies([IBMBody(markers=slice(0, len(vertices)), dynamics=body)])
+body = RigidDynamics.sphere(radius, args.density, centre, gravity=(0.0, 0.0, -args.gravity), rotate="locked", virtual_mass_coefficient=args.virtual_mass)
+if args.floor:
+    weight = -float(body.force[2])
+    assert args.stiffness * RANGE**2 > weight, f"--stiffness {args.stiffness} cannot carry the weight {weight:.4g} within the range {RANGE}"
+    stepper.set_contact(RANGE, args.stiffness, box=((-np.inf, -np.inf, FLOOR), (np.inf, np.inf, np.inf)))
+stepper.set_bodies([IBMBody(markers=slice(0, len(vertices)), dynamics=body, contact_radius=radius if args.floor else None)])
 omega = 1.0 / (3.0 * args.viscosity + 0.5)
 print(f"box {shape}, sphere radius {radius:.2f} ({len(vertices)} markers) at {centre}, density {args.density}, effective mass {body.mass:.1f}, "
       f"added mass of the coupling about {args.sweeps * float(areas.sum()):.1f}, gravity {args.gravity}, omega {omega:.4f}")
@@ -88,9 +103,12 @@ while done < args.steps:
     done += n
     pose = stepper.body_poses()[0]  # (raises if the state stopped being finite)
     print(f"step {done:6d}  c_z {pose[11]:.6f}  v_z {pose[17]:.6e}")
-    if pose[11] - radius < 4.0:
+    if not args.floor and pose[11] - radius < 4.0:
         print("the sphere is within two cells of the bottom (there is no contact force): stopping")
         break
 ctx.sync()
 print(f"{done} steps in {time.perf_counter() - t0:.2f} s; free fall without fluid would have reached v_z = {-args.gravity * done:.6e}")
 assert np.isfinite(f_0.numpy()).all()
+if args.floor:
+    gap, lift = pose[11] - radius - FLOOR, stepper.body_contact_forces()[0, 2]
+    print(f"gap above the floor plane {gap:.6f} (contact range {RANGE}), contact force {lift:.6e} against the weight {weight:.6e}, v_z {pose[17]:.6e}")

@@ -408,6 +408,30 @@ int xlbhip_ibm_body_poses(xlbhip_ibm* ibm, int n_bodies, double* poses, uint64_t
 int xlbhip_ibm_record_poses(xlbhip_ibm* ibm, int64_t n_rows);
 int xlbhip_ibm_poses_history(xlbhip_ibm* ibm, int64_t n_rows, double* poses);
 
+/* -- virtual mass and contact forces of the free bodies --
+ * No counterpart in the reference.  Both are opt-in and evaluated inside the integrator's launch (csrc/ibm_dynamics_kernels.hpp
+ * states every operation); a stepper that switches neither on enqueues exactly the launches it did without them.  All three are
+ * called after xlbhip_ibm_set_dynamics; xlbhip_ibm_set_bodies and xlbhip_ibm_set_dynamics switch both off again.
+ *
+ * _set_virtual_mass: per declared body (entries of bodies that are not dynamic are ignored) the virtual mass m_v and the virtual
+ * inertia I_v (added as I_v E to the body-frame inertia), finite and >= 0, after Schwarz, Kempe & Froehlich, J. Comput. Phys. 281
+ * (2015) 591: a = (F + m_v a_prev) / (mass + m_v), T' = T + I_v alpha_prev, with the acceleration and the change of the angular
+ * velocity of the PREVIOUS step, which the device keeps (6 doubles per body, zeroed by this call and by _set_dynamics).  The caller
+ * has put 1 / (mass + m_v), the inverse of (Ib + I_v E) and 1 / (I_a + I_v) into slots 0, 19-27 and 31 of the parameters of
+ * _set_dynamics, and the angular momentum of that inertia into the state.  Waits for the stream (set-up call). */
+int xlbhip_ibm_set_virtual_mass(xlbhip_ibm* ibm, int n_bodies, const double* virtual_mass, const double* virtual_inertia);
+/* _set_contact: a central repulsive force on every dynamic body i with radius[i] > 0 (0: the body does not take part), from the
+ * centres of the step's poses: k (range - gap)^2 (c_i - c_j) / d against every other body j with a radius — prescribed bodies and
+ * bodies at rest are obstacles — while gap = d - (r_i + r_j) < range and d > 0, and kw (range - gap)^2 along +a (-a) from the plane
+ * x_a = lo[a] (hi[a]) while gap = |c_a - plane| - r_i < range.  lo / hi: 3 doubles each, -inf / +inf switch a plane off, NULL all
+ * three; lo[a] < hi[a].  radius, range, stiffness and wall_stiffness are finite and >= 0.  The force enters the integrator's F and
+ * not the loads, which stay hydrodynamic; it exerts no torque.  With no radius above zero contact is off.  Waits for the stream. */
+int xlbhip_ibm_set_contact(xlbhip_ibm* ibm, int n_bodies, const double* radius, double range, double stiffness, double wall_stiffness,
+                           const double* lo, const double* hi);
+/* the contact force on every body in the last step, [n_bodies][3] (zero before the first step, for bodies that are not dynamic or
+ * have no radius, and while contact is off).  Synchronous. */
+int xlbhip_ibm_contact_forces(xlbhip_ibm* ibm, int n_bodies, double* forces);
+
 /* ---- flow statistics ------------------------------------------------------- */
 /* No counterpart in the reference: its drivers copy whole fields to the host and reduce them in NumPy (e.g.
  * examples/cfd/turbulent_channel_3d.py).  The object keeps running fp64 sums on the device of, per sampled cell: 1 (count), rho,

@@ -124,6 +124,9 @@ SIGNATURES = {
     "xlbhip_ibm_body_poses": [_p, _i, _p, C.POINTER(C.c_uint64)],
     "xlbhip_ibm_record_poses": [_p, _i64],
     "xlbhip_ibm_poses_history": [_p, _i64, _p],
+    "xlbhip_ibm_set_virtual_mass": [_p, _i, _p, _p],
+    "xlbhip_ibm_set_contact": [_p, _i, _p, _d, _d, _d, _p, _p],
+    "xlbhip_ibm_contact_forces": [_p, _i, _p],
     "xlbhip_stats_create": [_p, _i, _i, _i, _i, _i, _i, _i, _p, _pp],
     "xlbhip_stats_destroy": [_p],
     "xlbhip_stats_sample": [_p, _p, _p],
@@ -737,6 +740,28 @@ class IBM:
     def poses_history(self, n_rows):
         out = np.zeros((int(n_rows), self.n_bodies, 18), np.float64)
         check(load().xlbhip_ibm_poses_history(self._h, int(n_rows), out.ctypes.data))
+        return out
+
+    def set_virtual_mass(self, virtual_mass, virtual_inertia):
+        """m_v and I_v of every body, (n_bodies,) each; after set_dynamics."""
+        mv, iv = np.ascontiguousarray(virtual_mass, np.float64), np.ascontiguousarray(virtual_inertia, np.float64)
+        if mv.shape != (self.n_bodies,) or iv.shape != (self.n_bodies,):
+            raise ValueError(f"set_virtual_mass: expected two ({self.n_bodies},) arrays")
+        check(load().xlbhip_ibm_set_virtual_mass(self._h, self.n_bodies, mv.ctypes.data, iv.ctypes.data))
+
+    def set_contact(self, radius, range, stiffness, wall_stiffness, lo=None, hi=None):
+        """Contact radii (n_bodies,), 0 = the body takes no part; the model's range and stiffnesses; planes lo / hi (3,) or None."""
+        radius = np.ascontiguousarray(radius, np.float64)
+        if radius.shape != (self.n_bodies,):
+            raise ValueError(f"set_contact: expected ({self.n_bodies},) radii")
+        lo = None if lo is None else np.ascontiguousarray(lo, np.float64).reshape(3)
+        hi = None if hi is None else np.ascontiguousarray(hi, np.float64).reshape(3)
+        check(load().xlbhip_ibm_set_contact(self._h, self.n_bodies, radius.ctypes.data, float(range), float(stiffness), float(wall_stiffness),
+                                            None if lo is None else lo.ctypes.data, None if hi is None else hi.ctypes.data))
+
+    def contact_forces(self):
+        out = np.zeros((self.n_bodies, 3), np.float64)
+        check(load().xlbhip_ibm_contact_forces(self._h, self.n_bodies, out.ctypes.data))
         return out
 
     def download_markers(self, positions=True, velocities=True):

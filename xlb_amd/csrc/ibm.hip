@@ -1,6 +1,7 @@
 // libxlbhip: the immersed-boundary stepper (reference: xlb/operator/stepper/ibm_stepper.py).  One call = the ordinary step of a
 // stepper, then the coupling of ibm_kernels.hpp on the field the step wrote.  The object owns the markers, their footprint and the
 // per-footprint-cell scratch; everything it enqueues goes to the context's compute stream and nothing in a call waits for the device.
+#include <cmath>
 #include <cstddef>
 #include <cstring>
 #include <memory>
@@ -72,6 +73,14 @@ struct xlbhip_ibm {
   DeviceBuf live_pose;   // double [n_bodies][18]: what k_ibm_pose wrote for the step under way
   DeviceBuf pose_hist;   // double [pose_hist_rows][n_bodies][18], row pose_hist_next is the next step's
   int64_t pose_hist_rows = 0, pose_hist_next = 0;
+  // virtual mass and contact (xlbhip_ibm_set_virtual_mass / _set_contact): with either on, k_ibm_integrate_contact takes the place of
+  // k_ibm_integrate; with neither the launches are those of a stepper that has neither
+  bool virtual_on = false, contact_on = false;
+  DeviceBuf virt;      // double [n_bodies][2]: m_v, I_v
+  DeviceBuf prev;      // double [n_bodies][6]: a_prev | alpha_prev
+  DeviceBuf radius;    // double [n_bodies]: contact radius, 0 = takes no part
+  DeviceBuf contact;   // double [n_bodies][3]: the contact force of the last step
+  IbmContactModel contact_model{};
   // the move and the loads read the live table (else the staged / rest rows directly: the launches of a run without free bodies and
   // without a recorded pose history are exactly those of a stepper that has neither)
   bool use_live() const { return any_dynamic || pose_hist_rows > 0; }
@@ -240,6 +249,14 @@ static int ibm_live_pose(xlbhip_ibm* b, const double* staged, bool record) {
 // the dynamic bodies from the state of timestep t to that of t + 1, with the loads the step has just left
 static int ibm_integrate(xlbhip_ibm* b) {
   if (!b->any_dynamic) return 0;
+  if (b->virtual_on || b->contact_on) {
+    hipLaunchKernelGGL(k_ibm_integrate_contact, 1, IBM_MAX_BODIES, 0, b->ctx->stream, b->kind.get<int32_t>(), b->rotate.get<int32_t>(),
+                       b->dyn_params.get<double>(), b->loads.get<double>(), b->n_bodies, b->dyn_state.get<double>(), b->status.get<unsigned long long>(),
+                       b->virt.get<double>(), b->prev.get<double>(), b->contact_on ? b->radius.get<double>() : nullptr, b->contact_model,
+                       b->live_pose.get<double>(), b->contact.get<double>());
+    XLB_HIP(hipGetLastError());
+    return 0;
+  }
   hipLaunchKernelGGL(k_ibm_integrate, 1, IBM_MAX_BODIES, 0, b->ctx->stream, b->kind.get<int32_t>(), b->rotate.get<int32_t>(), b->dyn_params.get<double>(),
                      b->loads.get<double>(), b->n_bodies, b->dyn_state.get<double>(), b->status.get<unsigned long long>());
   XLB_HIP(hipGetLastError());
@@ -467,6 +484,7 @@ int xlbhip_ibm_set_bodies(xlbhip_ibm* b, int n_bodies, const int64_t* first, con
   b->hist_rows = b->hist_next = 0;
   b->pose_hist_rows = b->pose_hist_next = 0;
   b->any_prescribed = b->any_dynamic = b->dynamics_set = false;
+  b->virtual_on = b->contact_on = false;
   if (n_bodies == 0) return 0;
   for (int i = 0; i < n_bodies; ++i)
     XLB_REQUIRE(moving[i] >= IBM_BODY_REST && moving[i] <= IBM_BODY_DYNAMIC, "body %d: bad moving flag %d (0 at rest, 1 prescribed, 2 dynamic)", i, moving[i]);
@@ -504,6 +522,14 @@ int xlbhip_ibm_set_bodies(xlbhip_ibm* b, int n_bodies, const int64_t* first, con
   XLB_HIP(hipMemsetAsync(b->dyn_state.get(), 0, (size_t)n_bodies * IBM_DYN_STATE_DOUBLES * sizeof(double), c->stream));
   XLB_HIP(hipMemsetAsync(b->dyn_params.get(), 0, (size_t)n_bodies * IBM_DYN_PARAM_DOUBLES * sizeof(double), c->stream));
   XLB_HIP(hipMemsetAsync(b->status.get(), 0, sizeof(unsigned long long), c->stream));
+  XLB_HIP(b->virt.alloc((size_t)n_bodies * 2 * sizeof(double)));
+  XLB_HIP(b->prev.alloc((size_t)n_bodies * 6 * sizeof(double)));
+  XLB_HIP(b->radius.alloc((size_t)n_bodies * sizeof(double)));
+  XLB_HIP(b->contact.alloc((size_t)n_bodies * 3 * sizeof(double)));
+  XLB_HIP(hipMemsetAsync(b->virt.get(), 0, (size_t)n_bodies * 2 * sizeof(double), c->stream));
+  XLB_HIP(hipMemsetAsync(b->prev.get(), 0, (size_t)n_bodies * 6 * sizeof(double), c->stream));
+  XLB_HIP(hipMemsetAsync(b->radius.get(), 0, (size_t)n_bodies * sizeof(double), c->stream));
+  XLB_HIP(hipMemsetAsync(b->contact.get(), 0, (size_t)n_bodies * 3 * sizeof(double), c->stream));
   XLB_HIP(b->partial.alloc(std::max<size_t>(chunks.size(), 1) * 6 * sizeof(double)));
   XLB_HIP(b->loads.alloc((size_t)n_bodies * 6 * sizeof(double)));
   XLB_HIP(hipMemsetAsync(b->loads.get(), 0, (size_t)n_bodies * 6 * sizeof(double), c->stream));
@@ -540,7 +566,76 @@ int xlbhip_ibm_set_dynamics(xlbhip_ibm* b, int n_bodies, const int* rotate, cons
   if (int rc = upload_bytes(params, (size_t)n_bodies * IBM_DYN_PARAM_DOUBLES * sizeof(double), b->dyn_params)) return rc;
   if (int rc = upload_bytes(state, (size_t)n_bodies * IBM_DYN_STATE_DOUBLES * sizeof(double), b->dyn_state)) return rc;
   XLB_HIP(hipMemsetAsync(b->status.get(), 0, sizeof(unsigned long long), c->stream));
+  XLB_HIP(hipMemsetAsync(b->virt.get(), 0, (size_t)n_bodies * 2 * sizeof(double), c->stream));
+  XLB_HIP(hipMemsetAsync(b->prev.get(), 0, (size_t)n_bodies * 6 * sizeof(double), c->stream));
+  XLB_HIP(hipMemsetAsync(b->radius.get(), 0, (size_t)n_bodies * sizeof(double), c->stream));
+  XLB_HIP(hipMemsetAsync(b->contact.get(), 0, (size_t)n_bodies * 3 * sizeof(double), c->stream));
+  b->virtual_on = b->contact_on = false;
   b->dynamics_set = true;
+  return 0;
+}
+
+int xlbhip_ibm_set_virtual_mass(xlbhip_ibm* b, int n_bodies, const double* virtual_mass, const double* virtual_inertia) {
+  XLB_REQUIRE(b && virtual_mass && virtual_inertia, "null argument");
+  XLB_REQUIRE(n_bodies == b->n_bodies && n_bodies > 0, "xlbhip_ibm_set_virtual_mass: %d bodies, %d are declared (xlbhip_ibm_set_bodies)", n_bodies, b->n_bodies);
+  XLB_REQUIRE(b->dynamics_set, "xlbhip_ibm_set_virtual_mass: call xlbhip_ibm_set_dynamics first");
+  std::vector<double> virt((size_t)n_bodies * 2);
+  bool any = false;
+  for (int i = 0; i < n_bodies; ++i) {
+    const double mv = virtual_mass[i], iv = virtual_inertia[i];
+    XLB_REQUIRE(mv >= 0.0 && mv <= 1.7976931348623157e308, "body %d: virtual_mass %g must be finite and not negative", i, mv);
+    XLB_REQUIRE(iv >= 0.0 && iv <= 1.7976931348623157e308, "body %d: virtual_inertia %g must be finite and not negative", i, iv);
+    virt[2 * (size_t)i] = mv;
+    virt[2 * (size_t)i + 1] = iv;
+    any = any || mv > 0.0 || iv > 0.0;
+  }
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipStreamSynchronize(c->stream));  // queued steps read the tables replaced below
+  if (int rc = upload_bytes(virt.data(), virt.size() * sizeof(double), b->virt)) return rc;
+  XLB_HIP(hipMemsetAsync(b->prev.get(), 0, (size_t)n_bodies * 6 * sizeof(double), c->stream));
+  b->virtual_on = any;
+  return 0;
+}
+
+int xlbhip_ibm_set_contact(xlbhip_ibm* b, int n_bodies, const double* radius, double range, double stiffness, double wall_stiffness, const double* lo,
+                           const double* hi) {
+  XLB_REQUIRE(b && radius, "null argument");
+  XLB_REQUIRE(n_bodies == b->n_bodies && n_bodies > 0, "xlbhip_ibm_set_contact: %d bodies, %d are declared (xlbhip_ibm_set_bodies)", n_bodies, b->n_bodies);
+  XLB_REQUIRE(b->dynamics_set, "xlbhip_ibm_set_contact: call xlbhip_ibm_set_dynamics first");
+  XLB_REQUIRE((lo == nullptr) == (hi == nullptr), "xlbhip_ibm_set_contact: lo and hi are given together or not at all");
+  const double big = 1.7976931348623157e308, inf = HUGE_VAL;
+  XLB_REQUIRE(range >= 0.0 && range <= big, "xlbhip_ibm_set_contact: range %g must be finite and not negative", range);
+  XLB_REQUIRE(stiffness >= 0.0 && stiffness <= big, "xlbhip_ibm_set_contact: stiffness %g must be finite and not negative", stiffness);
+  XLB_REQUIRE(wall_stiffness >= 0.0 && wall_stiffness <= big, "xlbhip_ibm_set_contact: wall_stiffness %g must be finite and not negative", wall_stiffness);
+  bool any = false;
+  for (int i = 0; i < n_bodies; ++i) {
+    XLB_REQUIRE(radius[i] >= 0.0 && radius[i] <= big, "body %d: radius %g must be finite and not negative", i, radius[i]);
+    any = any || radius[i] > 0.0;
+  }
+  IbmContactModel model{range, stiffness, wall_stiffness, {-inf, -inf, -inf}, {inf, inf, inf}};
+  for (int a = 0; lo && a < 3; ++a) {
+    XLB_REQUIRE(lo[a] < hi[a], "xlbhip_ibm_set_contact: lo[%d] = %g must be below hi[%d] = %g", a, lo[a], a, hi[a]);  // (false for a NaN)
+    model.lo[a] = lo[a];
+    model.hi[a] = hi[a];
+  }
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipStreamSynchronize(c->stream));  // queued steps read the tables replaced below
+  if (int rc = upload_bytes(radius, (size_t)n_bodies * sizeof(double), b->radius)) return rc;
+  XLB_HIP(hipMemsetAsync(b->contact.get(), 0, (size_t)n_bodies * 3 * sizeof(double), c->stream));
+  b->contact_model = model;
+  b->contact_on = any && b->any_dynamic;
+  return 0;
+}
+
+int xlbhip_ibm_contact_forces(xlbhip_ibm* b, int n_bodies, double* forces) {
+  XLB_REQUIRE(b && n_bodies == b->n_bodies && (n_bodies == 0 || forces), "xlbhip_ibm_contact_forces: expected room for %d bodies", b ? b->n_bodies : 0);
+  if (n_bodies == 0) return 0;
+  xlbhip_ctx* c = b->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  XLB_HIP(hipMemcpyAsync(forces, b->contact.get(), (size_t)n_bodies * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  XLB_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
 

@@ -123,16 +123,23 @@ class RigidDynamics:
     ``translate``         which world axes the centre may move along
     ``rotate``            "free" (3-D rotation), ("axis", a) (about the fixed world direction a through the centre: a free-spinning
                           rotor) or "locked"
+    ``virtual_mass``      m_v >= 0 and
+    ``virtual_inertia``   I_v >= 0 (added as I_v E to the body-frame inertia): the virtual-mass stabilisation of Schwarz, Kempe and
+                          Froehlich (J. Comput. Phys. 281 (2015) 591).  The term is added to both sides of the equation of motion, on
+                          the right with the previous step's acceleration: a = (F + m_v a_prev) / (mass + m_v), and T + I_v alpha_prev
+                          for the torque.  A steady state is unchanged; transients are slowed
 
     The scheme is explicit with dt = 1 (csrc/ibm_dynamics_kernels.hpp states it to the operation): symplectic Euler for the centre,
     v' = v + F / mass, c' = c + v', and for the rotation L' = L + T, w* = R Ib^-1 R^T L', q' = normalise(cay(w*) q) with the Cayley
-    map in place of the exponential.  Explicit coupling of this kind is unstable for bodies about as light as the fluid; see
-    ``sphere``.  There are no contact or lubrication forces, and a body must stay two cells inside the box (no periodic wrap)."""
+    map in place of the exponential.  Explicit coupling of this kind is unstable for bodies about as light as the fluid unless a
+    virtual mass is set; see ``sphere``.  Contact forces with planes and between bodies are switched on with
+    ``IBMStepper.set_contact`` for bodies that carry an ``IBMBody(..., contact_radius=r)``; there are no lubrication, tangential or
+    frictional forces, and a body must stay two cells inside the box (no periodic wrap), which wall planes can enforce."""
 
     ROTATE_LOCKED, ROTATE_AXIS, ROTATE_FREE = 0, 1, 2
 
     def __init__(self, mass, inertia, centre, velocity=(0.0, 0.0, 0.0), orientation=None, angular_velocity=(0.0, 0.0, 0.0), force=(0.0, 0.0, 0.0),
-                 torque=(0.0, 0.0, 0.0), spring=None, translate=(True, True, True), rotate="free"):
+                 torque=(0.0, 0.0, 0.0), spring=None, translate=(True, True, True), rotate="free", virtual_mass=0.0, virtual_inertia=0.0):
         self.mass = float(_finite("mass", mass, ()))
         if not self.mass > 0.0:
             raise ValueError("RigidDynamics: mass must be positive")
@@ -142,6 +149,12 @@ class RigidDynamics:
         if inertia.shape != (3, 3) or not np.array_equal(inertia, inertia.T) or not (np.linalg.eigvalsh(inertia) > 0.0).all():
             raise ValueError("RigidDynamics: inertia must be a positive scalar or a 3 x 3 symmetric positive definite tensor")
         self.inertia = inertia
+        self.virtual_mass = float(_finite("virtual_mass", virtual_mass, ()))
+        self.virtual_inertia = float(_finite("virtual_inertia", virtual_inertia, ()))
+        if self.virtual_mass < 0.0:
+            raise ValueError("RigidDynamics: virtual_mass must not be negative")
+        if self.virtual_inertia < 0.0:
+            raise ValueError("RigidDynamics: virtual_inertia must not be negative")
         self.centre = _finite("centre", centre, (3,))
         self.velocity = _finite("velocity", velocity, (3,))
         self.orientation = np.eye(3) if orientation is None else _finite("orientation", orientation, (3, 3))
@@ -178,21 +191,32 @@ class RigidDynamics:
             raise ValueError('RigidDynamics: rotate must be "free", "locked" or ("axis", a)')
 
     @classmethod
-    def sphere(cls, radius, density, centre, gravity=(0.0, 0.0, 0.0), **kw):
+    def sphere(cls, radius, density, centre, gravity=(0.0, 0.0, 0.0), virtual_mass_coefficient=0.0, **kw):
         """A homogeneous sphere of ``density`` (the fluid's is 1) under ``gravity``, with Uhlmann's (J. Comput. Phys. 209 (2005) 448)
         effective quantities: the fluid inside the marker surface is forced too and moves with the body, which leaves
         mass = (density - 1) V, inertia = (density - 1) 2/5 V r^2 and force = (density - 1) V g for the integrator.
 
         density <= 1.2 is refused: with the effective mass tending to zero the explicit scheme is unstable below about that ratio
-        (Uhlmann reports the limit); lighter bodies need an implicit or a virtual-mass treatment, which this stepper does not have."""
+        (Uhlmann reports the limit); lighter bodies need a virtual mass: ``virtual_mass_coefficient`` = C_v > 0 sets
+        virtual_mass = C_v V and virtual_inertia = C_v 2/5 V r^2, and then any density above 1 is taken.  In the NumPy restatement
+        of the coupled loop (a 24^3 box, radius 5.3, four sweeps; profiles/ibm_virtual_mass.md) C_v = 4 holds density 2.5 (3 does not),
+        C_v = 6 and 8 hold densities 1.15 (4 does not) and 1.05; the rotational counterpart was not measured."""
         radius, density = float(radius), float(density)
         if not radius > 0.0 or not np.isfinite(radius):
             raise ValueError("RigidDynamics.sphere: radius must be positive")
-        if not density > 1.2:
+        coefficient = float(_finite("virtual_mass_coefficient", virtual_mass_coefficient, ()))
+        if coefficient < 0.0:
+            raise ValueError("RigidDynamics.sphere: virtual_mass_coefficient must not be negative")
+        if coefficient > 0.0:
+            if not density > 1.0:
+                raise ValueError("RigidDynamics.sphere: density must exceed 1 (the effective mass (density - 1) V must be positive)")
+        elif not density > 1.2:
             raise ValueError("RigidDynamics.sphere: density must exceed 1.2 (the explicit coupling is unstable for lighter bodies)")
         volume = 4.0 / 3.0 * np.pi * radius**3
         excess = (density - 1.0) * volume
         g = _finite("gravity", gravity, (3,))
+        if coefficient > 0.0:
+            kw.update(virtual_mass=coefficient * volume, virtual_inertia=coefficient * 0.4 * volume * radius * radius)
         return cls(mass=excess, inertia=excess * 0.4 * radius * radius, centre=centre, force=excess * g, **kw)
 
     uhlmann = sphere
@@ -216,15 +240,19 @@ class RigidDynamics:
 
     def native(self):
         """-> (rotation mode, 32 parameters, 16 doubles of initial state) as xlbhip_ibm_set_dynamics takes them: the host passes
-        1 / mass, Ib^-1, 1 / I_a with I_a = a^T R0 Ib R0^T a, and L(0) = R0 Ib R0^T w0 (axis mode: the rate a . w0)."""
+        1 / mass, Ib^-1, 1 / I_a with I_a = a^T R0 Ib R0^T a, and L(0) = R0 Ib R0^T w0 (axis mode: the rate a . w0).  With a virtual
+        mass or inertia, mass + m_v and Ib + I_v E take the places of mass and Ib in these; m_v and I_v themselves travel separately
+        (``virtual()``)."""
         R0 = self.orientation
-        world = R0 @ self.inertia @ R0.T
+        inertia = self.inertia + self.virtual_inertia * np.eye(3) if self.virtual_inertia > 0.0 else self.inertia
+        mass = self.mass + self.virtual_mass if self.virtual_mass > 0.0 else self.mass
+        world = R0 @ inertia @ R0.T
         params = np.zeros(32)
-        params[0] = 1.0 / self.mass
+        params[0] = 1.0 / mass
         params[1:4] = self.translate.astype(np.float64)
         params[4:7], params[7:10] = self.force, self.torque
         params[10:13], params[13:16], params[16:19] = self.anchor, self.stiffness, self.damping
-        params[19:28] = np.linalg.inv(self.inertia).reshape(9)
+        params[19:28] = np.linalg.inv(inertia).reshape(9)
         state = np.zeros(16)
         state[0:3], state[3:6] = self.centre, self.velocity
         state[6:10] = self._quaternion(R0)
@@ -236,6 +264,10 @@ class RigidDynamics:
             state[10:13] = world @ self.angular_velocity
         return self.rotate, params, state
 
+    def virtual(self):
+        """-> (m_v, I_v) as xlbhip_ibm_set_virtual_mass takes them."""
+        return self.virtual_mass, self.virtual_inertia
+
 
 class IBMBody:
     """A contiguous range of an IBMStepper's markers that moves as one rigid body.
@@ -246,9 +278,11 @@ class IBMBody:
                   is at rest (its loads are still summed)
     ``centre0``   the point the uploaded vertices refer to: marker k sits at c(t) + R(t) (X0_k - centre0).  Default: motion.at(0)[1],
                   dynamics.centre, or the mean of the body's markers for a body at rest (there it is the point the torque is taken
-                  about)."""
+                  about).
+    ``contact_radius``  r > 0: the body takes part in the contact model of ``IBMStepper.set_contact`` as a sphere of that radius
+                  about its centre — a free body is pushed, a prescribed body or one at rest is an obstacle.  None: it does not."""
 
-    def __init__(self, markers, motion=None, centre0=None, dynamics=None):
+    def __init__(self, markers, motion=None, centre0=None, dynamics=None, contact_radius=None):
         if not isinstance(markers, slice):
             raise TypeError("IBMBody: markers must be a slice of the marker arrays")
         if motion is not None and dynamics is not None:
@@ -261,3 +295,8 @@ class IBMBody:
         self.motion = motion
         self.dynamics = dynamics
         self.centre0 = None if centre0 is None else np.array(centre0, dtype=np.float64).reshape(3)
+        if contact_radius is not None:
+            contact_radius = float(contact_radius)
+            if not (np.isfinite(contact_radius) and contact_radius > 0.0):
+                raise ValueError("IBMBody: contact_radius must be positive and finite, or None")
+        self.contact_radius = contact_radius

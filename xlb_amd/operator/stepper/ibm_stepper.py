@@ -43,10 +43,21 @@ reads from it.  Free, prescribed and resting bodies mix in one ``set_bodies``; a
 initial values.  ``body_poses()`` is the pose (R | c | w | v, 18 doubles per body) the next call will use;
 ``run(..., record_poses=True)`` also returns the poses every step used, row for row with ``record_loads``.  A body whose new state
 is not finite stops where it is and ``body_poses()`` raises, naming it.  The integration is explicit: ``set_bodies`` warns
-(RuntimeWarning) when a free body's mass is below ibm_max_iterations x the sum of its markers' areas, the added mass the coupling
-can load it with, beyond which the scheme diverges unless the sweeps end early.  Not covered: contact or lubrication forces between bodies
-or with walls; a body crossing a periodic face (the coupling does not wrap: keep bodies two cells inside the box); density ratios
-at or below about 1.2, which need an implicit or virtual-mass treatment; deformable bodies.
+(RuntimeWarning) when a free body's mass plus virtual mass is below ibm_max_iterations x the sum of its markers' areas, the added
+mass the coupling can load it with, beyond which the scheme diverges unless the sweeps end early.
+
+Light bodies and contact.  ``RigidDynamics(..., virtual_mass=, virtual_inertia=)`` or ``RigidDynamics.sphere(...,
+virtual_mass_coefficient=C_v)`` adds the virtual-mass term of Schwarz, Kempe and Froehlich (2015) to the integrator, which is what a
+body about as dense as the fluid needs.  ``set_contact(range, stiffness, wall_stiffness, box)`` switches on a central repulsive
+force between the bodies that carry an ``IBMBody(..., contact_radius=r)`` and from the planes of ``box``; ``body_contact_forces()``
+reads the last step's.  Both are evaluated inside the integrator's launch: a light sphere that settles onto a floor is still one
+native ``run``.  A stepper that uses neither enqueues exactly the launches it did before.  Measured (profiles/ibm_virtual_mass.md):
+the NumPy restatement of the coupled loop, translation only, on a 24^3 box — C_v = 4 holds a sphere of density 2.5 and C_v = 8 one
+of density 1.15 with all four sweeps, where no virtual mass diverges; the device replays the restatement bit for bit.  NOT measured:
+the rotational counterpart in a coupled run, and any settling curve against an experiment.
+
+Not covered: lubrication, tangential or frictional contact; a body crossing a periodic face (the coupling does not wrap: keep bodies
+two cells inside the box, e.g. with the planes of ``set_contact``); deformable bodies.
 
 The host evaluates the poses (18 doubles per step and body) and stages them ahead of the steps, as it does for time-dependent
 walls: ``run`` works in chunks of at most POSE_CHUNK_STEPS = 256 steps and at most 1 MiB of poses (113 steps with 64 bodies); the
@@ -133,6 +144,7 @@ class IBMStepper(IncompressibleNavierStokesStepper):
         self._bodies = []
         self._any_moving = False  # some body with markers follows a prescribed motion: its poses are staged
         self._any_dynamic = False
+        self._contact = None  # (range, stiffness, wall_stiffness, lo, hi) of set_contact
         self._next_timestep = 0
         self._markers = IBMMarkers(self)
         self.s_lagr_forces = LagrangianForces(self)
@@ -205,15 +217,70 @@ class IBMStepper(IncompressibleNavierStokesStepper):
                 if body.dynamics is not None:
                     rotate[i], params[i], state[i] = body.dynamics.native()
             ibm.set_dynamics(rotate, params, state)
+            virtual = np.array([(0.0, 0.0) if body.dynamics is None else body.dynamics.virtual() for body in bodies])
+            if (virtual > 0.0).any():
+                ibm.set_virtual_mass(virtual[:, 0], virtual[:, 1])
         self._bodies = bodies
         self._body_centre0 = centre0
         self._next_timestep = 0  # (body_poses: a new declaration starts over, for prescribed bodies as for free ones)
         self._any_moving = any(body.motion is not None and b > a for body, (a, b) in zip(bodies, ranges))
+        self._apply_contact()
+
+    def set_contact(self, range, stiffness, wall_stiffness=None, box=None):
+        """Switch on the contact model for the bodies declared with an ``IBMBody(..., contact_radius=r)``, now and in every later
+        ``set_bodies``: a central repulsive soft-sphere force of the Glowinski / Wan-Turek kind, evaluated on the device inside the
+        integrator's launch from the centres of the step's poses.
+
+        ``range``           zeta >= 0: the force acts while the gap between two surfaces is below it
+        ``stiffness``       k >= 0: body i gets k (zeta - gap)^2 (c_i - c_j) / |c_i - c_j| from every body j with a radius, with
+                            gap = |c_i - c_j| - (r_i + r_j).  Prescribed bodies and bodies at rest are obstacles; only free bodies
+                            are pushed
+        ``wall_stiffness``  k_w >= 0 (default: ``stiffness``): k_w (zeta - gap)^2 along the inward normal of a plane of ``box``,
+                            gap = (distance of the centre from the plane) - r_i
+        ``box``             (lo, hi), 3 values each: the planes x_a = lo_a and x_a = hi_a; -inf / +inf switch a plane off.  None: no
+                            planes.  Planes two cells plus zeta inside the grid keep the markers' supports inside it
+
+        A body at rest on a plane under a weight W sits where k_w (zeta - gap)^2 = W: choose k_w zeta^2 well above W.  The force is
+        explicit, so k (k_w) must stay well below (mass + virtual mass) / dt^2 = the mass in lattice units.  It enters the
+        integrator only: ``body_loads()`` stays hydrodynamic.  Raises ValueError naming the argument that is negative or not finite,
+        or the axis with lo >= hi."""
+        def number(name, value):
+            value = float(value)
+            if not (np.isfinite(value) and value >= 0.0):
+                raise ValueError(f"set_contact: {name} must be finite and not negative")
+            return value
+
+        zeta, k = number("range", range), number("stiffness", stiffness)
+        kw = k if wall_stiffness is None else number("wall_stiffness", wall_stiffness)
+        lo = hi = None
+        if box is not None:
+            try:
+                lo, hi = (np.array(x, dtype=np.float64).reshape(3) for x in box)
+            except (TypeError, ValueError):
+                raise ValueError("set_contact: box must be (lo, hi) with 3 values each") from None
+            for a in (0, 1, 2):
+                if not lo[a] < hi[a]:
+                    raise ValueError(f"set_contact: box: lo >= hi along axis {a} ({lo[a]} and {hi[a]})")
+        self._contact = (zeta, k, kw, lo, hi)
+        self._apply_contact()
+
+    def _apply_contact(self):
+        if self._contact is None or not self._any_dynamic:
+            return
+        radius = [0.0 if body.contact_radius is None else body.contact_radius for body in self._bodies]
+        self._ibm_native().set_contact(radius, *self._contact)
+
+    def body_contact_forces(self):
+        """(n_bodies, 3) float64: the contact force on every body in the LAST call, read from the device now (zero for bodies that
+        are not free or carry no ``contact_radius``, and while no ``set_contact`` is in force)."""
+        if not self._bodies:
+            return np.zeros((0, 3))
+        return self._ibm_native().contact_forces()
 
     def _warn_light_bodies(self, bodies, ranges):
         """The marker force is the velocity deficit added up over the sweeps that ran, so a body that starts to move drags an added
         mass of up to ibm_max_iterations x (sum of its markers' areas) along; the explicit integrator diverges when that exceeds
-        the body's mass.  Say so when the body is declared, not when its state has stopped being finite."""
+        the body's mass plus its virtual mass.  Say so when the body is declared, not when its state has stopped being finite."""
         areas = self._markers._areas
         if areas is None:
             return
@@ -222,10 +289,11 @@ class IBMStepper(IncompressibleNavierStokesStepper):
             if dyn is None or not dyn.translate.any():
                 continue
             added = self.ibm_max_iterations * float(areas[a:b].astype(np.float64).sum())
-            if dyn.mass < added:
-                warnings.warn(f"set_bodies: body {i}: mass {dyn.mass:.4g} is below ibm_max_iterations x sum of marker areas = {added:.4g}, the added mass the "
+            if dyn.mass + dyn.virtual_mass < added:
+                what = f"mass {dyn.mass:.4g}" if dyn.virtual_mass == 0.0 else f"mass + virtual mass {dyn.mass + dyn.virtual_mass:.4g}"
+                warnings.warn(f"set_bodies: body {i}: {what} is below ibm_max_iterations x sum of marker areas = {added:.4g}, the added mass the "
                               "coupling can load it with; the explicit integration of this body is unstable unless the sweeps end early "
-                              "(heavier body, fewer sweeps, or a smaller ibm_relaxation)", RuntimeWarning, stacklevel=3)
+                              "(heavier body, a virtual mass, fewer sweeps, or a smaller ibm_relaxation)", RuntimeWarning, stacklevel=3)
 
     def _poses(self, t_first, n):
         """(n, n_bodies, 18) float64: R (row-major) | c | w | v of every body at t_first .. t_first + n - 1 (the rest pose for a
