@@ -12,27 +12,11 @@ static void launch(K k, size_t blocks, unsigned threads, A... a) {
   for (size_t b = 0; b < blocks; ++b)
     for (unsigned t = 0; t < threads; ++t) { blockIdx.x = (unsigned)b; threadIdx.x = t; k(a...); }
 }
-// the host tables of xlbhip_ibm_set_bodies
-struct Tables {
-  std::vector<int32_t> move_id, chunk0;
-  std::vector<IbmLoadChunk> chunks;
-};
-static Tables tables(int64_t n, int nb, const int64_t* first, const int64_t* count, const int* moving) {
-  Tables t;
-  t.move_id.assign((size_t)n, -1);
-  for (int i = 0; i < nb; ++i) {
-    if (moving[i]) std::fill(t.move_id.begin() + first[i], t.move_id.begin() + first[i] + count[i], (int32_t)i);
-    t.chunk0.push_back((int32_t)t.chunks.size());
-    for (int64_t o = 0; o < count[i]; o += IBM_LOADS_CHUNK)
-      t.chunks.push_back(IbmLoadChunk{(int32_t)i, (int32_t)(first[i] + o), (int32_t)std::min<int64_t>(IBM_LOADS_CHUNK, count[i] - o)});
-  }
-  t.chunk0.push_back((int32_t)t.chunks.size());
-  return t;
-}
 // pos / vel hold the uploaded arrays on entry and the moved ones on return; pose [nb][18], centre0 [nb][3]
 extern "C" int move_cpu(int64_t n, int nb, const int64_t* first, const int64_t* count, const int* moving, const double* centre0, const double* pose,
                         const float* pos0, float* pos, float* vel) {
-  const Tables t = tables(n, nb, first, count, moving);
+  const IbmBodyTables t = ibm_body_tables(n, nb, first, count, moving, centre0);  // the tables xlbhip_ibm_set_bodies uploads
+  if (!t.error.empty()) return 1;
   launch(k_ibm_move, (size_t)(n + 255) / 256, 256u, pos0, (const int32_t*)t.move_id.data(), pose, centre0, n, pos, vel);
   return 0;
 }
@@ -40,8 +24,9 @@ extern "C" int move_cpu(int64_t n, int nb, const int64_t* first, const int64_t* 
 extern "C" int loads_cpu(int64_t n, int nb, const int64_t* first, const int64_t* count, const double* pose, int f32, const void* F, const float* area,
                          const float* pos, double* loads, double* history_row) {
   const int moving[IBM_MAX_BODIES] = {};
-  if (nb > IBM_MAX_BODIES) return 1;
-  const Tables t = tables(n, nb, first, count, moving);
+  const double centre0[IBM_MAX_BODIES * 3] = {};  // (the chunks do not depend on them)
+  const IbmBodyTables t = ibm_body_tables(n, nb, first, count, moving, centre0);
+  if (!t.error.empty()) return 1;
   std::vector<double> partial(t.chunks.size() * 6 + 1, 0.0);
   if (!t.chunks.empty()) {
     if (f32) launch(k_ibm_loads<float>, t.chunks.size(), (unsigned)IBM_LOADS_CHUNK, t.chunks.data(), (const float*)F, area, pos, pose, partial.data());

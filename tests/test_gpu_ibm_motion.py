@@ -25,9 +25,11 @@ from xlb_amd import _lib
 from xlb_amd.grid import grid_factory
 from xlb_amd.operator.stepper import IBMBody, IBMStepper, RigidMotion
 
+import _ibm_dynamics_ref as dref
 import _ibm_motion_ref as mref
 import _ibm_ref as ref
 from _util import init_hip
+from test_ibm_contact_on_cpu import light_sphere
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -212,6 +214,57 @@ def test_resting_bodies_change_nothing():
             <= mref.loads_bound(F[300:], AREAS[300:], X0[300:], (11.0, 12.0, 13.0))).all()
     _, f, F, _, _ = run([resting, []])
     assert np.array_equal(f, plain_f) and np.array_equal(F, plain_F)
+
+
+PHASE_STEPS = 3
+
+
+def run_phase(stepper, phase, f_np, f_0, f_1, bc_mask, missing_mask):
+    """Three steps of one declaration from the initial populations and the uploaded markers; everything that can be read afterwards."""
+    f_0.assign(f_np)
+    out = {}
+    if phase == "free":  # the light sphere of test_ibm_contact_on_cpu.py on a floor plane 0.25 below it (range 0.5): pushed from the first step
+        floor = dref.CENTRE[2] - RADIUS - 0.25
+        stepper.set_contact(0.5, 2.0, wall_stiffness=1.0, box=((-np.inf, -np.inf, floor), (np.inf,) * 3))
+        stepper.set_bodies([IBMBody(markers=slice(0, N), dynamics=light_sphere(1.15, 8.0), contact_radius=RADIUS)])
+        cur, _, out["poses history"] = stepper.run(f_0, f_1, bc_mask, missing_mask, OMEGA, PHASE_STEPS, record_poses=True)
+    elif phase == "prescribed":
+        stepper.set_bodies([IBMBody(markers=slice(0, N), motion=motion())])
+        cur, _, out["loads history"] = stepper.run(f_0, f_1, bc_mask, missing_mask, OMEGA, PHASE_STEPS, record_loads=True)
+    else:
+        stepper.set_bodies([IBMBody(markers=slice(0, N))] if phase == "rest" else [])
+        cur, _ = stepper.run(f_0, f_1, bc_mask, missing_mask, OMEGA, PHASE_STEPS)
+    out.update({"f": cur.numpy(), "forces": stepper.s_lagr_forces.numpy(), "loads": stepper.body_loads(), "poses": stepper.body_poses(),
+                "contact": stepper.body_contact_forces(), "positions": stepper._markers.positions()})
+    return out
+
+
+def test_redeclaring_bodies_equals_a_fresh_stepper():
+    """One stepper declared four times over — a free light sphere with virtual mass on a floor, the same markers as a prescribed body,
+    as a body at rest, then no bodies — against a fresh stepper for each declaration, bit for bit: a flag, a table or a recording that
+    survives a redeclaration shows up here."""
+    still = np.zeros_like(X0)
+    stepper, lat, f_np, f_0, f_1, bc_mask, missing_mask = case()
+    markers = stepper.markers(X0, AREAS, still)
+    got = {}
+    for phase in ("free", "prescribed", "rest", "none"):
+        markers.update(vertices=X0, velocities=still)
+        got[phase] = run_phase(stepper, phase, f_np, f_0, f_1, bc_mask, missing_mask)
+    for phase, mine in got.items():
+        fresh, lat, f_np, f_0, f_1, bc_mask, missing_mask = case()
+        fresh.markers(X0, AREAS, still)
+        exp = run_phase(fresh, phase, f_np, f_0, f_1, bc_mask, missing_mask)
+        assert mine.keys() == exp.keys()
+        for what in exp:
+            assert mine[what].shape == exp[what].shape and np.array_equal(mine[what], exp[what]), (phase, what)
+    # every declaration did what it says
+    assert (got["free"]["contact"][0, 2] > 0.0) and got["free"]["poses history"].shape == (PHASE_STEPS, 1, 18)
+    assert not np.array_equal(got["free"]["positions"], X0) and not np.array_equal(got["prescribed"]["positions"], X0)
+    assert got["prescribed"]["loads history"].shape == (PHASE_STEPS, 1, 6) and np.abs(got["prescribed"]["loads history"]).min(axis=2).max() > 0
+    assert np.array_equal(got["prescribed"]["contact"], np.zeros((1, 3))) and np.array_equal(got["rest"]["contact"], np.zeros((1, 3)))
+    assert np.array_equal(got["rest"]["positions"], X0) and np.array_equal(got["none"]["positions"], X0)
+    assert np.array_equal(got["rest"]["f"], got["none"]["f"]) and not np.array_equal(got["rest"]["f"], got["prescribed"]["f"])
+    assert got["none"]["loads"].shape == (0, 6) and got["none"]["poses"].shape == (0, 18)
 
 
 def test_unstaged_pose_and_bad_bodies_fail_loudly():

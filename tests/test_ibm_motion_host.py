@@ -1,12 +1,11 @@
-"""Host side of the rigid bodies of IBMStepper: RigidMotion's poses, the validation of set_bodies (which needs no device: it fails
-before the native object is asked for anything but the number of markers) and the NumPy restatement of the move and the loads
+"""Host side of the rigid bodies of IBMStepper: RigidMotion's poses, the validation of set_bodies (helper.ibm_helper.declare_bodies, which
+needs no device) and the NumPy restatement of the move and the loads
 (tests/_ibm_motion_ref.py) against a plain fp64 rigid transform."""
 
 import numpy as np
 import pytest
 
-from xlb_amd.helper.ibm_helper import IBMBody, RigidMotion
-from xlb_amd.operator.stepper.ibm_stepper import IBMStepper
+from xlb_amd.helper.ibm_helper import IBMBody, RigidMotion, declare_bodies
 
 import _ibm_motion_ref as mref
 import _ibm_ref as ref
@@ -56,34 +55,22 @@ def test_zero_axis_is_refused():
         RigidMotion((0, 0, 0), (0, 0, 0), 0.1)
 
 
-class _FakeNative:
-    n = 400
-
-
-class _Validation(IBMStepper):
-    """set_bodies' checks without a device: the native object only has to say how many markers there are."""
-
-    def __init__(self):
-        self._bodies, self._any_moving = [], False
-
-    def _ibm_native(self):
-        return _FakeNative()
-
-
 def test_set_bodies_validation_names_the_body():
-    s = _Validation()
+    def declare(bodies):
+        return declare_bodies(bodies, 400, lambda: pytest.fail("no resting body needs the uploaded positions here"))
+
     with pytest.raises(ValueError, match=r"body 1.*300:401.*out of bounds.*400"):
-        s.set_bodies([IBMBody(slice(0, 100)), IBMBody(slice(300, 401))])
+        declare([IBMBody(slice(0, 100)), IBMBody(slice(300, 401))])
     with pytest.raises(ValueError, match=r"body 0.*out of bounds"):
-        s.set_bodies([IBMBody(slice(-5, 100))])
+        declare([IBMBody(slice(-5, 100))])
     with pytest.raises(ValueError, match=r"body 0.*out of bounds"):
-        s.set_bodies([IBMBody(slice(200, 100))])
+        declare([IBMBody(slice(200, 100))])
     with pytest.raises(ValueError, match=r"bodies 0 and 2 overlap"):
-        s.set_bodies([IBMBody(slice(0, 100)), IBMBody(slice(200, 300)), IBMBody(slice(99, 150))])
+        declare([IBMBody(slice(0, 100)), IBMBody(slice(200, 300)), IBMBody(slice(99, 150))])
     with pytest.raises(ValueError, match=r"body 0.*contiguous"):
-        s.set_bodies([IBMBody(slice(0, 100, 2))])
+        declare([IBMBody(slice(0, 100, 2))])
     with pytest.raises(ValueError, match=r"65 bodies.*64"):
-        s.set_bodies([IBMBody(slice(i, i + 1)) for i in range(65)])
+        declare([IBMBody(slice(i, i + 1)) for i in range(65)])
     with pytest.raises(TypeError):
         IBMBody(markers=[0, 1, 2])
     with pytest.raises(TypeError):

@@ -669,10 +669,14 @@ class IBM:
                                     C.byref(where)))
         return bool(where.value)
 
-    def forces(self):
-        out = np.zeros((self.n, 3), np.float64)
-        check(load().xlbhip_ibm_forces(self._h, self.n, out.ctypes.data))
+    def _read(self, name, shape):
+        """float64 array of `shape` filled by the read-back xlbhip_ibm_<name>(handle, shape[0], out)"""
+        out = np.zeros(shape, np.float64)
+        check(getattr(load(), "xlbhip_ibm_" + name)(self._h, shape[0], out.ctypes.data))
         return out
+
+    def forces(self):
+        return self._read("forces", (self.n, 3))
 
     def iterations(self):
         n = _i()
@@ -705,17 +709,13 @@ class IBM:
         check(load().xlbhip_ibm_stage_poses(self._h, int(first_timestep), poses.shape[0], poses.ctypes.data))
 
     def loads(self):
-        out = np.zeros((self.n_bodies, 6), np.float64)
-        check(load().xlbhip_ibm_loads(self._h, self.n_bodies, out.ctypes.data))
-        return out
+        return self._read("loads", (self.n_bodies, 6))
 
     def record_loads(self, n_rows):
         check(load().xlbhip_ibm_record_loads(self._h, int(n_rows)))
 
     def loads_history(self, n_rows):
-        out = np.zeros((int(n_rows), self.n_bodies, 6), np.float64)
-        check(load().xlbhip_ibm_loads_history(self._h, int(n_rows), out.ctypes.data))
-        return out
+        return self._read("loads_history", (int(n_rows), self.n_bodies, 6))
 
     DYN_PARAM_DOUBLES, DYN_STATE_DOUBLES = 32, 16  # IBM_DYN_PARAM_DOUBLES, IBM_DYN_STATE_DOUBLES of csrc/ibm_dynamics_kernels.hpp
 
@@ -738,9 +738,7 @@ class IBM:
         check(load().xlbhip_ibm_record_poses(self._h, int(n_rows)))
 
     def poses_history(self, n_rows):
-        out = np.zeros((int(n_rows), self.n_bodies, 18), np.float64)
-        check(load().xlbhip_ibm_poses_history(self._h, int(n_rows), out.ctypes.data))
-        return out
+        return self._read("poses_history", (int(n_rows), self.n_bodies, 18))
 
     def set_virtual_mass(self, virtual_mass, virtual_inertia):
         """m_v and I_v of every body, (n_bodies,) each; after set_dynamics."""
@@ -760,9 +758,7 @@ class IBM:
                                             None if lo is None else lo.ctypes.data, None if hi is None else hi.ctypes.data))
 
     def contact_forces(self):
-        out = np.zeros((self.n_bodies, 3), np.float64)
-        check(load().xlbhip_ibm_contact_forces(self._h, self.n_bodies, out.ctypes.data))
-        return out
+        return self._read("contact_forces", (self.n_bodies, 3))
 
     def download_markers(self, positions=True, velocities=True):
         p = np.zeros((self.n, 3), np.float32) if positions else None

@@ -53,18 +53,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include "ibm_bodies.hpp"
 #include "ibm_motion_kernels.hpp"
 
 namespace xlb {
-
-constexpr int IBM_DYN_STATE_DOUBLES = 16;
-constexpr int IBM_DYN_PARAM_DOUBLES = 32;
-enum : int32_t { IBM_BODY_REST = 0, IBM_BODY_PRESCRIBED = 1, IBM_BODY_DYNAMIC = 2 };  // the `moving` flags of xlbhip_ibm_set_bodies
-enum : int32_t { IBM_ROTATE_LOCKED = 0, IBM_ROTATE_AXIS = 1, IBM_ROTATE_FREE = 2 };
-
-struct IbmContactModel {
-  double range, stiffness, wall_stiffness, lo[3], hi[3];
-};
 
 __device__ __forceinline__ bool ibm_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }  // (false for a NaN)
 

@@ -21,16 +21,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include "ibm_bodies.hpp"
+
 namespace xlb {
-
-constexpr int IBM_MAX_BODIES = 64;
-constexpr int IBM_POSE_DOUBLES = 18;  // R[9] | c[3] | w[3] | v[3]
-constexpr int IBM_LOADS_CHUNK = 256;  // markers per partial sum = threads per block of k_ibm_loads
-
-// one block of k_ibm_loads: `count` (1 .. 256) markers from `first`, all of body `body`
-struct IbmLoadChunk {
-  int32_t body, first, count;
-};
 
 // move_id[k]: the body of marker k when that body moves, else -1 (a body at rest, no body: the marker is not touched)
 __global__ void k_ibm_move(const float* __restrict__ pos0, const int32_t* __restrict__ move_id, const double* __restrict__ pose,

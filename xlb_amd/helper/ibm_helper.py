@@ -7,6 +7,8 @@ that are about one cell apart.
 examples/ibm/wind_turbine_ibm.py:160-199 turns its rotor with a kernel of its own; here the host evaluates poses and the stepper's
 native code applies them).  ``RigidDynamics`` describes a free body, which the stepper's native code integrates from its loads."""
 
+from types import SimpleNamespace
+
 import numpy as np
 
 from .nse_fields import create_nse_fields
@@ -300,3 +302,53 @@ class IBMBody:
             if not (np.isfinite(contact_radius) and contact_radius > 0.0):
                 raise ValueError("IBMBody: contact_radius must be positive and finite, or None")
         self.contact_radius = contact_radius
+
+
+def declare_bodies(bodies, n_markers, uploaded_positions, max_bodies=64):
+    """What ``IBMStepper.set_bodies`` hands to the native object for a list of IBMBody over ``n_markers`` markers; needs no device.
+    ``uploaded_positions()`` -> the (n_markers, 3) positions uploaded last, asked for only when a resting body with markers has
+    no ``centre0`` (it gets the mean of its markers).  Raises ValueError naming the body for a range that is out of bounds or
+    overlaps another, and for more than ``max_bodies`` bodies.
+
+    -> ``ranges`` [(a, b)], ``kinds`` (0 at rest, 1 prescribed, 2 dynamic), ``centre0`` (n, 3), ``radius`` (n,) contact radii with
+    0 for none, ``virtual`` (n, 2) m_v | I_v, and — None unless some body is dynamic — ``rotate`` (n,), ``params`` (n, 32),
+    ``state`` (n, 16) as xlbhip_ibm_set_dynamics takes them."""
+    if len(bodies) > max_bodies:
+        raise ValueError(f"set_bodies: {len(bodies)} bodies, at most {max_bodies} are supported")
+    n = n_markers
+    ranges = []
+    for i, body in enumerate(bodies):
+        if not isinstance(body, IBMBody):
+            raise TypeError(f"set_bodies: body {i} is not an IBMBody")
+        sl = body.markers
+        a, b = (0 if sl.start is None else sl.start), (n if sl.stop is None else sl.stop)
+        if sl.step not in (None, 1):
+            raise ValueError(f"set_bodies: body {i}: the markers must be a contiguous range (slice step {sl.step})")
+        if not 0 <= a <= b <= n:
+            raise ValueError(f"set_bodies: body {i}: markers {a}:{b} are out of bounds for {n} markers")
+        for j, (c, d) in enumerate(ranges):
+            if a < d and c < b:
+                raise ValueError(f"set_bodies: bodies {j} and {i} overlap (markers {c}:{d} and {a}:{b})")
+        ranges.append((a, b))
+    centre0 = np.zeros((len(bodies), 3))
+    uploaded = None
+    for i, (body, (a, b)) in enumerate(zip(bodies, ranges)):
+        if body.centre0 is not None:
+            centre0[i] = body.centre0
+        elif body.motion is not None:
+            centre0[i] = np.asarray(body.motion.at(0)[1], dtype=np.float64)
+        elif body.dynamics is not None:
+            centre0[i] = body.dynamics.centre
+        elif b > a:
+            uploaded = uploaded_positions() if uploaded is None else uploaded
+            centre0[i] = uploaded[a:b].astype(np.float64).mean(axis=0)
+    kinds = [2 if body.dynamics is not None else int(body.motion is not None) for body in bodies]
+    out = SimpleNamespace(ranges=ranges, kinds=kinds, centre0=centre0, rotate=None, params=None, state=None)
+    out.radius = np.array([0.0 if body.contact_radius is None else body.contact_radius for body in bodies], dtype=np.float64)
+    out.virtual = np.array([(0.0, 0.0) if body.dynamics is None else body.dynamics.virtual() for body in bodies], dtype=np.float64).reshape(-1, 2)
+    if 2 in kinds:
+        out.rotate, out.params, out.state = np.zeros(len(bodies), np.int32), np.zeros((len(bodies), 32)), np.zeros((len(bodies), 16))
+        for i, body in enumerate(bodies):
+            if body.dynamics is not None:
+                out.rotate[i], out.params[i], out.state[i] = body.dynamics.native()
+    return out

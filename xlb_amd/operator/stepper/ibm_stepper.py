@@ -70,7 +70,7 @@ import warnings
 import numpy as np
 
 from ... import _lib
-from ...helper.ibm_helper import IBMBody, RigidDynamics, RigidMotion  # noqa: F401  (re-exported: they are this stepper's vocabulary)
+from ...helper.ibm_helper import IBMBody, RigidDynamics, RigidMotion, declare_bodies  # noqa: F401  (re-exported: they are this stepper's vocabulary)
 from ...compute_backend import ComputeBackend
 from ...precision_policy import Precision
 from ..operator import Operator
@@ -142,7 +142,7 @@ class IBMStepper(IncompressibleNavierStokesStepper):
             raise ValueError("ibm_tolerance must not be negative")
         self._ibm = None
         self._bodies = []
-        self._any_moving = False  # some body with markers follows a prescribed motion: its poses are staged
+        self._any_prescribed = False  # some body with markers follows a prescribed motion: its poses are staged
         self._any_dynamic = False
         self._contact = None  # (range, stiffness, wall_stiffness, lo, hi) of set_contact
         self._next_timestep = 0
@@ -177,53 +177,20 @@ class IBMStepper(IncompressibleNavierStokesStepper):
         today's plain stepper; markers a device has moved stay where they are).  Raises ValueError naming the body for a range that
         is out of bounds or overlaps another, and for more than 64 bodies."""
         bodies = list(bodies)
-        if len(bodies) > self.MAX_BODIES:
-            raise ValueError(f"set_bodies: {len(bodies)} bodies, at most {self.MAX_BODIES} are supported")
         ibm = self._ibm_native()
-        n = ibm.n
-        ranges = []
-        for i, body in enumerate(bodies):
-            if not isinstance(body, IBMBody):
-                raise TypeError(f"set_bodies: body {i} is not an IBMBody")
-            sl = body.markers
-            a, b = (0 if sl.start is None else sl.start), (n if sl.stop is None else sl.stop)
-            if sl.step not in (None, 1):
-                raise ValueError(f"set_bodies: body {i}: the markers must be a contiguous range (slice step {sl.step})")
-            if not 0 <= a <= b <= n:
-                raise ValueError(f"set_bodies: body {i}: markers {a}:{b} are out of bounds for {n} markers")
-            for j, (c, d) in enumerate(ranges):
-                if a < d and c < b:
-                    raise ValueError(f"set_bodies: bodies {j} and {i} overlap (markers {c}:{d} and {a}:{b})")
-            ranges.append((a, b))
-        centre0 = np.zeros((len(bodies), 3))
-        uploaded = None
-        for i, (body, (a, b)) in enumerate(zip(bodies, ranges)):
-            if body.centre0 is not None:
-                centre0[i] = body.centre0
-            elif body.motion is not None:
-                centre0[i] = np.asarray(body.motion.at(0)[1], dtype=np.float64)
-            elif body.dynamics is not None:
-                centre0[i] = body.dynamics.centre
-            elif b > a:
-                uploaded = self._markers.positions() if uploaded is None else uploaded
-                centre0[i] = uploaded[a:b].astype(np.float64).mean(axis=0)
-        kinds = [2 if body.dynamics is not None else int(body.motion is not None) for body in bodies]  # 0 at rest, 1 prescribed, 2 dynamic
-        ibm.set_bodies([a for a, _ in ranges], [b - a for a, b in ranges], kinds, centre0)
-        self._any_dynamic = 2 in kinds
+        d = declare_bodies(bodies, ibm.n, self._markers.positions, self.MAX_BODIES)
+        ibm.set_bodies([a for a, _ in d.ranges], [b - a for a, b in d.ranges], d.kinds, d.centre0)
+        self._any_dynamic = 2 in d.kinds
         if self._any_dynamic:
-            self._warn_light_bodies(bodies, ranges)
-            rotate, params, state = np.zeros(len(bodies), np.int32), np.zeros((len(bodies), 32)), np.zeros((len(bodies), 16))
-            for i, body in enumerate(bodies):
-                if body.dynamics is not None:
-                    rotate[i], params[i], state[i] = body.dynamics.native()
-            ibm.set_dynamics(rotate, params, state)
-            virtual = np.array([(0.0, 0.0) if body.dynamics is None else body.dynamics.virtual() for body in bodies])
-            if (virtual > 0.0).any():
-                ibm.set_virtual_mass(virtual[:, 0], virtual[:, 1])
+            self._warn_light_bodies(bodies, d.ranges)
+            ibm.set_dynamics(d.rotate, d.params, d.state)
+            if (d.virtual > 0.0).any():
+                ibm.set_virtual_mass(d.virtual[:, 0], d.virtual[:, 1])
         self._bodies = bodies
-        self._body_centre0 = centre0
+        self._body_centre0 = d.centre0
+        self._body_radius = d.radius
         self._next_timestep = 0  # (body_poses: a new declaration starts over, for prescribed bodies as for free ones)
-        self._any_moving = any(body.motion is not None and b > a for body, (a, b) in zip(bodies, ranges))
+        self._any_prescribed = any(body.motion is not None and b > a for body, (a, b) in zip(bodies, d.ranges))
         self._apply_contact()
 
     def set_contact(self, range, stiffness, wall_stiffness=None, box=None):
@@ -267,8 +234,7 @@ class IBMStepper(IncompressibleNavierStokesStepper):
     def _apply_contact(self):
         if self._contact is None or not self._any_dynamic:
             return
-        radius = [0.0 if body.contact_radius is None else body.contact_radius for body in self._bodies]
-        self._ibm_native().set_contact(radius, *self._contact)
+        self._ibm_native().set_contact(self._body_radius, *self._contact)
 
     def body_contact_forces(self):
         """(n_bodies, 3) float64: the contact force on every body in the LAST call, read from the device now (zero for bodies that
@@ -329,7 +295,7 @@ class IBMStepper(IncompressibleNavierStokesStepper):
         if status:
             bad = [i for i in range(len(self._bodies)) if status >> i & 1]
             raise RuntimeError(f"body_poses: the state of bodies {bad} stopped being finite (loads too large for the explicit integrator?)")
-        if self._any_moving:
+        if self._any_prescribed:
             staged = self._poses(self._next_timestep, 1)[0]
             for i, body in enumerate(self._bodies):
                 if body.motion is not None:
@@ -340,7 +306,7 @@ class IBMStepper(IncompressibleNavierStokesStepper):
     def hip_implementation(self, f_0, f_1, vertices, areas, velocities, bc_mask, missing_mask, omega, timestep):
         self._set_markers(vertices, areas, velocities)
         self._stage(timestep, 1)
-        if self._any_moving:
+        if self._any_prescribed:
             self._ibm_native().stage_poses(timestep, self._poses(timestep, 1))
         self._ibm_native().step(f_0, f_1, bc_mask, missing_mask, omega, timestep)
         self._next_timestep = int(timestep) + 1
@@ -364,11 +330,11 @@ class IBMStepper(IncompressibleNavierStokesStepper):
             if self._time_dependent_bcs():
                 for k in range(n_steps):
                     self._stage(first_timestep + k, 1)
-                    if self._any_moving:
+                    if self._any_prescribed:
                         ibm.stage_poses(first_timestep + k, self._poses(first_timestep + k, 1))
                     ibm.step(cur, oth, bc_mask, missing_mask, omega, first_timestep + k)
                     cur, oth = oth, cur
-            elif self._any_moving:
+            elif self._any_prescribed:
                 chunk, done = self._pose_chunk(), 0
                 poses = self._poses(first_timestep, min(chunk, n_steps))
                 while done < n_steps:
