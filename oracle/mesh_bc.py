@@ -178,7 +178,7 @@ def aabb_close_solid(shape, vertices, close_voxels):
         t = orc._tri_box_setup(v)
         if t is None:
             continue
-        lo = np.maximum(np.floor(v.min(axis=0)).astype(int) - 1 + tl, 0)
+        lo = np.maximum(np.ceil(v.min(axis=0)).astype(int) - 1 + tl, 0)  # voxels touching the bounding box (wp.mesh_query_aabb)
         hi = np.minimum(np.floor(v.max(axis=0)).astype(int) + tl, np.array(pshape) - 1)
         for i in range(lo[0], hi[0] + 1):
             for j in range(lo[1], hi[1] + 1):

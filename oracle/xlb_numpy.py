@@ -799,7 +799,9 @@ def mesh_mask_aabb(shape, lat, bc_id, vertices, bc_mask, missing_mask):
         t = _tri_box_setup(v)
         if t is None:
             continue
-        lo = np.maximum(np.floor(v.min(axis=0)).astype(int) - 1, 0)
+        # the voxels [i, i + 1] that touch the triangle's bounding box, the candidates of wp.mesh_query_aabb(low, low + 1)
+        # (mesh_boundary_masker.py:135-154); the overlap test is only exact for those
+        lo = np.maximum(np.ceil(v.min(axis=0)).astype(int) - 1, 0)
         hi = np.minimum(np.floor(v.max(axis=0)).astype(int), np.array(shape) - 1)
         for i in range(lo[0], hi[0] + 1):
             for j in range(lo[1], hi[1] + 1):

@@ -91,6 +91,31 @@ def max_ulp_diff(a, b):
     return int(np.abs(ia - ib).max())
 
 
+def mesh_zoo():
+    """{name: (vertices, grid shape)}: the procedural meshes of the mesh-voxeliser tests (tests/_mesh_ref.py holds the pieces).
+    All but `integer_box` are in generic position: no vertex coordinate and no face plane on an integer or on k + 0.5, so that
+    few links and voxels sit on a decision boundary.  The grids are multiples of no tile or block size."""
+    import _mesh_ref as mr
+
+    rot = mr.rotation()
+    big, mid, small = (18, 16, 14), (17, 13, 11), (9, 10, 8)
+    ctr = np.array([8.83, 7.87, 6.91])
+    sphere = mr.rotated(icosphere(ctr, 4.23, 2), ctr, rot)  # 320 triangles: more than one 256-thread block
+    generic = mr.rotated(mr.box((5.63, 4.71, 3.77), (11.91, 10.23, 9.39)), ctr, mr.rotation(angle=0.4))
+    return {
+        "sphere2": (sphere, big),
+        "torus": (mr.torus(ctr, 4.63, 1.71, 24, 12, mr.rotation(angle=0.3)), big),  # 576 triangles, fluid cells in the hole
+        "box": (generic, big),
+        "box_low_faces": (mr.box((0.0, 0.0, 0.0), (5.37, 4.61, 3.29)), small),  # vertex coordinates 0.0 on the three low faces
+        "box_high_faces": (mr.box((11.31, 7.43, 5.63), (16.995, 12.993, 10.991)), mid),  # ends within 0.01 of the high faces
+        "plate": (mr.box((3.31, 2.43, 5.57), (13.63, 10.71, 5.87)), mid),  # 0.3 thick, between two planes of cell centres
+        "two_boxes": (np.concatenate([mr.box((3.23, 4.31, 3.37), (7.62, 11.27, 9.71)), mr.box((8.32, 5.19, 4.13), (13.41, 10.63, 10.29))]), big),
+        "sphere2_inward": (mr.inward(sphere), big),
+        "box_zero_area": (mr.with_zero_area_triangle(generic), big),
+        "integer_box": (mr.box((3.0, 4.0, 2.0), (7.0, 8.0, 6.0)), small),  # degenerate on purpose: never compared with the fp64 reference
+    }
+
+
 def icosphere(center, radius, subdivisions=2):
     """triangle soup (3 n, 3) of a sphere, counter-clockwise seen from outside, built procedurally (no STL reader here)"""
     t = (1.0 + 5.0**0.5) / 2.0

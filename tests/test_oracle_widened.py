@@ -6,19 +6,7 @@ import numpy as np
 
 from oracle import xlb_numpy as orc
 
-
-def icosphere(center, radius, subdivisions=1):
-    t = (1.0 + 5.0**0.5) / 2.0
-    v = np.array([[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t], [t, 0, -1], [t, 0, 1], [-t, 0, -1], [-t, 0, 1]], float)
-    f = [[0, 11, 5], [0, 5, 1], [0, 1, 7], [0, 7, 10], [0, 10, 11], [1, 5, 9], [5, 11, 4], [11, 10, 2], [10, 7, 6], [7, 1, 8], [3, 9, 4], [3, 4, 2], [3, 2, 6],
-         [3, 6, 8], [3, 8, 9], [4, 9, 5], [2, 4, 11], [6, 2, 10], [8, 6, 7], [9, 8, 1]]
-    tris = v[np.array(f)]
-    for _ in range(subdivisions):
-        a, b, c = tris[:, 0], tris[:, 1], tris[:, 2]
-        ab, bc, ca = (a + b) / 2, (b + c) / 2, (c + a) / 2
-        tris = np.concatenate([np.stack([a, ab, ca], 1), np.stack([b, bc, ab], 1), np.stack([c, ca, bc], 1), np.stack([ab, bc, ca], 1)])
-    tris = tris / np.linalg.norm(tris, axis=2, keepdims=True)
-    return (np.asarray(center) + radius * tris).reshape(-1, 3).astype(np.float32)
+from _util import icosphere
 
 
 def test_aabb_voxelisation_gives_a_closed_shell_at_the_right_radius():
@@ -27,7 +15,7 @@ def test_aabb_voxelisation_gives_a_closed_shell_at_the_right_radius():
     lat = orc.Lattice("D3Q19")
     shape = (14, 13, 12)
     c, r = np.array([6.3, 6.6, 5.9]), 3.1
-    bc, mm = orc.mesh_mask_aabb(shape, lat, 7, icosphere(c, r), np.zeros((1,) + shape, np.uint8), np.zeros((19,) + shape, bool))
+    bc, mm = orc.mesh_mask_aabb(shape, lat, 7, icosphere(c, r, 1), np.zeros((1,) + shape, np.uint8), np.zeros((19,) + shape, bool))
     solid = bc[0] == orc.BC_SOLID
     lab, _ = ndimage.label(~solid)
     assert lab[6, 6, 5] != lab[0, 0, 0]  # inside and outside are separated
@@ -49,7 +37,7 @@ def test_ray_voxelisation_links_are_symmetric_and_straddle_the_surface():
     lat = orc.Lattice("D3Q19")
     shape = (12, 12, 12)
     c, r = np.array([5.8, 6.1, 5.7]), 2.7
-    bc, mm = orc.mesh_mask_ray(shape, lat, 3, icosphere(c, r), np.zeros((1,) + shape, np.uint8), np.zeros((19,) + shape, bool))
+    bc, mm = orc.mesh_mask_ray(shape, lat, 3, icosphere(c, r, 1), np.zeros((1,) + shape, np.uint8), np.zeros((19,) + shape, bool))
     assert not (bc[0] == orc.BC_SOLID).any()
     x, y, z = np.where(bc[0] == 3)
     rad = np.linalg.norm(np.stack([x, y, z], 1) + 0.5 - c, axis=1)

@@ -659,7 +659,10 @@ static __global__ void k_mesh_solid(const float* verts /*[n_tri][3][3]*/, int64_
   const int ext[3] = {nx, ny, nz};
   for (int a = 0; a < 3; ++a) {
     const float mn = fminf(v[a], fminf(v[3 + a], v[6 + a])), mx = fmaxf(v[a], fmaxf(v[3 + a], v[6 + a]));
-    lo[a] = max(0, (int)floorf(mn) - 1);
+    // voxels [i, i + 1] that touch [mn, mx]: i + 1 >= mn and i <= mx, the candidates of wp.mesh_query_aabb(low, low + 1)
+    // (mesh_boundary_masker.py:135-154).  The overlap test is only exact for those: one cell further down, a voxel beyond an
+    // acute corner passes every edge function without touching the triangle.
+    lo[a] = max(0, (int)ceilf(mn) - 1);
     hi[a] = min(ext[a] - 1, (int)floorf(mx));
   }
   for (int i = lo[0]; i <= hi[0]; ++i)
@@ -941,7 +944,7 @@ static __global__ void k_mesh_solid_padded(const float* verts, int64_t n_tri, ui
   const int ext[3] = {px, py, pz};
   for (int a = 0; a < 3; ++a) {
     const float mn = fminf(v[a], fminf(v[3 + a], v[6 + a])), mx = fmaxf(v[a], fmaxf(v[3 + a], v[6 + a]));
-    lo[a] = max(0, (int)floorf(mn) - 1 + pad);
+    lo[a] = max(0, (int)ceilf(mn) - 1 + pad);  // the voxels that touch the bounding box, as in k_mesh_solid
     hi[a] = min(ext[a] - 1, (int)floorf(mx) + pad);
   }
   for (int i = lo[0]; i <= hi[0]; ++i)
