@@ -24,6 +24,9 @@ pytestmark = pytest.mark.gpu
 
 CASES = [("D2Q9", (100, 100)), ("D3Q19", (50, 50, 50)), ("D3Q27", (50, 50, 50))]
 SMALL = [("D2Q9", (50, 50)), ("D3Q19", (20, 20, 20)), ("D3Q27", (20, 20, 20)), ("D3Q19", (6, 10, 18))]
+POLICIES = ["FP32FP32", "FP32FP16", "FP64FP64", "FP64FP32", "FP64FP16"]
+# (name, shape, policy) over SMALL[:3] x POLICIES; the FP32FP32 cases keep the ids they had before the policies were added
+SMALL_BY_POLICY = [pytest.param(n, s, p, id=f"{n}-shape{i}" + ("" if p == "FP32FP32" else f"-{p}")) for i, (n, s) in enumerate(SMALL[:3]) for p in POLICIES]
 
 
 @pytest.mark.parametrize("name", ["D2Q9", "D3Q19", "D3Q27"])
@@ -133,27 +136,31 @@ def test_stream_is_roll(name, shape):
 
 
 @pytest.mark.parametrize("name,shape", SMALL[:3])
-@pytest.mark.parametrize("policy", ["FP32FP32", "FP64FP64"])
+@pytest.mark.parametrize("policy", POLICIES)
 def test_operators_bit_exact_vs_oracle(name, shape, policy):
+    """f, feq and the collided populations are fields of the STORE type, rho / u / pi of the compute type: every operator widens what it
+    reads to the compute type, computes there and rounds what it writes (ops_kernels.hpp: load_rt / store_rt)."""
     vs, pp = init_hip(name, policy)
     lat = orc.Lattice(name)
-    T = orc.compute_dtype(policy)
+    T, S = orc.compute_dtype(policy), orc.store_dtype(policy)
     grid = grid_factory(shape)
     f_np = orc.perturbed_init(shape, lat, policy, seed=5, amp_rho=0.05, amp_u=0.05)
     f_np = (f_np + 0.001 * np.random.default_rng(2).standard_normal(f_np.shape)).astype(f_np.dtype)  # off equilibrium
+    assert f_np.dtype == S
     f = grid.create_field(vs.q).assign(f_np)
     rho = grid.create_field(1, dtype=pp.compute_precision)
     u = grid.create_field(vs.d, dtype=pp.compute_precision)
     Macroscopic()(f, rho, u)
     o_rho, o_u = orc.macroscopic(f_np.astype(T), lat)
-    assert np.array_equal(rho.numpy(), o_rho) and np.array_equal(u.numpy(), o_u)
+    assert rho.numpy().dtype == T and np.array_equal(rho.numpy(), o_rho) and np.array_equal(u.numpy(), o_u)
     feq = QuadraticEquilibrium()(rho, u, grid.create_field(vs.q))
     o_feq = orc.equilibrium(o_rho, o_u, lat, T)
-    assert np.array_equal(feq.numpy(), o_feq.astype(f_np.dtype))
+    assert feq.numpy().dtype == S and np.array_equal(feq.numpy(), o_feq.astype(f_np.dtype))
+    o_feq = o_feq.astype(S).astype(T)  # what the collisions read back from the feq field (the same numbers when S is T)
     out = BGK()(f, feq, grid.create_field(vs.q), 1.3)
     assert np.array_equal(out.numpy(), orc.bgk(f_np.astype(T), o_feq, 1.3).astype(f_np.dtype))
     pi = SecondMoment()(f, grid.create_field(vs.d * (vs.d + 1) // 2, dtype=pp.compute_precision))
-    assert np.array_equal(pi.numpy(), orc.second_moment(f_np.astype(T), lat))
+    assert pi.numpy().dtype == T and np.array_equal(pi.numpy(), orc.second_moment(f_np.astype(T), lat))
     if name != "D3Q19":
         out = KBC()(f, feq, grid.create_field(vs.q), 1.7)
         assert np.array_equal(out.numpy(), orc.kbc(f_np.astype(T), o_feq, 1.7, lat).astype(f_np.dtype))
@@ -211,10 +218,11 @@ def test_masker_interior_halfway_padding_and_overwrite_order(name, shape):
     assert np.array_equal(missing_mask.numpy(), o_mm.astype(np.uint8))
 
 
-@pytest.mark.parametrize("name,shape", SMALL[:3])
-def test_equilibrium_bc(name, shape):
+@pytest.mark.parametrize("name,shape,policy", SMALL_BY_POLICY)
+def test_equilibrium_bc(name, shape, policy):
     # reference tests/boundary_conditions/bc_equilibrium/test_bc_equilibrium_warp.py
-    vs, pp = init_hip(name)
+    vs, pp = init_hip(name, policy)
+    T, S = orc.compute_dtype(policy), orc.store_dtype(policy)
     grid, f_0, f_1, missing_mask, bc_mask = create_nse_fields(shape)
     indices = sphere(shape)
     bc = EquilibriumBC(rho=1.0, u=(0.0,) * vs.d, indices=indices)
@@ -222,22 +230,30 @@ def test_equilibrium_bc(name, shape):
     f_pre = grid.create_field(cardinality=vs.q)
     f_post = grid.create_field(cardinality=vs.q, fill_value=2.0)
     f = bc(f_pre, f_post, bc_mask, missing_mask).numpy()
+    assert f.dtype == S
     inside = bc_mask.numpy()[0] == bc.id
+    # feq(1, 0) in the compute type, rounded to the store type: w_i to the store type's precision
+    exp = orc.equilibrium(np.ones((1, 1), T), np.zeros((vs.d, 1), T), orc.Lattice(name), T).astype(S)
     for i in range(vs.q):
-        assert np.allclose(f[i][inside], vs._w[i])
+        assert np.allclose(f[i][inside], vs._w[i], rtol=float(np.finfo(S).eps))
+        assert np.all(f[i][inside] == exp[i, 0])
         assert np.allclose(f[i][~inside], 2.0)
 
 
-@pytest.mark.parametrize("name,shape", SMALL[:3])
-def test_fullway_and_halfway_bc_vs_oracle(name, shape):
+@pytest.mark.parametrize("name,shape,policy", SMALL_BY_POLICY)
+def test_fullway_and_halfway_bc_vs_oracle(name, shape, policy):
     # reference tests/boundary_conditions/bc_fullway_bounce_back/* (with the inside check asserted)
-    vs, pp = init_hip(name)
+    vs, pp = init_hip(name, policy)
     lat = orc.Lattice(name)
+    T, S = orc.compute_dtype(policy), orc.store_dtype(policy)
     rng = np.random.default_rng(4)
-    a_pre = rng.random((vs.q,) + shape, dtype=np.float32)
-    a_post = rng.random((vs.q,) + shape, dtype=np.float32)
+    a_pre = rng.random((vs.q,) + shape, dtype=np.float32).astype(S)
+    a_post = rng.random((vs.q,) + shape, dtype=np.float32).astype(S)
+    # (the second moving wall: no component is a number of any store type, nor is a sum of two — the wall term is summed in the STORE
+    # type, bc_halfway_bounce_back.py:97-102, which the mixed policies tell from a sum in the compute type)
     for cls, kind, kw in ((FullwayBounceBackBC, orc.KIND_FULLWAY_BB, {}), (HalfwayBounceBackBC, orc.KIND_HALFWAY_BB, {}),
                           (HalfwayBounceBackBC, orc.KIND_HALFWAY_BB, {"prescribed_value": (0.03,) + (0.01,) * (vs.d - 1)}),
+                          (HalfwayBounceBackBC, orc.KIND_HALFWAY_BB, {"prescribed_value": (0.0123, 0.0071, 0.0034)[: vs.d]}),
                           (DoNothingBC, orc.KIND_DO_NOTHING, {})):
         grid, f_0, f_1, missing_mask, bc_mask = create_nse_fields(shape)
         indices = sphere(shape)
@@ -248,10 +264,13 @@ def test_fullway_and_halfway_bc_vs_oracle(name, shape):
         out = bc(f_pre, f_post, bc_mask, missing_mask).numpy()
         obc = orc.BC(kind, bc.id, indices, u_wall=kw.get("prescribed_value"))
         o_bm, o_mm = orc.build_masks(shape, lat, [obc])
-        exp = orc.apply_bc(obc, a_pre, a_post, o_bm, o_mm, lat, "FP32FP32")
-        assert np.array_equal(out, exp), (cls.__name__, kw)
+        exp = orc.apply_bc(obc, a_pre.astype(T), a_post.astype(T), o_bm, o_mm, lat, policy).astype(S)
+        assert out.dtype == S and np.array_equal(out, exp), (cls.__name__, kw)
         inside = o_bm[0] == bc.id
         assert np.array_equal(out[:, ~inside], a_post[:, ~inside])
+        if "prescribed_value" in kw:  # the wall's motion enters the result
+            at_rest = orc.apply_bc(orc.BC(kind, bc.id, indices), a_pre.astype(T), a_post.astype(T), o_bm, o_mm, lat, policy).astype(S)
+            assert not np.array_equal(exp, at_rest)
 
 
 def test_operator_dispatch_errors():

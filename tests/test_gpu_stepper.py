@@ -203,23 +203,35 @@ def test_all_bc_kinds_in_one_step_vs_oracle(shape, vec):
         get_context().set_option("vec", 0)
 
 
-@pytest.mark.parametrize("walls_cls", [FullwayBounceBackBC, HalfwayBounceBackBC])
-def test_ghost_plane_protocol_single_rank(walls_cls):
+# (lattice, policy, walls): ghost planes of 4-, 2- and 8-byte elements; the D3Q19 FP32FP32 cases keep the ids they had before the others came
+GHOST_CASES = [pytest.param(la, po, w, id=w.__name__ + ("" if (la, po) == ("D3Q19", "FP32FP32") else f"-{la}-{po}"))
+               for la, po in (("D3Q19", "FP32FP32"), ("D3Q19", "FP32FP16"), ("D3Q19", "FP64FP64"), ("D3Q27", "FP64FP32"))
+               for w in (FullwayBounceBackBC, HalfwayBounceBackBC)]
+
+
+@pytest.mark.parametrize("lattice,policy,walls_cls", GHOST_CASES)
+def test_ghost_plane_protocol_single_rank(lattice, policy, walls_cls):
     """Fields with ghost x-planes + self ring exchange (the slab protocol on one rank) give the
-    same bits as the plain periodic kernel, with and without interior/edge splitting."""
+    same bits as the plain periodic kernel, with and without interior/edge splitting — and all of them the oracle's."""
     results = []
+    shape = (10, 8, 16)
     for cfg in (None, {"halo": 1}, {"halo": 2}):
-        grid, bcs, lat, obcs = hip_cavity_3d((10, 8, 16), walls_cls, backend_config=cfg)
+        grid, bcs, lat, obcs = hip_cavity_3d(shape, walls_cls, lattice=lattice, policy=policy, backend_config=cfg)
         assert grid.halo == (cfg or {}).get("halo", 0)
         stepper = IncompressibleNavierStokesStepper(grid=grid, boundary_conditions=bcs)
         f_0, f_1, bc_mask, missing_mask = stepper.prepare_fields()
-        f_0.assign(orc.perturbed_init((10, 8, 16), lat, seed=3))
+        f_np = orc.perturbed_init(shape, lat, policy, seed=3)
+        f_0.assign(f_np)
         for overlap in (1, 0):
             get_context().set_option("overlap", overlap)
             f_0, f_1 = stepper.run(f_0, f_1, bc_mask, missing_mask, 1.4, 3)
         get_context().set_option("overlap", 1)
         results.append(f_0.numpy())
     assert np.array_equal(results[0], results[1]) and np.array_equal(results[0], results[2])
+    o_bm, o_mm = orc.build_masks(shape, lat, obcs)
+    exp = orc.run(f_np, o_bm, o_mm, obcs, 1.4, lat, 6, policy)
+    assert results[0].dtype == exp.dtype
+    assert np.array_equal(results[0], exp), f"not bit-exact: max ulp {max_ulp_diff(results[0], exp)}"
 
 
 def test_stepper_argument_errors():
