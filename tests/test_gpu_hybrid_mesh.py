@@ -296,3 +296,130 @@ def test_hybrid_bc_standalone_operator_vs_oracle():
         o_bm, o_mm = orc.build_masks(shape, lat, [obc])
         exp = mb.apply_hybrid(obc, pre, post, o_bm, o_mm, lat, "FP32FP32")
         assert np.array_equal(out.numpy(), exp)
+
+
+# ---- the extended slow path with more than one cell per thread (the "vec" option) ---------------------------------------
+WIDE_SHAPE = (12, 10, 8)  # nz divisible by 4; the body's cells sit at z = 1 .. 6: they straddle the lane groups of 2 and of 4
+WIDE_LANES = [("D3Q19", "FP32FP32", 1), ("D3Q19", "FP32FP32", 2), ("D3Q19", "FP32FP32", 4), ("D3Q27", "FP64FP64", 1), ("D3Q27", "FP64FP64", 2)]
+_wide_cache = {}
+
+
+def single_steps(stepper, vec, f_0, f_1, bc_mask, missing_mask, omega, steps):
+    """stepper.run through the single-step kernel with `vec` cells per thread"""
+    from xlb_amd.default_config import get_context
+
+    ctx = get_context()
+    before = {k: ctx.get_option(k) for k in ("fuse2", "vec")}
+    try:
+        ctx.set_option("fuse2", 0)
+        ctx.set_option("vec", vec)
+        f_0, f_1 = stepper.run(f_0, f_1, bc_mask, missing_mask, omega, steps)
+        return f_0.numpy()
+    finally:
+        for k, v in before.items():
+            ctx.set_option(k, v)
+
+
+def wide_reference(key, make):
+    """the oracle's result of a case, computed once for all lane widths and left unchanged"""
+    if key not in _wide_cache:
+        res = make()
+        for a in res:
+            a.setflags(write=False)
+        _wide_cache[key] = res
+    return _wide_cache[key]
+
+
+@pytest.mark.parametrize("bc_method", list(KINDS))
+@pytest.mark.parametrize("lattice,policy,vec", WIDE_LANES)
+def test_hybrid_bc_on_indices_wide_lanes_vs_oracle(bc_method, lattice, policy, vec):
+    """test_hybrid_bc_on_indices_vs_oracle with a moving wall and 1, 2 and 4 cells per thread: a thread of the single-step kernel then
+    holds hybrid cells and fluid cells side by side, and more than one hybrid cell.  Bit for bit."""
+    vs, pp = init_hip(lattice, policy)
+    lat = orc.Lattice(lattice)
+    shape, u_wall, steps, omega = WIDE_SHAPE, (0.02, -0.01, 0.005), 8, 1.5
+    body = body_indices(shape)
+    assert body[2].min() == 2 and body[2].max() == 5
+    bc = HybridBC(bc_method, prescribed_value=u_wall, indices=body.tolist())
+    obc = mb.HybridBC(KINDS[bc_method], bc.id, body, u_wall=u_wall)
+    stepper = IncompressibleNavierStokesStepper(grid=grid_factory(shape), boundary_conditions=[bc])
+    f_0, f_1, bc_mask, missing_mask = stepper.prepare_fields()
+
+    def make():
+        o_bm, o_mm = orc.build_masks(shape, lat, [obc])
+        f_np = orc.perturbed_init(shape, lat, policy, seed=41, amp_rho=0.01, amp_u=0.03)
+        return o_bm, o_mm, f_np, mb.run(f_np, o_bm, o_mm, [obc], omega, lat, steps, policy)
+
+    o_bm, o_mm, f_np, exp = wide_reference(("hybrid", bc_method, lattice, policy), make)
+    assert np.array_equal(bc_mask.numpy(), o_bm) and np.array_equal(missing_mask.numpy(), o_mm.astype(np.uint8))
+    f_0.assign(f_np)
+    out = single_steps(stepper, vec, f_0, f_1, bc_mask, missing_mask, omega, steps)
+    assert np.isfinite(out).all()
+    assert np.array_equal(out, exp)
+
+
+@pytest.mark.parametrize("lattice,policy,vec", WIDE_LANES)
+def test_halfway_bc_wall_velocity_profile_wide_lanes_vs_oracle(lattice, policy, vec):
+    """The 3-D case of test_halfway_bc_wall_velocity_profile_vs_oracle (a rotating RAY-voxelised mesh sphere) on a grid with nz = 16 and
+    1, 2 and 4 cells per thread.  Bit for bit."""
+    vs, pp = init_hip(lattice, policy)
+    lat, shape, steps, omega = orc.Lattice(lattice), (18, 16, 16), 6, 1.5
+    rot, ctr = np.array([0.003, 0.0, -0.004]), np.asarray(CENTER)
+
+    def profile(cells):
+        return np.cross(rot.reshape(1, 3), (cells.astype(np.float64) - ctr.reshape(3, 1)).T).T
+
+    bc = HalfwayBounceBackBC(profile=profile, mesh_vertices=icosphere(CENTER, RADIUS, 1), voxelization_method=method_of("RAY"))
+    stepper = IncompressibleNavierStokesStepper(grid=grid_factory(shape), boundary_conditions=[bc])
+    f_0, f_1, bc_mask, missing_mask = stepper.prepare_fields()
+
+    def make():
+        z1, zq = np.zeros((1,) + shape, np.uint8), np.zeros((lat.q,) + shape, bool)
+        o_bm, o_mm = mb.mesh_mask_ray(shape, lat, bc.id, icosphere(CENTER, RADIUS, 1), z1, zq, None)[:2]
+        allc = np.stack(np.meshgrid(*[np.arange(n) for n in shape], indexing="ij")).reshape(3, -1)
+        o_b = mb.HalfwayProfileBC(bc.id, None, profile(allc).reshape((3,) + shape))
+        f_np = orc.perturbed_init(shape, lat, policy, seed=53, amp_rho=0.01, amp_u=0.02)
+        with np.errstate(all="ignore"):
+            return o_bm, o_mm, f_np, mb.run(f_np, o_bm, o_mm, [o_b], omega, lat, steps, policy)
+
+    o_bm, o_mm, f_np, exp = wide_reference(("halfway", lattice, policy), make)
+    assert np.array_equal(bc_mask.numpy(), o_bm) and np.array_equal(missing_mask.numpy(), o_mm.astype(np.uint8))
+    tagged_z = np.where((o_bm[0] == bc.id).any(axis=(0, 1)))[0]
+    assert tagged_z.min() < 4 and tagged_z.max() >= 8  # more than one lane group of 4
+    f_0.assign(f_np)
+    out = single_steps(stepper, vec, f_0, f_1, bc_mask, missing_mask, omega, steps)
+    fluid = np.broadcast_to(o_bm != BC_SOLID, out.shape)
+    assert np.isfinite(out[fluid]).all()
+    assert np.array_equal(out[fluid], exp[fluid])
+
+
+@pytest.mark.parametrize("bc_method", list(KINDS))
+@pytest.mark.parametrize("vec", [1, 2, 4])
+def test_hybrid_bc_with_distances_wide_lanes_vs_oracle(bc_method, vec):
+    """HybridBC on the RAY-voxelised mesh sphere WITH wall distances (the sparse weight table) on a grid with nz = 16 and 1, 2 and 4 cells
+    per thread: every lane of a thread looks up its own cell's weights.  Bit for bit."""
+    vs, pp = init_hip("D3Q19")
+    lat, shape, steps, omega = orc.Lattice("D3Q19"), (18, 16, 16), 6, 1.3
+    b_s = HybridBC(bc_method, mesh_vertices=icosphere(CENTER, RADIUS, 1), voxelization_method=method_of("RAY"), use_mesh_distance=True)
+    stepper = IncompressibleNavierStokesStepper(grid=grid_factory(shape), boundary_conditions=[b_s])
+    f_0, f_1, bc_mask, missing_mask = stepper.prepare_fields()
+
+    def mask():
+        z1, zq = np.zeros((1,) + shape, np.uint8), np.zeros((lat.q,) + shape, bool)
+        return mb.mesh_mask_ray(shape, lat, b_s.id, icosphere(CENTER, RADIUS, 1), z1, zq, np.zeros((lat.q,) + shape, np.float32))
+
+    o_bm, o_mm, o_d = wide_reference(("dist-mask",), mask)
+
+    def make():
+        f_np = orc.perturbed_init(shape, lat, seed=43, amp_rho=0.01, amp_u=0.02)
+        with np.errstate(all="ignore"):
+            return f_np, mb.run(f_np, o_bm, o_mm, [mb.HybridBC(KINDS[bc_method], b_s.id, None, distances=o_d)], omega, lat, steps)
+
+    f_np, exp = wide_reference(("dist", bc_method), make)
+    assert np.array_equal(bc_mask.numpy(), o_bm) and np.array_equal(missing_mask.numpy(), o_mm.astype(np.uint8))
+    assert (o_d != 0).sum() > 100
+    f_0.assign(f_np)
+    out = single_steps(stepper, vec, f_0, f_1, bc_mask, missing_mask, omega, steps)
+    fluid = np.broadcast_to(o_bm != BC_SOLID, out.shape)
+    assert np.isfinite(out[fluid]).all()
+    assert np.array_equal(out[fluid], exp[fluid])

@@ -449,3 +449,81 @@ def test_end_plane_pairs_follow_the_mask_of_each_run():
         ctx.set_option("fuse2", 1)
     for k, (g, e) in enumerate(zip(got, exp)):
         assert np.array_equal(g, e), f"leg {k}: {int((g != e).sum())} values differ from the single-step path"
+
+
+# ---- a wall cell directly behind an ExtrapolationOutflowBC cell ---------------------------------------------------------------
+@pytest.mark.parametrize("wall", ["hybrid_bounceback_regularized", "hybrid_bounceback_grads", "hybrid_nonequilibrium_regularized", "halfway_profile"])
+@pytest.mark.parametrize("lattice,policy", [("D3Q19", "FP32FP32"), ("D3Q27", "FP64FP32")])
+def test_wall_cell_behind_an_outflow_cell_vs_oracle(lattice, policy, wall):
+    """The outflow pass extrapolates from the POST-STREAM populations of the cell behind each outflow cell, i.e. after that cell's own
+    streaming-step BC whatever its kind (nse_stepper.py:246-272; oracle/mesh_bc.py:step).  Here that cell belongs to a HybridBC body or
+    to a halfway wall with a velocity profile: a 2 x 2 x 2 body at x = nx - 4, nx - 3 whose padded cells reach x = nx - 2.  Six single
+    steps, bit for bit.  The two regularising hybrid methods rewrite every population of the wall cell, so they pin the outflow pass;
+    Grad's method and the profile wall rewrite only its missing directions (c_x = +1), which the extrapolation (c_x = -1) does not
+    read: those cases pin the step kernel next to an outflow face, not the pass."""
+    from oracle import mesh_bc as mb
+    from xlb_amd.default_config import get_context
+    from xlb_amd.operator.boundary_condition import HybridBC
+
+    shape, steps, omega = (10, 8, 8), 6, 1.4
+    vs, pp = init_hip(lattice, policy)
+    lat = orc.Lattice(lattice)
+    grid = grid_factory(shape)
+    box_ne = grid.bounding_box_indices(remove_edges=True)
+    body = np.array(np.meshgrid([6, 7], [3, 4], [3, 4], indexing="ij")).reshape(3, -1)
+    u_in, u_wall = (0.03, 0.0, 0.0), (0.0, 0.01, -0.02)
+    uw_field = np.broadcast_to(np.asarray(u_wall).reshape(3, 1, 1, 1), (3,) + shape)
+    b_in = RegularizedBC("velocity", prescribed_value=u_in, indices=box_ne["left"])
+    b_out = ExtrapolationOutflowBC(indices=box_ne["right"])
+    o_in = orc.BC(orc.KIND_REGULARIZED_VELOCITY, b_in.id, box_ne["left"], prescribed=u_in)
+    o_out = orc.BC(orc.KIND_EXTRAPOLATION_OUTFLOW, b_out.id, box_ne["right"])
+    if wall == "halfway_profile":
+        b_s = HalfwayBounceBackBC(profile=lambda cells: np.broadcast_to(np.asarray(u_wall).reshape(3, 1), cells.shape), indices=body.tolist())
+        o_s = mb.HalfwayProfileBC(b_s.id, body, uw_field)
+    else:
+        b_s = HybridBC(wall[len("hybrid_"):], prescribed_value=u_wall, indices=body.tolist())
+        o_s = mb.HybridBC(wall, b_s.id, body, u_wall=u_wall)
+    stepper = IncompressibleNavierStokesStepper(grid=grid, boundary_conditions=[b_in, b_out, b_s])
+    f_0, f_1, bc_mask, missing_mask = stepper.prepare_fields()
+    o_bm, o_mm = orc.build_masks(shape, lat, [o_in, o_out, o_s])
+    assert np.array_equal(bc_mask.numpy(), o_bm) and np.array_equal(missing_mask.numpy(), o_mm.astype(np.uint8))
+    behind = o_bm[0, -2][o_bm[0, -1] == b_out.id]
+    assert (behind == b_s.id).sum() >= 4  # wall cells directly behind outflow cells
+    f_np = orc.perturbed_init(shape, lat, policy, seed=59, amp_rho=0.01, amp_u=0.02)
+    f_0.assign(f_np)
+    exp = mb.run(f_np, o_bm, o_mm, [o_in, o_out, o_s], omega, lat, steps, policy)
+    assert np.isfinite(exp).all()
+    ctx = get_context()
+    try:
+        ctx.set_option("fuse2", 0)
+        a, b = stepper.run(f_0, f_1, bc_mask, missing_mask, omega, steps)
+        out = a.numpy()
+    finally:
+        ctx.set_option("fuse2", 1)
+    assert np.isfinite(out).all()
+    assert np.array_equal(out, exp), f"max ulp {max_ulp_diff(out, exp)}, max abs {np.abs(out.astype(np.float64) - exp).max()}"
+
+
+def test_standalone_operator_with_a_profile_fp64_compute_fp32_store():
+    """bc(f_pre, f_post, bc_mask, missing_mask) of a Zou-He inlet with per-cell values in FP64FP32: the operator's constants and
+    its profile table reach the kernel in the compute dtype (test_flow_past_sphere_setup_vs_oracle covers FP32FP32 and FP64FP64)."""
+    shape, policy = (8, 10, 12), "FP64FP32"
+    vs, pp = init_hip("D3Q19", policy)
+    lat = orc.Lattice("D3Q19")
+    grid = grid_factory(shape)
+    box_ne = grid.bounding_box_indices(remove_edges=True)
+    prof = parabolic_inlet(shape) * (1.0 + 1e-9)  # (values that are no fp32 numbers)
+    for cls, kind in ((ZouHeBC, orc.KIND_ZOUHE_VELOCITY), (RegularizedBC, orc.KIND_REGULARIZED_VELOCITY)):
+        b_in = cls("velocity", profile=lambda: prof, indices=box_ne["left"])
+        obc = orc.BC(kind, b_in.id, box_ne["left"], prescribed=prof)
+        stepper = IncompressibleNavierStokesStepper(grid=grid, boundary_conditions=[b_in])
+        f_0, f_1, bc_mask, missing_mask = stepper.prepare_fields()
+        o_bm, o_mm = orc.build_masks(shape, lat, [obc])
+        assert np.array_equal(bc_mask.numpy(), o_bm) and np.array_equal(missing_mask.numpy(), o_mm.astype(np.uint8))
+        post = (lat.w[:, None, None, None] * (1 + 0.05 * np.random.default_rng(9).standard_normal((19,) + shape))).astype(np.float32)
+        f_1.assign(post)
+        got = b_in(f_0, f_1, bc_mask, missing_mask).numpy()
+        with np.errstate(all="ignore"):
+            e = orc.apply_bc(obc, post.astype(np.float64), post.astype(np.float64), o_bm, o_mm, lat, policy)
+        assert got.dtype == np.float32 and np.array_equal(got, e.astype(np.float32))
+        assert not np.array_equal(got, post)

@@ -489,8 +489,6 @@ int xlbhip_momentum_transfer(xlbhip_ctx* c, int lattice, int cdt, const xlbhip_b
   XLB_REQUIRE(bc->kind == XLBHIP_BC_HALFWAY_BB || bc->kind == XLBHIP_BC_FULLWAY_BB,
               "momentum_transfer: the no-slip BC must be a halfway or fullway bounce-back (kind %d given)", bc->kind);
   XLB_REQUIRE(cdt == XLBHIP_F32 || cdt == XLBHIP_F64, "bad compute dtype %d", cdt);
-  BcValues vals;
-  std::memcpy(vals.v, bc->values, sizeof(vals.v));
   DeviceBuf dforce;
   XLB_HIP(dforce.alloc(3 * sizeof(double)));
   XLB_HIP(hipMemsetAsync(dforce.get(), 0, 3 * sizeof(double), c->stream));
@@ -498,8 +496,8 @@ int xlbhip_momentum_transfer(xlbhip_ctx* c, int lattice, int cdt, const xlbhip_b
   const int wall = bc->kind == XLBHIP_BC_HALFWAY_BB ? 1 : 0;
   const int rc = by_lattice(lattice, [&](auto L) {
     return by_compute(cdt, [&](auto T) {
-      hipLaunchKernelGGL((k_momentum_transfer<decltype(L), decltype(T)>), blocks_for(n), 256, 0, c->stream, view(f_0), view(bcm), view(miss), dims(f_0),
-                         bc->id, vals, wall, dforce.get<double>());
+      hipLaunchKernelGGL((k_momentum_transfer<decltype(L), decltype(T)>), blocks_for(n), BC_BLOCK, 0, c->stream, view(f_0), view(bcm), view(miss), dims(f_0),
+                         bc->id, bc_values<decltype(T)>(bc->values), wall, dforce.get<double>());
       XLB_HIP(hipGetLastError());
       return 0;
     });
@@ -603,52 +601,50 @@ int xlbhip_apply_bc_profile(xlbhip_ctx* c, int lattice, int cdt, const xlbhip_bc
   XLB_REQUIRE(same_grid(f_pre, f_post), "bc: grids differ");
   touch(f_post);
   XLB_REQUIRE(bc->id >= 1 && bc->id <= 255, "bc id %d out of range", bc->id);
-  XLB_REQUIRE(bc->kind >= XLBHIP_BC_EQUILIBRIUM && bc->kind <= XLBHIP_BC_HYBRID_NEQ_REGULARIZED, "unknown bc kind %d (wall-velocity tables live in the stepper)", bc->kind);
-  XLB_REQUIRE(bc->kind < XLBHIP_BC_HYBRID_BB_REGULARIZED || (lattice_d(lattice) == 3 && bc->values[4] == 0.0),
+  XLB_REQUIRE(bc_is_known(bc->kind) && bc->kind != XLBHIP_BC_HALFWAY_BB_PROFILE, "unknown bc kind %d (wall-velocity tables live in the stepper)", bc->kind);
+  XLB_REQUIRE(!bc_is_hybrid(bc->kind) || (lattice_d(lattice) == 3 && bc->values[4] == 0.0),
               "HybridBC as a stand-alone operator: 3-D lattices, without mesh distances (those live in the stepper: xlbhip_stepper_set_bc_distances)");
-  if (bc->kind == XLBHIP_BC_HALFWAY_BB || bc->kind >= XLBHIP_BC_ZOUHE_VELOCITY)
+  if (bc_reads_missing(bc->kind))
     XLB_REQUIRE(miss && miss->dtype == XLBHIP_MISSING && same_grid(miss, f_post), "bc: this boundary condition needs a missing_mask field");
   XLB_REQUIRE(cdt == XLBHIP_F32 || cdt == XLBHIP_F64, "bad compute dtype %d", cdt);
-  BcValues vals;
-  std::memcpy(vals.v, bc->values, sizeof(vals.v));
   const size_t n = f_post->cells();
-  // per-cell prescribed values (sorted by storage cell): uploaded for this call only — the stand-alone operator is
-  // not on the hot path
+  // per-cell prescribed values (sorted by storage cell, in the compute dtype): uploaded for this call only — the stand-alone
+  // operator is not on the hot path
+  std::vector<uint32_t> keys;
+  std::vector<char> image;
+  DeviceScratch scratch(c->stream);  // (declared after the host vectors: it drains the stream before they die)
   uint32_t* dk = nullptr;
-  double* dv = nullptr;
+  char* dv = nullptr;
   if (n_prof > 0) {
     XLB_REQUIRE(storage_cells && values, "null profile table");
-    XLB_REQUIRE(bc->kind >= XLBHIP_BC_ZOUHE_VELOCITY && bc->kind <= XLBHIP_BC_REGULARIZED_PRESSURE, "profiles belong to Zou-He / Regularized BCs");
+    XLB_REQUIRE(bc_is_zouhe_family(bc->kind), "profiles belong to Zou-He / Regularized BCs");
     std::vector<std::pair<uint32_t, int64_t>> order((size_t)n_prof);
     for (int64_t i = 0; i < n_prof; ++i) order[(size_t)i] = {storage_cells[i], i};
     std::sort(order.begin(), order.end());
-    std::vector<uint32_t> keys((size_t)n_prof);
+    keys.resize((size_t)n_prof);
     std::vector<double> v((size_t)n_prof * 3);
     for (int64_t i = 0; i < n_prof; ++i) {
       keys[(size_t)i] = order[(size_t)i].first;
       for (int a = 0; a < 3; ++a) v[(size_t)i * 3 + a] = values[order[(size_t)i].second * 3 + a];
     }
-    XLB_HIP(hipMalloc(&dk, keys.size() * sizeof(uint32_t)));
-    XLB_HIP(hipMalloc(&dv, v.size() * sizeof(double)));
+    image = compute_image(cdt, v);
+    XLB_HIP(scratch.alloc(&dk, keys.size() * sizeof(uint32_t)));
+    XLB_HIP(scratch.alloc(&dv, image.size()));
     XLB_HIP(hipMemcpyAsync(dk, keys.data(), keys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    XLB_HIP(hipMemcpyAsync(dv, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    XLB_HIP(hipStreamSynchronize(c->stream));  // the host vectors die with this scope
+    XLB_HIP(hipMemcpyAsync(dv, image.data(), image.size(), hipMemcpyHostToDevice, c->stream));
   }
   const int np = (int)n_prof;
-  int rc = by_lattice(lattice, [&](auto L) {
+  return by_lattice(lattice, [&](auto L) {
     return by_compute(cdt, [&](auto T) {
-      hipLaunchKernelGGL((k_apply_bc<decltype(L), decltype(T)>), blocks_for(n), 256, 0, c->stream, bc->id, bc->kind, vals, view(f_pre), view(f_post),
-                         view(bcm), view(miss), dims(f_post), dk, dv, np);
+      using TT = decltype(T);
+      BcValues<TT> vals = bc_values<TT>(bc->values);
+      if (np > 0) vals.v[PROF_FLAG] = TT(1);  // prescribed values come from the table (cell.hpp: wall_velocity)
+      hipLaunchKernelGGL((k_apply_bc<decltype(L), TT>), blocks_for(n), BC_BLOCK, 0, c->stream, bc->id, bc->kind, vals, view(f_pre), view(f_post),
+                         view(bcm), view(miss), dims(f_post), dk, reinterpret_cast<const TT*>(dv), np);
       XLB_HIP(hipGetLastError());
       return 0;
     });
   });
-  if (dk) {
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(dk);
-    (void)hipFree(dv);
-  }
-  return rc;
 }
 
 int xlbhip_field_gather(const xlbhip_field* f, int64_t n, const uint32_t* cells, void* out, size_t bytes) {

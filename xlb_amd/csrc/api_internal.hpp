@@ -107,6 +107,14 @@ struct DeviceScratch {
   }
 };
 
+// the 27 values of a BC descriptor in the compute dtype
+template <class T>
+static BcValues<T> bc_values(const double* v) {
+  BcValues<T> out;
+  for (int l = 0; l < 27; ++l) out.v[l] = static_cast<T>(v[l]);
+  return out;
+}
+
 // `v` as host bytes in the compute dtype
 static std::vector<char> compute_image(int cdt, const std::vector<double>& v) {
   std::vector<char> image;

@@ -544,6 +544,19 @@ __device__ __forceinline__ void zouhe_cell(T (&f)[L::Q], unsigned m, const T* va
   });
 }
 
+// moving-wall term of a halfway wall with a per-cell velocity: 6 w_l (c_l . u_wall), the components summed in axis order
+// (helper_functions_bc.py:230-250)
+template <class L, class T, int l>
+__device__ __forceinline__ T halfway_profile_term(const T* uw) {
+  T cu = T(0.0);
+  static_for<3>([&](auto ac) {
+    constexpr int ax = decltype(ac)::value;
+    if constexpr (L::c(ax, l) == 1) cu = cu + uw[ax];
+    if constexpr (L::c(ax, l) == -1) cu = cu - uw[ax];
+  });
+  return cu * (T(6.0) * T(L::w(l)));
+}
+
 // ---- HybridBC (bc_hybrid.py:254-358; helper_functions_bc.py:160-340), kernel backends only in the reference ------------
 // f: post-streaming populations of the boundary cell (updated in place); pre: the cell's own pre-streaming populations;
 // m: missing bit-set; wgt: the q wall-distance weights of the cell as the mesh masker stored them (the weight of missing
@@ -580,7 +593,7 @@ __device__ __forceinline__ void hybrid_cell(T (&f)[L::Q], const T (&pre)[L::Q], 
         v = pre[o];
       }
       if ((m >> o) & 1u) v = pre[o];  // sandwiched between two solid cells
-      if (moving) v = v + c_dot(lc, val) * (T(6.0) * T(L::w(l)));
+      if (moving) v = v + halfway_profile_term<L, T, l>(val);
       out[l] = ((m >> l) & 1u) ? v : f[l];
     });
   } else {
@@ -836,6 +849,118 @@ __device__ __forceinline__ int prof_find(const uint32_t* keys, int n, uint32_t k
       hi = mid;
   }
   return lo;
+}
+
+// ---- kind predicates (host and device) ----
+constexpr bool bc_is_known(int k) { return k >= XLBHIP_BC_EQUILIBRIUM && k <= XLBHIP_BC_HALFWAY_BB_PROFILE; }
+constexpr bool bc_is_zouhe_family(int k) { return k >= XLBHIP_BC_ZOUHE_VELOCITY && k <= XLBHIP_BC_REGULARIZED_PRESSURE; }
+constexpr bool bc_is_hybrid(int k) { return k >= XLBHIP_BC_HYBRID_BB_REGULARIZED && k <= XLBHIP_BC_HYBRID_NEQ_REGULARIZED; }
+constexpr bool bc_is_extended(int k) { return k >= XLBHIP_BC_ZOUHE_VELOCITY; }  // the extended step-kernel variant's: all but the four basic kinds
+constexpr bool bc_reads_missing(int k) { return k == XLBHIP_BC_HALFWAY_BB || bc_is_extended(k); }
+constexpr bool bc_is_edge_kind(int k) { return bc_is_extended(k) || k == XLBHIP_BC_DO_NOTHING; }  // not evaluated by the two-step kernel itself
+constexpr bool bc_has_wall_table(int k) { return bc_is_hybrid(k) || k == XLBHIP_BC_HALFWAY_BB_PROFILE; }  // cells may sit in the sparse tables
+
+// The cell's entry of the profile table (sorted storage cells, 3 values each) into uw[0..2]; nothing without a table
+template <class T>
+__device__ __forceinline__ void profile_entry(const uint32_t* prof_keys, const T* prof_vals, int n_prof, unsigned key, T (&uw)[5]) {
+  if (n_prof > 0) {
+    const T* pv = prof_vals + 3 * (size_t)prof_find(prof_keys, n_prof, key);
+    uw[0] = pv[0];
+    uw[1] = pv[1];
+    uw[2] = pv[2];
+  }
+}
+// Prescribed values of a Zou-He / Regularized or HybridBC cell (velocity uw[0..2] or density uw[0]; uw[3], uw[4]: HybridBC's flags): the
+// BC's constants val[0..4], the first three from the profile table when the BC is flagged for it.  bc_zouhe.py:225-232, bc_hybrid.py:265
+template <class T>
+__device__ __forceinline__ void wall_velocity(const T* val, const uint32_t* prof_keys, const T* prof_vals, int n_prof, unsigned key, T (&uw)[5]) {
+  uw[0] = val[0];
+  uw[1] = val[1];
+  uw[2] = val[2];
+  uw[3] = val[3];
+  uw[4] = val[4];
+  if (val[PROF_FLAG] != T(0)) profile_entry<T>(prof_keys, prof_vals, n_prof, key, uw);
+}
+// the q wall-distance weights of a HybridBC cell from the sparse table, or nullptr (val[4] == 0: no distances; or no entry for the cell)
+template <class L, class T>
+__device__ __forceinline__ const float* wall_weights(const T* val, const uint32_t* dist_keys, const float* dist_vals, int n_dist, unsigned key) {
+  if (val[4] != T(0) && n_dist > 0) {
+    const int slot = prof_find(dist_keys, n_dist, key);
+    if (dist_keys[slot] == key) return dist_vals + (size_t)slot * L::Q;
+  }
+  return nullptr;
+}
+
+// Zou-He / Regularized cell of kind `kind` (bc_zouhe.py, bc_regularized.py)
+template <class L, class T>
+__device__ __forceinline__ void zouhe_apply(unsigned kind, T (&f)[L::Q], unsigned m, const T* val) {
+  zouhe_cell<L, T>(f, m, val, kind == XLBHIP_BC_ZOUHE_VELOCITY || kind == XLBHIP_BC_REGULARIZED_VELOCITY, kind >= XLBHIP_BC_REGULARIZED_VELOCITY);
+}
+
+// The streaming-step boundary condition of kind `kind` on one cell (boundary_condition.py:146-180 with the bodies of bc_equilibrium.py,
+// bc_halfway_bounce_back.py, bc_do_nothing.py, bc_extrapolation_outflow.py:137-145, bc_zouhe.py, bc_regularized.py, bc_hybrid.py).
+// f: pulled populations, updated in place; pre: the cell's own pre-streaming ones; m: missing bits; uw: wall_velocity(); wgt: wall_weights()
+template <class L, class T>
+__device__ __forceinline__ void apply_streaming_bc(unsigned kind, T (&f)[L::Q], const T (&pre)[L::Q], unsigned m, const T* val, const T (&uw)[5],
+                                                   const float* wgt) {
+  constexpr int Q = L::Q;
+  if (kind == XLBHIP_BC_EQUILIBRIUM) {
+    static_for<Q>([&](auto lc) { f[decltype(lc)::value] = val[decltype(lc)::value]; });
+  } else if (kind == XLBHIP_BC_HALFWAY_BB) {
+    // missing & boundary -> f_pre[opp] + moving-wall term (0.0 for a no-slip wall; the reference adds it in that case too)
+    static_for<Q>([&](auto lc) {
+      constexpr int l = decltype(lc)::value;
+      if ((m >> l) & 1u) f[l] = pre[opp<L>(l)] + val[l];
+    });
+  } else if (kind == XLBHIP_BC_HALFWAY_BB_PROFILE) {
+    static_for<Q>([&](auto lc) {
+      constexpr int l = decltype(lc)::value;
+      if ((m >> l) & 1u) f[l] = pre[opp<L>(l)] + halfway_profile_term<L, T, l>(uw);
+    });
+  } else if (kind == XLBHIP_BC_DO_NOTHING) {
+    static_for<Q>([&](auto lc) { f[decltype(lc)::value] = pre[decltype(lc)::value]; });
+  } else if (kind == XLBHIP_BC_EXTRAPOLATION_OUTFLOW) {
+    // last step's auxiliary data; the new ones are assembled after the step (k_outflow_aux)
+    static_for<Q>([&](auto lc) {
+      constexpr int l = decltype(lc)::value;
+      if ((m >> l) & 1u) f[l] = pre[opp<L>(l)];
+    });
+  } else if (bc_is_zouhe_family(kind)) {
+    zouhe_apply<L, T>(kind, f, m, uw);
+  } else if (bc_is_hybrid(kind)) {
+    if constexpr (L::D == 3) hybrid_cell<L, T>(f, pre, m, wgt, uw, (int)kind - XLBHIP_BC_HYBRID_BB_REGULARIZED);
+  }
+}
+
+// ---- momentum exchange of one link: force += c[:, o] * phi, and the grid sum (force/momentum_transfer.py:167-205) ----
+template <class L, int o, class T>
+__device__ __forceinline__ void add_link_force(T phi, T& fx, T& fy, T& fz) {
+  if constexpr (L::c(0, o) == 1) fx = fx + phi;
+  if constexpr (L::c(0, o) == -1) fx = fx - phi;
+  if constexpr (L::c(1, o) == 1) fy = fy + phi;
+  if constexpr (L::c(1, o) == -1) fy = fy - phi;
+  if constexpr (L::c(2, o) == 1) fz = fz + phi;
+  if constexpr (L::c(2, o) == -1) fz = fz - phi;
+}
+// sum over a block of BC_BLOCK threads (every thread calls), then one fp64 atomic per component (the reference's order is unpinned too)
+constexpr int BC_BLOCK = 256;  // block size of the whole-field BC kernels: their launch bound and their launches use it
+template <class T>
+__device__ __forceinline__ void block_sum3_add(T fx, T fy, T fz, double* force /*[3]*/) {
+  __shared__ double red[3][BC_BLOCK];
+  const int t = threadIdx.x;
+  red[0][t] = (double)fx;
+  red[1][t] = (double)fy;
+  red[2][t] = (double)fz;
+  __syncthreads();
+  for (int s = BC_BLOCK / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      red[0][t] += red[0][t + s];
+      red[1][t] += red[1][t + s];
+      red[2][t] += red[2][t + s];
+    }
+    __syncthreads();
+  }
+  if (t < 3 && red[t][0] != 0.0) atomicAdd(force + t, red[t][0]);
 }
 
 constexpr int COLL_FORCED = 4;  // (COLL_FAST = 8 is defined with kbc_fast above)

@@ -155,76 +155,69 @@ __global__ void k_collide(FieldView f, FieldView feq, FieldView fout, Dims d, T 
   });
 }
 
+template <class T>
 struct BcValues {
-  double v[27];
+  T v[27];  // the constants of one BC in the compute dtype (converted on the host), passed by value
 };
 
-// bc(f_pre, f_post, bc_mask, missing_mask) -> f_post: boundary_condition.py:146-180 with the
-// JAX bodies of bc_equilibrium.py:75-80, bc_halfway_bounce_back.py:124-132,
-// bc_fullway_bounce_back.py:52-56, bc_do_nothing.py:50-54
+// The stepper's boundary tables: kind and constants by id, per-cell prescribed values and HybridBC wall-distance weights by sorted storage cell
+template <class T>
+struct BcView {
+  const uint8_t* kind;  // [256]
+  const T* values;      // [256][27]
+  const uint32_t* prof_keys;
+  const T* prof_vals;
+  int n_prof;
+  const uint32_t* dist_keys;
+  const float* dist_vals;
+  int n_dist;
+};
+
+// apply_streaming_bc for cell `key` (storage cell index) of BC `id`, its wall velocity and weights looked up in the tables
 template <class L, class T>
-__global__ void k_apply_bc(int id, int kind, BcValues vals, FieldView f_pre, FieldView f_post, FieldView bc, FieldView miss,
-                           Dims d, const uint32_t* prof_keys, const double* prof_vals, int n_prof) {
+__device__ __forceinline__ void apply_streaming_bc(const BcView<T>& tb, unsigned id, unsigned key, T (&f)[L::Q], const T (&pre)[L::Q], unsigned m) {
+  const unsigned kind = tb.kind[id];
+  const T* val = tb.values + id * 27u;
+  T uw[5] = {T(0), T(0), T(0), T(0), T(0)};
+  if (kind == XLBHIP_BC_HALFWAY_BB_PROFILE)
+    profile_entry<T>(tb.prof_keys, tb.prof_vals, tb.n_prof, key, uw);
+  else if (bc_is_extended(kind))
+    wall_velocity<T>(val, tb.prof_keys, tb.prof_vals, tb.n_prof, key, uw);
+  const float* wgt = bc_is_hybrid(kind) ? wall_weights<L, T>(val, tb.dist_keys, tb.dist_vals, tb.n_dist, key) : nullptr;
+  apply_streaming_bc<L, T>(kind, f, pre, m, val, uw, wgt);
+}
+
+// bc(f_pre, f_post, bc_mask, missing_mask) -> f_post: boundary_condition.py:146-180.  Stand-alone operator: the prescribed
+// values of a Zou-He / Regularized BC come from the call's own table when the host flagged them (PROF_FLAG), HybridBC has no distances.
+template <class L, class T>
+__global__ void __launch_bounds__(BC_BLOCK) k_apply_bc(int id, int kind, BcValues<T> vals, FieldView f_pre, FieldView f_post, FieldView bc, FieldView miss,
+                           Dims d, const uint32_t* prof_keys, const T* prof_vals, int n_prof) {
   int x, y, z;
   if (!cell_of_thread(d, x, y, z)) return;
   const uint8_t b = static_cast<const uint8_t*>(bc.data)[cell_index(bc, d, x, y, z)];
   if (b != id) return;
   const size_t ip = cell_index(f_pre, d, x, y, z), io = cell_index(f_post, d, x, y, z);
   unsigned m = 0;
-  if (kind == XLBHIP_BC_HALFWAY_BB || kind >= XLBHIP_BC_ZOUHE_VELOCITY) m = static_cast<const uint32_t*>(miss.data)[cell_index(miss, d, x, y, z)];
-  if (kind >= XLBHIP_BC_ZOUHE_VELOCITY && kind <= XLBHIP_BC_REGULARIZED_PRESSURE) {
-    T ff[L::Q], val[3];
-    static_for<L::Q>([&](auto lc) {
-      constexpr int l = decltype(lc)::value;
-      ff[l] = load_rt<T>(f_post, (size_t)l * f_post.plane_stride + io);
-    });
-    const double* pv = vals.v;
-    if (n_prof > 0) pv = prof_vals + 3 * (size_t)prof_find(prof_keys, n_prof, (uint32_t)cell_index(bc, d, x, y, z));
-    val[0] = static_cast<T>(pv[0]);
-    val[1] = static_cast<T>(pv[1]);
-    val[2] = static_cast<T>(pv[2]);
-    zouhe_cell<L, T>(ff, m, val, kind == XLBHIP_BC_ZOUHE_VELOCITY || kind == XLBHIP_BC_REGULARIZED_VELOCITY,
-                     kind >= XLBHIP_BC_REGULARIZED_VELOCITY);
-    static_for<L::Q>([&](auto lc) {
-      constexpr int l = decltype(lc)::value;
-      store_rt<T>(f_post, (size_t)l * f_post.plane_stride + io, ff[l]);
-    });
-    return;
-  }
-  if (kind >= XLBHIP_BC_HYBRID_BB_REGULARIZED && kind <= XLBHIP_BC_HYBRID_NEQ_REGULARIZED) {
-    if constexpr (L::D == 3) {
-      T ff[L::Q], pre[L::Q], val[5];
-      static_for<L::Q>([&](auto lc) {
-        constexpr int l = decltype(lc)::value;
-        ff[l] = load_rt<T>(f_post, (size_t)l * f_post.plane_stride + io);
-        pre[l] = load_rt<T>(f_pre, (size_t)l * f_pre.plane_stride + ip);
-      });
-      for (int a = 0; a < 5; ++a) val[a] = static_cast<T>(vals.v[a]);
-      hybrid_cell<L, T>(ff, pre, m, nullptr, val, kind - XLBHIP_BC_HYBRID_BB_REGULARIZED);
-      static_for<L::Q>([&](auto lc) {
-        constexpr int l = decltype(lc)::value;
-        store_rt<T>(f_post, (size_t)l * f_post.plane_stride + io, ff[l]);
-      });
-    }
-    return;
+  if (bc_reads_missing(kind)) m = static_cast<const uint32_t*>(miss.data)[cell_index(miss, d, x, y, z)];
+  T ff[L::Q], pre[L::Q];
+  static_for<L::Q>([&](auto lc) {
+    constexpr int l = decltype(lc)::value;
+    ff[l] = load_rt<T>(f_post, (size_t)l * f_post.plane_stride + io);
+    pre[l] = load_rt<T>(f_pre, (size_t)l * f_pre.plane_stride + ip);
+  });
+  // halfway walls and the outflow's streaming part replace the missing directions only: the others are not written
+  unsigned written = (kind == XLBHIP_BC_HALFWAY_BB || kind == XLBHIP_BC_EXTRAPOLATION_OUTFLOW) ? m : ~0u;
+  if (kind == XLBHIP_BC_FULLWAY_BB) {
+    // bc_fullway_bounce_back.py:52-56 (post-collision)
+    static_for<L::Q>([&](auto lc) { ff[decltype(lc)::value] = pre[opp<L>(decltype(lc)::value)]; });
+  } else {
+    T uw[5] = {T(0), T(0), T(0), T(0), T(0)};
+    if (bc_is_extended(kind)) wall_velocity<T>(vals.v, prof_keys, prof_vals, n_prof, (unsigned)cell_index(bc, d, x, y, z), uw);
+    apply_streaming_bc<L, T>((unsigned)kind, ff, pre, m, vals.v, uw, nullptr);
   }
   static_for<L::Q>([&](auto lc) {
     constexpr int l = decltype(lc)::value;
-    constexpr int o = opp<L>(l);
-    if (kind == XLBHIP_BC_EQUILIBRIUM) {
-      store_rt<T>(f_post, (size_t)l * f_post.plane_stride + io, static_cast<T>(vals.v[l]));
-    } else if (kind == XLBHIP_BC_HALFWAY_BB) {
-      if ((m >> l) & 1u)
-        store_rt<T>(f_post, (size_t)l * f_post.plane_stride + io,
-                    load_rt<T>(f_pre, (size_t)o * f_pre.plane_stride + ip) + static_cast<T>(vals.v[l]));
-    } else if (kind == XLBHIP_BC_EXTRAPOLATION_OUTFLOW) {
-      // bc_extrapolation_outflow.py:137-145 (streaming step; the extrapolation itself is k_outflow_aux)
-      if ((m >> l) & 1u) store_rt<T>(f_post, (size_t)l * f_post.plane_stride + io, load_rt<T>(f_pre, (size_t)o * f_pre.plane_stride + ip));
-    } else if (kind == XLBHIP_BC_FULLWAY_BB) {
-      store_rt<T>(f_post, (size_t)l * f_post.plane_stride + io, load_rt<T>(f_pre, (size_t)o * f_pre.plane_stride + ip));
-    } else if (kind == XLBHIP_BC_DO_NOTHING) {
-      store_rt<T>(f_post, (size_t)l * f_post.plane_stride + io, load_rt<T>(f_pre, (size_t)l * f_pre.plane_stride + ip));
-    }
+    if ((written >> l) & 1u) store_rt<T>(f_post, (size_t)l * f_post.plane_stride + io, ff[l]);
   });
 }
 
@@ -294,7 +287,22 @@ static __global__ void k_ext_interior_scan(FieldView bc, const uint8_t* kind_tab
   if (!cell_of_thread(d, x, y, z)) return;
   if (x < 1 || x > d.nx - 2) return;
   const unsigned id = static_cast<const uint8_t*>(bc.data)[cell_index(bc, d, x, y, z)];
-  if (id != 0u && (kind_tab[id] >= XLBHIP_BC_ZOUHE_VELOCITY || kind_tab[id] == XLBHIP_BC_DO_NOTHING)) *flag = 1;
+  if (id != 0u && bc_is_edge_kind(kind_tab[id])) *flag = 1;
+}
+
+// periodic pull of the q populations arriving at a cell (stream.py:57-62), and the cell's own ones
+template <class L, class T>
+__device__ __forceinline__ void pull_cell(const FieldView& f0, const Dims& d, int x, int y, int z, T (&f)[L::Q]) {
+  static_for<L::Q>([&](auto lc) {
+    constexpr int l = decltype(lc)::value;
+    const int xs = f0.halo ? x - L::c(0, l) : wrap(x - L::c(0, l), d.nx);
+    f[l] = load_rt<T>(f0, (size_t)l * f0.plane_stride + cell_index(f0, d, xs, wrap(y - L::c(1, l), d.ny), wrap(z - L::c(2, l), d.nz)));
+  });
+}
+template <class L, class T>
+__device__ __forceinline__ void own_cell(const FieldView& f0, const Dims& d, int x, int y, int z, T (&f)[L::Q]) {
+  const size_t c = cell_index(f0, d, x, y, z);
+  static_for<L::Q>([&](auto lc) { f[decltype(lc)::value] = load_rt<T>(f0, (size_t) decltype(lc)::value * f0.plane_stride + c); });
 }
 
 // ---- MomentumTransfer (force/momentum_transfer.py:167-205, JAX): force on the solid behind a no-slip BC ----------
@@ -303,9 +311,8 @@ static __global__ void k_ext_interior_scan(FieldView bc, const uint8_t* kind_tab
 // bounce-back of the own cell (halfway: f0[opp l] + wall term; fullway: f0[opp l]);  F = sum c_{opp l} phi_l.
 // One double-precision atomic per block and component (the grid sum's order is unpinned in the reference as well).
 template <class L, class T>
-__global__ void k_momentum_transfer(FieldView f0, FieldView bc, FieldView miss, Dims d, int id, BcValues vals, int add_wall_term,
+__global__ void __launch_bounds__(BC_BLOCK) k_momentum_transfer(FieldView f0, FieldView bc, FieldView miss, Dims d, int id, BcValues<T> vals, int add_wall_term,
                                     double* force /*[3]*/) {
-  __shared__ double red[3][256];
   int x, y, z;
   T fx = T(0), fy = T(0), fz = T(0);
   if (cell_of_thread(d, x, y, z)) {
@@ -320,44 +327,21 @@ __global__ void k_momentum_transfer(FieldView f0, FieldView bc, FieldView miss, 
           if ((m >> l) & 1u) {
             const T fo = load_rt<T>(f0, (size_t)o * f0.plane_stride + own);
             T ps = fo;
-            if (add_wall_term) ps = fo + static_cast<T>(vals.v[l]);
-            const T phi = fo + ps;
-            // force += c[:, opp l] * phi
-            if constexpr (L::c(0, o) == 1) fx = fx + phi;
-            if constexpr (L::c(0, o) == -1) fx = fx - phi;
-            if constexpr (L::c(1, o) == 1) fy = fy + phi;
-            if constexpr (L::c(1, o) == -1) fy = fy - phi;
-            if constexpr (L::c(2, o) == 1) fz = fz + phi;
-            if constexpr (L::c(2, o) == -1) fz = fz - phi;
+            if (add_wall_term) ps = fo + vals.v[l];
+            add_link_force<L, o>(fo + ps, fx, fy, fz);
           }
         });
       }
     }
   }
-  const int t = threadIdx.x;
-  red[0][t] = (double)fx;
-  red[1][t] = (double)fy;
-  red[2][t] = (double)fz;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) {
-      red[0][t] += red[0][t + s];
-      red[1][t] += red[1][t + s];
-      red[2][t] += red[2][t + s];
-    }
-    __syncthreads();
-  }
-  if (t < 3 && red[t][0] != 0.0) atomicAdd(force + t, red[t][0]);
+  block_sum3_add(fx, fy, fz, force);
 }
 
 // MomentumTransfer for the BCs whose post-stream populations need the stepper's tables (HybridBC: wall distances, wall-velocity
 // profile; halfway bounce-back with a profile) — the kernel backends' path of the reference, force/momentum_transfer.py:225-262 with
 // FetchPopulations (:75-92): f_post_stream = the BC applied to (own populations of f_0, populations pulled from f_0).
 template <class L, class T>
-__global__ void k_momentum_transfer_tab(FieldView f0, FieldView bc, FieldView miss, Dims d, int id, const uint8_t* kind_tab, const T* val_tab,
-                                        const uint32_t* prof_keys, const T* prof_vals, int n_prof, const uint32_t* dist_keys,
-                                        const float* dist_vals, int n_dist, double* force /*[3]*/) {
-  __shared__ double red[3][256];
+__global__ void __launch_bounds__(BC_BLOCK) k_momentum_transfer_tab(FieldView f0, FieldView bc, FieldView miss, Dims d, int id, BcView<T> tb, double* force /*[3]*/) {
   constexpr int Q = L::Q;
   int x, y, z;
   T fx = T(0), fy = T(0), fz = T(0);
@@ -366,75 +350,19 @@ __global__ void k_momentum_transfer_tab(FieldView f0, FieldView bc, FieldView mi
     if (b == id) {
       const unsigned m = static_cast<const uint32_t*>(miss.data)[cell_index(miss, d, x, y, z)];
       if ((m & 1u) == 0u) {
-        const size_t own = cell_index(f0, d, x, y, z);
-        const unsigned key = (unsigned)cell_index(bc, d, x, y, z);
-        const unsigned kind = kind_tab[id];
-        const T* val = val_tab + (unsigned)id * 27u;
         T pre[Q], ps[Q];
-        static_for<Q>([&](auto lc) {
-          constexpr int l = decltype(lc)::value;
-          pre[l] = load_rt<T>(f0, (size_t)l * f0.plane_stride + own);
-          const int xs = f0.halo ? x - L::c(0, l) : wrap(x - L::c(0, l), d.nx);
-          ps[l] = load_rt<T>(f0, (size_t)l * f0.plane_stride + cell_index(f0, d, xs, wrap(y - L::c(1, l), d.ny), wrap(z - L::c(2, l), d.nz)));
-        });
-        T uw[5] = {val[0], val[1], val[2], val[3], val[4]};
-        if ((kind == XLBHIP_BC_HALFWAY_BB_PROFILE || val[PROF_FLAG] != T(0)) && n_prof > 0) {
-          const T* pv = prof_vals + 3 * (size_t)prof_find(prof_keys, n_prof, key);
-          uw[0] = pv[0];
-          uw[1] = pv[1];
-          uw[2] = pv[2];
-        }
-        if (kind == XLBHIP_BC_HALFWAY_BB_PROFILE) {
-          static_for<Q>([&](auto lc) {
-            constexpr int l = decltype(lc)::value;
-            T cu = T(0.0);
-            static_for<3>([&](auto ac) {
-              constexpr int ax = decltype(ac)::value;
-              if constexpr (L::c(ax, l) == 1) cu = cu + uw[ax];
-              if constexpr (L::c(ax, l) == -1) cu = cu - uw[ax];
-            });
-            if ((m >> l) & 1u) ps[l] = pre[opp<L>(l)] + cu * (T(6.0) * T(L::w(l)));
-          });
-        } else {
-          if constexpr (L::D == 3) {
-            const float* wgt = nullptr;
-            if (val[4] != T(0) && n_dist > 0) {
-              const int slot = prof_find(dist_keys, n_dist, key);
-              if (dist_keys[slot] == key) wgt = dist_vals + (size_t)slot * Q;
-            }
-            hybrid_cell<L, T>(ps, pre, m, wgt, uw, (int)kind - XLBHIP_BC_HYBRID_BB_REGULARIZED);
-          }
-        }
+        own_cell<L, T>(f0, d, x, y, z, pre);
+        pull_cell<L, T>(f0, d, x, y, z, ps);
+        apply_streaming_bc<L, T>(tb, (unsigned)id, (unsigned)cell_index(bc, d, x, y, z), ps, pre, m);
         static_for<Q>([&](auto lc) {
           constexpr int l = decltype(lc)::value;
           constexpr int o = opp<L>(l);
-          if ((m >> l) & 1u) {
-            const T phi = pre[o] + ps[l];
-            if constexpr (L::c(0, o) == 1) fx = fx + phi;
-            if constexpr (L::c(0, o) == -1) fx = fx - phi;
-            if constexpr (L::c(1, o) == 1) fy = fy + phi;
-            if constexpr (L::c(1, o) == -1) fy = fy - phi;
-            if constexpr (L::c(2, o) == 1) fz = fz + phi;
-            if constexpr (L::c(2, o) == -1) fz = fz - phi;
-          }
+          if ((m >> l) & 1u) add_link_force<L, o>(pre[o] + ps[l], fx, fy, fz);
         });
       }
     }
   }
-  const int t = threadIdx.x;
-  red[0][t] = (double)fx;
-  red[1][t] = (double)fy;
-  red[2][t] = (double)fz;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) {
-      red[0][t] += red[0][t + s];
-      red[1][t] += red[1][t + s];
-      red[2][t] += red[2][t + s];
-    }
-    __syncthreads();
-  }
-  if (t < 3 && red[t][0] != 0.0) atomicAdd(force + t, red[t][0]);
+  block_sum3_add(fx, fy, fz, force);
 }
 
 // ---- GridToPoint (postprocess/grid_to_point.py:28-94): trilinear interpolation of component 0 at arbitrary points ----
@@ -460,61 +388,19 @@ __global__ void k_grid_to_point(FieldView g, Dims d, const float* pts /*[n][3]*/
 }
 
 // ---- ExtrapolationOutflowBC: auxiliary data after the collision --------------------------
-// Post-stream populations of ONE cell: periodic pull + the STREAMING-step boundary condition of that cell
-// (nse_stepper.py:246-257).  Generic slow path: only the outflow cells and the cells behind them run it.
+// assemble_auxiliary_data of ExtrapolationOutflowBC (bc_extrapolation_outflow.py:104-134), run after the step kernel: at an outflow cell b
+// with outward normal n, for every l whose opposite is missing, f_1[l](b) = cs * f_post_stream[opp l](b - n) + (1 - cs) * f_post_stream[opp l](b).
+// f_post_stream of a cell: periodic pull + that cell's STREAMING-step BC (nse_stepper.py:246-257): the outflow rule for b, any kind behind it.
 template <class L, class T>
-__device__ void post_stream_cell(const FieldView& f0, const FieldView& bc, const FieldView& miss, const Dims& d, const uint8_t* kind_tab,
-                                 const T* val_tab, const uint32_t* prof_keys, const T* prof_vals, int n_prof, int x, int y, int z,
-                                 T (&f)[L::Q]) {
-  static_for<L::Q>([&](auto lc) {
-    constexpr int l = decltype(lc)::value;
-    const int xs = f0.halo ? x - L::c(0, l) : wrap(x - L::c(0, l), d.nx);
-    const int ys = wrap(y - L::c(1, l), d.ny);
-    const int zs = wrap(z - L::c(2, l), d.nz);
-    f[l] = load_rt<T>(f0, (size_t)l * f0.plane_stride + cell_index(f0, d, xs, ys, zs));
-  });
-  const unsigned id = static_cast<const uint8_t*>(bc.data)[cell_index(bc, d, x, y, z)];
-  if (id == 0u) return;
-  const unsigned kind = kind_tab[id];
-  const T* val = val_tab + id * 27u;
-  const size_t own = cell_index(f0, d, x, y, z);
-  unsigned m = 0;
-  if (miss.data) m = static_cast<const uint32_t*>(miss.data)[cell_index(miss, d, x, y, z)];
-  if (kind == XLBHIP_BC_EQUILIBRIUM) {
-    static_for<L::Q>([&](auto lc) { f[decltype(lc)::value] = val[decltype(lc)::value]; });
-  } else if (kind == XLBHIP_BC_HALFWAY_BB) {
-    static_for<L::Q>([&](auto lc) {
-      constexpr int l = decltype(lc)::value;
-      if ((m >> l) & 1u) f[l] = load_rt<T>(f0, (size_t)opp<L>(l) * f0.plane_stride + own) + val[l];
-    });
-  } else if (kind == XLBHIP_BC_EXTRAPOLATION_OUTFLOW) {
-    static_for<L::Q>([&](auto lc) {
-      constexpr int l = decltype(lc)::value;
-      if ((m >> l) & 1u) f[l] = load_rt<T>(f0, (size_t)opp<L>(l) * f0.plane_stride + own);
-    });
-  } else if (kind == XLBHIP_BC_DO_NOTHING) {
-    static_for<L::Q>([&](auto lc) {
-      constexpr int l = decltype(lc)::value;
-      f[l] = load_rt<T>(f0, (size_t)l * f0.plane_stride + own);
-    });
-  } else if (kind >= XLBHIP_BC_ZOUHE_VELOCITY && kind <= XLBHIP_BC_REGULARIZED_PRESSURE) {
-    if (val[PROF_FLAG] != T(0) && n_prof > 0) val = prof_vals + 3 * (size_t)prof_find(prof_keys, n_prof, (uint32_t)cell_index(bc, d, x, y, z));
-    zouhe_cell<L, T>(f, m, val, kind == XLBHIP_BC_ZOUHE_VELOCITY || kind == XLBHIP_BC_REGULARIZED_VELOCITY,
-                     kind >= XLBHIP_BC_REGULARIZED_VELOCITY);
-  }
-}
-
-// assemble_auxiliary_data of ExtrapolationOutflowBC (bc_extrapolation_outflow.py:104-134), run after the step kernel:
-// at an outflow cell b with outward normal n, for every direction l whose opposite is missing,
-//   f_1[l](b) = cs * f_post_stream[opp l](b - n) + (1 - cs) * f_post_stream[opp l](b)
-template <class L, class T>
-__global__ void k_outflow_aux(FieldView f0, FieldView f1, FieldView bc, FieldView miss, Dims d, const uint8_t* kind_tab, const T* val_tab,
-                              const uint32_t* prof_keys, const T* prof_vals, int n_prof) {
+__global__ void __launch_bounds__(BC_BLOCK) k_outflow_aux(FieldView f0, FieldView f1, FieldView bc, FieldView miss, Dims d, BcView<T> tb) {
+  // nearly every thread leaves here: its bc_mask byte sits at the thread's linear index (cell_index is linear in it), no division needed
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)d.nx * d.ny * d.nz) return;
+  const unsigned id = static_cast<const uint8_t*>(bc.data)[t + (size_t)bc.halo * d.ny * d.nz];
+  if (id == 0u || tb.kind[id] != XLBHIP_BC_EXTRAPOLATION_OUTFLOW) return;
   int x, y, z;
-  if (!cell_of_thread(d, x, y, z)) return;
-  const unsigned id = static_cast<const uint8_t*>(bc.data)[cell_index(bc, d, x, y, z)];
-  if (id == 0u || kind_tab[id] != XLBHIP_BC_EXTRAPOLATION_OUTFLOW) return;
-  const T* val = val_tab + id * 27u;
+  cell_of_thread(d, x, y, z);
+  const T* val = tb.values + id * 27u;
   const int n0 = (int)val[0], n1 = (int)val[1], n2 = (int)val[2];
   const T cs = val[3], omcs = val[4];
   int xn = x - n0;
@@ -524,10 +410,19 @@ __global__ void k_outflow_aux(FieldView f0, FieldView f1, FieldView bc, FieldVie
     xn = wrap(xn, d.nx);
   }
   const int yn = wrap(y - n1, d.ny), zn = wrap(z - n2, d.nz);
-  T fb[L::Q], fn[L::Q];
-  post_stream_cell<L, T>(f0, bc, miss, d, kind_tab, val_tab, prof_keys, prof_vals, n_prof, x, y, z, fb);
-  post_stream_cell<L, T>(f0, bc, miss, d, kind_tab, val_tab, prof_keys, prof_vals, n_prof, xn, yn, zn, fn);
-  const unsigned m = static_cast<const uint32_t*>(miss.data)[cell_index(miss, d, x, y, z)];
+  const uint32_t* mp = static_cast<const uint32_t*>(miss.data);
+  const unsigned m = mp[cell_index(miss, d, x, y, z)];
+  const T none[5] = {T(0), T(0), T(0), T(0), T(0)};
+  T fb[L::Q], fn[L::Q], pre[L::Q];
+  pull_cell<L, T>(f0, d, x, y, z, fb);
+  own_cell<L, T>(f0, d, x, y, z, pre);
+  apply_streaming_bc<L, T>(XLBHIP_BC_EXTRAPOLATION_OUTFLOW, fb, pre, m, val, none, nullptr);
+  pull_cell<L, T>(f0, d, xn, yn, zn, fn);
+  const unsigned idn = static_cast<const uint8_t*>(bc.data)[cell_index(bc, d, xn, yn, zn)];
+  if (idn != 0u) {
+    own_cell<L, T>(f0, d, xn, yn, zn, pre);
+    apply_streaming_bc<L, T>(tb, idn, (unsigned)cell_index(bc, d, xn, yn, zn), fn, pre, mp[cell_index(miss, d, xn, yn, zn)]);
+  }
   const size_t o1 = cell_index(f1, d, x, y, z);
   static_for<L::Q>([&](auto lc) {
     constexpr int l = decltype(lc)::value;

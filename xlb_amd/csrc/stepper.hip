@@ -222,6 +222,13 @@ static Step2Launch make_launch2(xlbhip_stepper* s, const Step2Case& pc, const xl
   return p;
 }
 
+// the stepper's boundary tables for the whole-field kernels; prof_vals: the profile table of the timestep in question
+template <class T>
+static BcView<T> bc_view(const xlbhip_stepper* s, const void* prof_vals) {
+  return {s->bc.tab_kind.get<uint8_t>(), s->bc.tab_values.get<const T>(), s->prof.keys.get<uint32_t>(), static_cast<const T*>(prof_vals), s->prof.n,
+          s->dist_keys.get<uint32_t>(),  s->dist_vals.get<float>(),       s->n_dist};
+}
+
 // assemble_auxiliary_data of the ExtrapolationOutflowBC cells after a step src -> dst (nse_stepper.py:270-272)
 static int outflow_aux(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
                        int64_t t) {
@@ -233,9 +240,8 @@ static int outflow_aux(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field*
   return by_lattice(s->lattice, [&](auto L) {
     return by_compute(s->cdt, [&](auto T) {
       using TT = decltype(T);
-      hipLaunchKernelGGL((k_outflow_aux<decltype(L), TT>), blocks_for(n), 256, 0, c->stream, view(src), view(dst), view(bcm), view(miss), dims(dst),
-                         s->bc.tab_kind.get<uint8_t>(), s->bc.tab_values.get<const TT>(), s->prof.keys.get<uint32_t>(), static_cast<const TT*>(pv),
-                         s->prof.n);
+      hipLaunchKernelGGL((k_outflow_aux<decltype(L), TT>), blocks_for(n), BC_BLOCK, 0, c->stream, view(src), view(dst), view(bcm), view(miss), dims(dst),
+                         bc_view<TT>(s, pv));
       XLB_HIP(hipGetLastError());
       return 0;
     });
@@ -547,16 +553,16 @@ int xlbhip_stepper_create(xlbhip_ctx* c, int lattice, int collision, int cdt, in
   for (int i = 0; i < n_bc; ++i) {
     const xlbhip_bc_desc& b = bcs[i];
     XLB_REQUIRE(b.id >= 1 && b.id <= 255, "bc id %d out of range 1..255", b.id);
-    XLB_REQUIRE(b.kind >= XLBHIP_BC_EQUILIBRIUM && b.kind <= XLBHIP_BC_HALFWAY_BB_PROFILE, "unknown bc kind %d", b.kind);
-    XLB_REQUIRE(b.kind < XLBHIP_BC_HYBRID_BB_REGULARIZED || b.kind > XLBHIP_BC_HYBRID_NEQ_REGULARIZED || lattice_d(lattice) == 3,
+    XLB_REQUIRE(bc_is_known(b.kind), "unknown bc kind %d", b.kind);
+    XLB_REQUIRE(!bc_is_hybrid(b.kind) || lattice_d(lattice) == 3,
                 "This BC is not implemented in 2D!");  // bc_hybrid.py:119-120
     if (b.kind == XLBHIP_BC_EXTRAPOLATION_OUTFLOW) has_outflow = true;
-    if (b.kind >= XLBHIP_BC_ZOUHE_VELOCITY || b.kind == XLBHIP_BC_DO_NOTHING) has_edge_kinds = true;
+    if (bc_is_edge_kind(b.kind)) has_edge_kinds = true;
     XLB_REQUIRE(kind[b.id] == 0, "bc id %d used twice", b.id);
-    if (b.kind >= XLBHIP_BC_ZOUHE_VELOCITY) extended = needs_missing = true;
+    if (bc_is_extended(b.kind)) extended = true;
     kind[b.id] = (uint8_t)b.kind;
     for (int l = 0; l < q; ++l) vals[b.id * 27 + l] = b.values[l];
-    if (b.kind == XLBHIP_BC_HALFWAY_BB) needs_missing = true;
+    if (bc_reads_missing(b.kind)) needs_missing = true;
   }
   unsigned long long ids_packed = 0;
   unsigned kinds_packed = 0;
@@ -616,7 +622,7 @@ int xlbhip_stepper_set_bc_profile_cells(xlbhip_stepper* s, int bc_id, int64_t n,
   XLB_HIP(hipSetDevice(s->ctx->device));
   uint8_t kind = 0;
   XLB_HIP(hipMemcpy(&kind, s->bc.tab_kind.get<uint8_t>() + bc_id, 1, hipMemcpyDeviceToHost));
-  XLB_REQUIRE((kind >= XLBHIP_BC_HYBRID_BB_REGULARIZED && kind <= XLBHIP_BC_HYBRID_NEQ_REGULARIZED) || kind == XLBHIP_BC_HALFWAY_BB_PROFILE,
+  XLB_REQUIRE(bc_has_wall_table(kind),
               "time-dependent wall velocities: bc %d is of kind %d (HybridBC / HalfwayBounceBackBC with a profile)", bc_id, (int)kind);
   if (int rc = s->prof.declare_time_dependent(bc_id, n, storage_cells)) return rc;
   return flag_profile_bc(s, bc_id);
@@ -652,7 +658,7 @@ int xlbhip_stepper_momentum_transfer_at(xlbhip_stepper* s, int bc_id, int64_t ti
   uint8_t kind = 0;
   XLB_HIP(hipSetDevice(c->device));
   XLB_HIP(hipMemcpy(&kind, s->bc.tab_kind.get<uint8_t>() + bc_id, 1, hipMemcpyDeviceToHost));
-  XLB_REQUIRE((kind >= XLBHIP_BC_HYBRID_BB_REGULARIZED && kind <= XLBHIP_BC_HYBRID_NEQ_REGULARIZED) || kind == XLBHIP_BC_HALFWAY_BB_PROFILE,
+  XLB_REQUIRE(bc_has_wall_table(kind),
               "momentum_transfer through the stepper: bc %d is of kind %d (HybridBC / profile walls; plain walls use xlbhip_momentum_transfer)", bc_id,
               (int)kind);
   const void* pv = s->prof.table_for(bc_id, timestep);
@@ -664,9 +670,8 @@ int xlbhip_stepper_momentum_transfer_at(xlbhip_stepper* s, int bc_id, int64_t ti
   const int rc = by_lattice(s->lattice, [&](auto L) {
     return by_compute(s->cdt, [&](auto T) {
       using TT = decltype(T);
-      hipLaunchKernelGGL((k_momentum_transfer_tab<decltype(L), TT>), blocks_for(n), 256, 0, c->stream, view(f_0), view(bcm), view(miss), dims(f_0), bc_id,
-                         s->bc.tab_kind.get<uint8_t>(), s->bc.tab_values.get<const TT>(), s->prof.keys.get<uint32_t>(), static_cast<const TT*>(pv),
-                         s->prof.n, s->dist_keys.get<uint32_t>(), s->dist_vals.get<float>(), s->n_dist, dforce.get<double>());
+      hipLaunchKernelGGL((k_momentum_transfer_tab<decltype(L), TT>), blocks_for(n), BC_BLOCK, 0, c->stream, view(f_0), view(bcm), view(miss), dims(f_0), bc_id,
+                         bc_view<TT>(s, pv), dforce.get<double>());
       XLB_HIP(hipGetLastError());
       return 0;
     });
