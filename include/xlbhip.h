@@ -36,6 +36,7 @@ typedef struct xlbhip_field xlbhip_field;
 typedef struct xlbhip_stepper xlbhip_stepper;
 typedef struct xlbhip_ibm xlbhip_ibm;
 typedef struct xlbhip_stats xlbhip_stats;
+typedef struct xlbhip_scalar xlbhip_scalar;
 
 /* element types of a field; mirrors Precision in xlb/precision_policy.py:13-54 */
 enum {
@@ -485,6 +486,36 @@ int xlbhip_halo_exchange(xlbhip_ctx* ctx, int lattice, xlbhip_field* f);
 /* the exchange a fused pair of steps needs (fields with 2 ghost planes): every population of the neighbours' edge
  * planes and the face-crossing populations of the planes behind them */
 int xlbhip_halo_exchange_wide(xlbhip_ctx* ctx, int lattice, xlbhip_field* f);
+
+/* ---- scalar transport ------------------------------------------------------------------------------------------------------
+ * (no counterpart in the reference, which only names the physics: PhysicsType.ADE, xlb/physics_type.py; pinned by the NumPy
+ * restatement tests/_scalar_ref.py)  One scalar phi advected and diffused by the flow on the sub-lattice of rest + main directions
+ * (D2Q5 / D3Q7; scalar direction 0 = rest, 1.. = the lattice's main directions in ascending order), updated in the SAME kernel as
+ * the fluid: geq_j = w_j phi (1 + c_j.u / cs^2) with the post-streaming velocity u, g <- g - omega_scalar (g - geq), diffusivity
+ * cs^2 (1 / omega_scalar - 1/2), cs^2 = 1/4 (3-D) or 1/3 (2-D).  With a force or buoyancy the fluid collides through the
+ * exact-difference forced path with the per-cell force  force + buoyancy * (phi - reference)  (internal 3-component form), phi the
+ * sum of the post-streaming g.  Fields without ghost planes, FP32FP32 / FP64FP64 / FP64FP32, the bit-exact collisions.
+ * bcs: as for xlbhip_stepper_create; kinds 1..9 with constant values (no HybridBC, no profile walls). */
+int xlbhip_scalar_create(xlbhip_ctx* ctx, int lattice, int collision, int compute_dtype, int store_dtype, int n_bc, const xlbhip_bc_desc* bcs,
+                         xlbhip_scalar** out);
+int xlbhip_scalar_destroy(xlbhip_scalar* s);
+/* The scalar's rule at the cells of bc id bc_ids[i], acting where the FLUID's missing_mask bit of a main direction is set:
+ * rules[i] = 0 adiabatic (bounce-back; the default of every bc id), 1 Dirichlet (anti-bounce-back: phi = values[i] at the link
+ * midpoint; refused on a fullway wall), 2 do-nothing (the cell keeps its pre-streaming g, every direction).  At fullway cells the
+ * scalar is bounced fullway after the collision.  Replaces all rules set before. */
+int xlbhip_scalar_set_rules(xlbhip_scalar* s, int n, const int32_t* bc_ids, const int32_t* rules, const double* values);
+/* force, buoyancy: 3 doubles each or NULL (both NULL: passive scalar, the fluid is that of xlbhip_step bit for bit) */
+int xlbhip_scalar_set_coupling(xlbhip_scalar* s, const double* force, const double* buoyancy, double reference, double smagorinsky_coef);
+/* g_0 = geq(phi, u(f_0)); phi: a cardinality-1 float field, or NULL for the constant phi0 */
+int xlbhip_scalar_init(xlbhip_scalar* s, const xlbhip_field* f_0, const xlbhip_field* phi, double phi0, xlbhip_field* g_0);
+/* ScalarMoment()(g, phi): phi = sum_j g_j, sequential in j, in the compute dtype */
+int xlbhip_scalar_moment(xlbhip_ctx* ctx, int lattice, int compute_dtype, const xlbhip_field* g, xlbhip_field* phi);
+/* one coupled step (f, g)(t) -> (f, g)(t + 1); omega, omega_scalar in (0, 2] */
+int xlbhip_scalar_step(xlbhip_scalar* s, const xlbhip_field* f_src, xlbhip_field* f_dst, const xlbhip_field* g_src, xlbhip_field* g_dst,
+                       const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, double omega, double omega_scalar, int64_t timestep);
+/* n_steps x (step, swap both pairs) enqueued without a host wait; *result_in_b: the result is in (f_b, g_b) */
+int xlbhip_scalar_run(xlbhip_scalar* s, xlbhip_field* f_a, xlbhip_field* f_b, xlbhip_field* g_a, xlbhip_field* g_b, const xlbhip_field* bc_mask,
+                      const xlbhip_field* missing_mask, double omega, double omega_scalar, int64_t first_timestep, int64_t n_steps, int* result_in_b);
 
 #ifdef __cplusplus
 }

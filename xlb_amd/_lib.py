@@ -132,6 +132,14 @@ SIGNATURES = {
     "xlbhip_stats_sample": [_p, _p, _p],
     "xlbhip_stats_read": [_p, _i64, _p, C.POINTER(_i64), C.POINTER(_d), _p],
     "xlbhip_stats_reset": [_p],
+    "xlbhip_scalar_create": [_p, _i, _i, _i, _i, _i, C.POINTER(BcDesc), _pp],
+    "xlbhip_scalar_destroy": [_p],
+    "xlbhip_scalar_set_rules": [_p, _i, _p, _p, _p],
+    "xlbhip_scalar_set_coupling": [_p, _p, _p, _d, _d],
+    "xlbhip_scalar_init": [_p, _p, _p, _d, _p],
+    "xlbhip_scalar_moment": [_p, _i, _i, _p, _p],
+    "xlbhip_scalar_step": [_p, _p, _p, _p, _p, _p, _p, _d, _d, _i64],
+    "xlbhip_scalar_run": [_p, _p, _p, _p, _p, _p, _p, _d, _d, _i64, _i64, C.POINTER(C.c_int)],
 }
 
 _lib = None
@@ -769,6 +777,57 @@ class IBM:
     def free(self):
         if self._h:
             load().xlbhip_ibm_destroy(self._h)
+            self._h = _p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Scalar:
+    """Native scalar-transport object (xlbhip_scalar_create): the tables of the coupled fluid + scalar step."""
+
+    ADIABATIC, DIRICHLET, DO_NOTHING = 0, 1, 2  # SCALAR_* of csrc/scalar_kernels.hpp
+
+    def __init__(self, ctx, lattice_id, collision_id, compute_code, store_code, bc_descs):
+        self.ctx = ctx
+        n = len(bc_descs)
+        arr = (BcDesc * max(n, 1))(*bc_descs)
+        self._h = _p()
+        check(load().xlbhip_scalar_create(ctx.handle, lattice_id, collision_id, compute_code, store_code, n, arr, C.byref(self._h)))
+
+    def set_rules(self, rules):
+        """rules: [(bc id, ADIABATIC / DIRICHLET / DO_NOTHING, value)]"""
+        ids = np.array([r[0] for r in rules], dtype=np.int32)
+        kinds = np.array([r[1] for r in rules], dtype=np.int32)
+        values = np.array([r[2] for r in rules], dtype=np.float64)
+        check(load().xlbhip_scalar_set_rules(self._h, len(rules), ids.ctypes.data, kinds.ctypes.data, values.ctypes.data))
+
+    def set_coupling(self, force3, buoyancy3, reference, smagorinsky_coef):
+        f = None if force3 is None else np.ascontiguousarray(force3, dtype=np.float64)
+        b = None if buoyancy3 is None else np.ascontiguousarray(buoyancy3, dtype=np.float64)
+        check(load().xlbhip_scalar_set_coupling(self._h, None if f is None else f.ctypes.data, None if b is None else b.ctypes.data, float(reference),
+                                                float(smagorinsky_coef)))
+
+    def init(self, f_0, phi, phi0, g_0):
+        check(load().xlbhip_scalar_init(self._h, _hf(f_0), _h(phi), float(phi0), _hf(g_0)))
+
+    def step(self, f_src, f_dst, g_src, g_dst, bc_mask, missing_mask, omega, omega_scalar, timestep):
+        check(load().xlbhip_scalar_step(self._h, _hf(f_src), _hf(f_dst), _hf(g_src), _hf(g_dst), _h(bc_mask), _h(missing_mask), float(omega),
+                                        float(omega_scalar), int(timestep)))
+
+    def run(self, f_a, f_b, g_a, g_b, bc_mask, missing_mask, omega, omega_scalar, first_timestep, n_steps):
+        """n coupled steps; returns True when the result is in (f_b, g_b)."""
+        where = C.c_int()
+        check(load().xlbhip_scalar_run(self._h, _hf(f_a), _hf(f_b), _hf(g_a), _hf(g_b), _h(bc_mask), _h(missing_mask), float(omega),
+                                       float(omega_scalar), int(first_timestep), int(n_steps), C.byref(where)))
+        return bool(where.value)
+
+    def free(self):
+        if self._h:
+            load().xlbhip_scalar_destroy(self._h)
             self._h = _p()
 
     def __del__(self):

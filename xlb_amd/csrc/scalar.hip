@@ -1,0 +1,276 @@
+// libxlbhip: scalar transport.  The object owns the boundary tables of the coupled step (the fluid's, built from the same descriptors
+// as a stepper's, and the scalar's rule and value by bc id); a step enqueues the coupled kernel and the fluid's outflow pass on the
+// context's compute stream, and nothing here waits for the device.
+#include <cmath>
+#include <memory>
+#include <vector>
+
+#include "api_internal.hpp"
+#include "scalar_launch.hpp"
+
+using namespace xlb;
+
+struct xlbhip_scalar {
+  xlbhip_ctx* ctx = nullptr;
+  int lattice = 0, collision = 0, cdt = 0, sdt = 0;
+  int n_bc = 0;
+  bool has_outflow = false;
+  unsigned long long ids_packed = 0;
+  unsigned kinds_packed = 0;
+  DeviceBuf tab_kind;    // uint8 [256]
+  DeviceBuf tab_values;  // [256][27] compute dtype
+  DeviceBuf sc_rule;     // uint8 [256] SCALAR_*
+  DeviceBuf sc_value;    // [256] compute dtype
+  std::vector<uint8_t> kind_host = std::vector<uint8_t>(256, 0);
+  bool forced = false;
+  ScalarCoupling cp{{0, 0, 0}, {0, 0, 0}, 0.0};
+  double smag_cs = 0.17;
+};
+
+namespace xlb {
+
+static int scalar_q(int lattice) { return 2 * lattice_d(lattice) + 1; }
+
+static int upload_rules(xlbhip_scalar* s, const std::vector<uint8_t>& rule, const std::vector<double>& value) {
+  if (int rc = upload_bytes(rule.data(), 256, s->sc_rule)) return rc;
+  return upload_values(s->cdt, value, s->sc_value);
+}
+
+static int check_scalar_fields(const xlbhip_scalar* s, const xlbhip_field* fa, const xlbhip_field* fb, const xlbhip_field* ga, const xlbhip_field* gb,
+                               const xlbhip_field* bcm, const xlbhip_field* miss) {
+  XLB_REQUIRE(s && fa && fb && ga && gb, "null argument");
+  XLB_REQUIRE(fa != fb && ga != gb, "f_0 / f_1 and g_0 / g_1 must be different fields (double buffering)");
+  const int q = lattice_q(s->lattice), qs = scalar_q(s->lattice);
+  XLB_REQUIRE(fa->card == q && fb->card == q, "population fields must have cardinality %d", q);
+  XLB_REQUIRE(ga->card == qs && gb->card == qs, "scalar population fields must have cardinality %d", qs);
+  for (const xlbhip_field* f : {fa, fb, ga, gb}) {
+    XLB_REQUIRE(f->dtype == s->sdt, "population fields must have the store dtype %d", s->sdt);
+    XLB_REQUIRE(f->halo == 0, "scalar transport: fields without ghost planes only (single rank)");
+    XLB_REQUIRE(same_grid(f, fa), "the fields of a scalar-transport step must share one grid");
+  }
+  XLB_REQUIRE(fa->plane_stride == fb->plane_stride && ga->plane_stride == gb->plane_stride, "f_0 / f_1 or g_0 / g_1 layouts differ");
+  // the kernel's per-thread offsets inside an x plane are 32-bit byte offsets (8-byte elements, 4-byte missing words)
+  XLB_REQUIRE((size_t)fa->ny * fa->nz <= ((size_t)1 << 28), "scalar transport: an x plane of %d x %d cells is too large for the step kernel", fa->ny, fa->nz);
+  XLB_REQUIRE(s->lattice != XLBHIP_D2Q9 || fa->nx == 1, "a 2-D grid is stored as one x plane (%d given)", fa->nx);
+  if (s->n_bc > 0) {
+    XLB_REQUIRE(bcm && bcm->dtype == XLBHIP_U8 && bcm->card == 1 && same_grid(bcm, fa) && bcm->halo == 0, "bad or missing bc_mask field");
+    XLB_REQUIRE(miss && miss->dtype == XLBHIP_MISSING && same_grid(miss, fa) && miss->halo == 0, "bad or missing missing_mask field");
+  }
+  return 0;
+}
+
+static int check_omegas(double omega, double omega_s) {
+  XLB_REQUIRE(std::isfinite(omega) && omega > 0.0 && omega <= 2.0, "omega %g outside (0, 2]", omega);
+  XLB_REQUIRE(std::isfinite(omega_s) && omega_s > 0.0 && omega_s <= 2.0, "omega_scalar %g outside (0, 2]", omega_s);
+  return 0;
+}
+
+// one coupled step (f, g)(t) -> (f, g)(t + 1), then the auxiliary data of the fluid's ExtrapolationOutflowBC cells
+static int scalar_step_once(xlbhip_scalar* s, const xlbhip_field* fs, xlbhip_field* fd, const xlbhip_field* gs, xlbhip_field* gd, const xlbhip_field* bcm,
+                            const xlbhip_field* miss, double omega, double omega_s) {
+  xlbhip_ctx* c = s->ctx;
+  touch(fd);
+  touch(gd);
+  ScalarLaunch q;
+  StepLaunch& p = q.f;
+  p = StepLaunch();
+  p.src = fs->data;
+  p.dst = fd->data;
+  p.bc = s->n_bc > 0 ? static_cast<const uint8_t*>(bcm->data) : nullptr;
+  p.miss = s->n_bc > 0 ? static_cast<const uint32_t*>(miss->data) : nullptr;
+  p.tab_kind = s->tab_kind.get<uint8_t>();
+  p.tab_values = s->tab_values.get();
+  p.ids_packed = s->ids_packed;
+  p.kinds_packed = s->kinds_packed;
+  p.n_bc = s->n_bc;
+  p.plane_stride = fs->plane_stride;
+  p.nx = fs->nx;
+  p.ny = fs->ny;
+  p.nz = fs->nz;
+  p.halo = 0;
+  p.x_begin = 0;
+  p.x_count = fs->nx;
+  p.omega = omega;
+  p.smag_cs = s->smag_cs;
+  p.compute_dtype = s->cdt;
+  p.store_dtype = s->sdt;
+  p.vec = (int)opt(c, "vec", 0);
+  p.has_bc = s->n_bc > 0 ? 2 : 0;
+  p.stream = c->stream;
+  q.gsrc = gs->data;
+  q.gdst = gd->data;
+  q.g_plane_stride = gs->plane_stride;
+  q.sc_rule = s->sc_rule.get<uint8_t>();
+  q.sc_value = s->sc_value.get();
+  q.cp = s->cp;
+  q.omega_s = omega_s;
+  const int coll = s->collision | (s->forced ? COLL_FORCED : 0);
+  int rc;
+  if (s->lattice == XLBHIP_D2Q9)
+    rc = launch_scalar_d2q9(q, coll);
+  else if (s->lattice == XLBHIP_D3Q19)
+    rc = launch_scalar_d3q19(q, coll);
+  else
+    rc = launch_scalar_d3q27(q, coll);
+  if (rc || !s->has_outflow) return rc;
+  const size_t n = fd->cells();
+  return by_lattice(s->lattice, [&](auto L) {
+    return by_compute(s->cdt, [&](auto T) {
+      using TT = decltype(T);
+      const BcView<TT> tb = {s->tab_kind.get<uint8_t>(), s->tab_values.get<const TT>(), nullptr, nullptr, 0, nullptr, nullptr, 0};
+      hipLaunchKernelGGL((k_outflow_aux<decltype(L), TT>), blocks_for(n), BC_BLOCK, 0, c->stream, view(fs), view(fd), view(bcm), view(miss), dims(fd), tb);
+      XLB_HIP(hipGetLastError());
+      return 0;
+    });
+  });
+}
+
+}  // namespace xlb
+
+extern "C" {
+
+int xlbhip_scalar_create(xlbhip_ctx* c, int lattice, int collision, int cdt, int sdt, int n_bc, const xlbhip_bc_desc* bcs, xlbhip_scalar** out) {
+  XLB_REQUIRE(c && out, "null argument");
+  XLB_REQUIRE(lattice_q(lattice) > 0, "unknown lattice %d", lattice);
+  XLB_REQUIRE(collision == XLBHIP_BGK || collision == XLBHIP_KBC || collision == XLBHIP_SMAGORINSKY_LES_BGK, "unknown collision %d", collision);
+  XLB_REQUIRE(!(collision == XLBHIP_KBC && lattice == XLBHIP_D3Q19), "Velocity set not supported: D3Q19 has no KBC (reference kbc.py:65-66)");
+  XLB_REQUIRE((cdt == XLBHIP_F32 && sdt == XLBHIP_F32) || (cdt == XLBHIP_F64 && (sdt == XLBHIP_F64 || sdt == XLBHIP_F32)),
+              "scalar transport is built for FP32FP32, FP64FP64 and FP64FP32 only (got compute=%d store=%d)", cdt, sdt);
+  XLB_REQUIRE(n_bc == 0 || bcs, "null bc list");
+  auto s = std::make_unique<xlbhip_scalar>();
+  const int q = lattice_q(lattice);
+  std::vector<double> vals(256 * 27, 0.0);
+  for (int i = 0; i < n_bc; ++i) {
+    const xlbhip_bc_desc& b = bcs[i];
+    XLB_REQUIRE(b.id >= 1 && b.id <= 255, "bc id %d out of range 1..255", b.id);
+    XLB_REQUIRE(s->kind_host[b.id] == 0, "bc id %d used twice", b.id);
+    const bool supported = (b.kind >= XLBHIP_BC_EQUILIBRIUM && b.kind <= XLBHIP_BC_DO_NOTHING) || bc_is_zouhe_family(b.kind) ||
+                           b.kind == XLBHIP_BC_EXTRAPOLATION_OUTFLOW;
+    XLB_REQUIRE(supported, "scalar transport: bc kind %d (HybridBC, profile walls) is not supported by the coupled step", b.kind);
+    if (b.kind == XLBHIP_BC_EXTRAPOLATION_OUTFLOW) s->has_outflow = true;
+    s->kind_host[b.id] = (uint8_t)b.kind;
+    for (int l = 0; l < q; ++l) vals[b.id * 27 + l] = b.values[l];
+  }
+  for (int i = 0; i < n_bc && i < 8; ++i) {
+    s->ids_packed |= (unsigned long long)(bcs[i].id & 0xff) << (8 * i);
+    s->kinds_packed |= (unsigned)(bcs[i].kind & 0xf) << (4 * i);
+  }
+  XLB_HIP(hipSetDevice(c->device));
+  s->ctx = c;
+  s->lattice = lattice;
+  s->collision = collision;
+  s->cdt = cdt;
+  s->sdt = sdt;
+  s->n_bc = n_bc;
+  if (int rc = upload_bytes(s->kind_host.data(), 256, s->tab_kind)) return rc;
+  if (int rc = upload_values(cdt, vals, s->tab_values)) return rc;
+  if (int rc = upload_rules(s.get(), std::vector<uint8_t>(256, SCALAR_ADIABATIC), std::vector<double>(256, 0.0))) return rc;
+  *out = s.release();
+  return 0;
+}
+
+int xlbhip_scalar_destroy(xlbhip_scalar* s) {
+  if (!s) return 0;
+  (void)hipSetDevice(s->ctx->device);
+  (void)hipStreamSynchronize(s->ctx->stream);
+  delete s;
+  return 0;
+}
+
+int xlbhip_scalar_set_rules(xlbhip_scalar* s, int n, const int32_t* bc_ids, const int32_t* rules, const double* values) {
+  XLB_REQUIRE(s && n >= 0 && (n == 0 || (bc_ids && rules && values)), "bad argument");
+  std::vector<uint8_t> rule(256, SCALAR_ADIABATIC);
+  std::vector<double> value(256, 0.0);
+  for (int i = 0; i < n; ++i) {
+    const int id = bc_ids[i];
+    XLB_REQUIRE(id >= 1 && id <= 255 && s->kind_host[id] != 0, "scalar rule for bc id %d, which is none of this stepper's boundary conditions", id);
+    XLB_REQUIRE(rules[i] >= SCALAR_ADIABATIC && rules[i] <= SCALAR_DO_NOTHING, "unknown scalar rule %d", rules[i]);
+    XLB_REQUIRE(!(rules[i] == SCALAR_DIRICHLET && s->kind_host[id] == XLBHIP_BC_FULLWAY_BB),
+                "a Dirichlet scalar rule cannot sit on a fullway bounce-back wall (bc id %d): the scalar is bounced fullway there", id);
+    XLB_REQUIRE(std::isfinite(values[i]), "scalar rule of bc id %d: value is not finite", id);
+    rule[id] = (uint8_t)rules[i];
+    value[id] = values[i];
+  }
+  XLB_HIP(hipSetDevice(s->ctx->device));
+  XLB_HIP(hipStreamSynchronize(s->ctx->stream));  // (launches may still read the old tables)
+  return upload_rules(s, rule, value);
+}
+
+int xlbhip_scalar_set_coupling(xlbhip_scalar* s, const double* force, const double* buoyancy, double reference, double smagorinsky_coef) {
+  XLB_REQUIRE(s, "null argument");
+  s->forced = force != nullptr || buoyancy != nullptr;
+  for (int a = 0; a < 3; ++a) {
+    s->cp.force[a] = force ? force[a] : 0.0;
+    s->cp.buoyancy[a] = buoyancy ? buoyancy[a] : 0.0;
+  }
+  s->cp.reference = reference;
+  s->smag_cs = smagorinsky_coef;
+  return 0;
+}
+
+int xlbhip_scalar_init(xlbhip_scalar* s, const xlbhip_field* f_0, const xlbhip_field* phi, double phi0, xlbhip_field* g_0) {
+  XLB_REQUIRE(s && f_0 && g_0, "null argument");
+  XLB_CHECK_POP(f_0, s->lattice, "scalar_init(f_0)");
+  XLB_REQUIRE(is_float(g_0->dtype) && g_0->card == scalar_q(s->lattice) && same_grid(g_0, f_0) && g_0->halo == 0 && f_0->halo == 0,
+              "scalar_init: g_0 must be a %d-population float field on f_0's grid, without ghost planes", scalar_q(s->lattice));
+  XLB_REQUIRE(!phi || (is_float(phi->dtype) && phi->card == 1 && same_grid(phi, f_0) && phi->halo == 0), "scalar_init: bad scalar field");
+  xlbhip_ctx* c = s->ctx;
+  XLB_HIP(hipSetDevice(c->device));
+  touch(g_0);
+  const size_t n = f_0->cells();
+  return by_lattice(s->lattice, [&](auto L) {
+    return by_compute(s->cdt, [&](auto T) {
+      using TT = decltype(T);
+      hipLaunchKernelGGL((k_scalar_init<decltype(L), TT>), blocks_for(n), 256, 0, c->stream, view(f_0), view(phi), (TT)phi0, view(g_0), dims(f_0));
+      XLB_HIP(hipGetLastError());
+      return 0;
+    });
+  });
+}
+
+int xlbhip_scalar_moment(xlbhip_ctx* c, int lattice, int compute_dtype, const xlbhip_field* g, xlbhip_field* phi) {
+  XLB_REQUIRE(c && g && phi, "null argument");
+  XLB_REQUIRE(lattice_q(lattice) > 0, "unknown lattice %d", lattice);
+  XLB_REQUIRE(compute_dtype == XLBHIP_F32 || compute_dtype == XLBHIP_F64, "bad compute dtype %d", compute_dtype);
+  XLB_REQUIRE(is_float(g->dtype) && g->card == scalar_q(lattice), "scalar_moment: expected a %d-population float field", scalar_q(lattice));
+  XLB_REQUIRE(is_float(phi->dtype) && phi->card == 1 && same_grid(phi, g) && phi->halo == g->halo, "scalar_moment: bad output field");
+  XLB_HIP(hipSetDevice(c->device));
+  touch(phi);
+  const size_t n = g->cells();
+  return by_lattice(lattice, [&](auto L) {
+    return by_compute(compute_dtype, [&](auto T) {
+      using TT = decltype(T);
+      hipLaunchKernelGGL((k_scalar_moment<decltype(L), TT>), blocks_for(n), 256, 0, c->stream, view(g), view(phi), dims(g));
+      XLB_HIP(hipGetLastError());
+      return 0;
+    });
+  });
+}
+
+int xlbhip_scalar_step(xlbhip_scalar* s, const xlbhip_field* f_src, xlbhip_field* f_dst, const xlbhip_field* g_src, xlbhip_field* g_dst,
+                       const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, double omega, double omega_scalar, int64_t timestep) {
+  (void)timestep;  // (no time-dependent walls in the coupled step)
+  if (int rc = check_scalar_fields(s, f_src, f_dst, g_src, g_dst, bc_mask, missing_mask)) return rc;
+  if (int rc = check_omegas(omega, omega_scalar)) return rc;
+  XLB_HIP(hipSetDevice(s->ctx->device));
+  return scalar_step_once(s, f_src, f_dst, g_src, g_dst, bc_mask, missing_mask, omega, omega_scalar);
+}
+
+int xlbhip_scalar_run(xlbhip_scalar* s, xlbhip_field* f_a, xlbhip_field* f_b, xlbhip_field* g_a, xlbhip_field* g_b, const xlbhip_field* bc_mask,
+                      const xlbhip_field* missing_mask, double omega, double omega_scalar, int64_t first_timestep, int64_t n_steps, int* result_in_b) {
+  (void)first_timestep;
+  XLB_REQUIRE(result_in_b && n_steps >= 0, "bad argument");
+  if (int rc = check_scalar_fields(s, f_a, f_b, g_a, g_b, bc_mask, missing_mask)) return rc;
+  if (int rc = check_omegas(omega, omega_scalar)) return rc;
+  XLB_HIP(hipSetDevice(s->ctx->device));
+  xlbhip_field *fc = f_a, *fo = f_b, *gc = g_a, *go = g_b;
+  for (int64_t i = 0; i < n_steps; ++i) {
+    if (int rc = scalar_step_once(s, fc, fo, gc, go, bc_mask, missing_mask, omega, omega_scalar)) return rc;
+    std::swap(fc, fo);
+    std::swap(gc, go);
+  }
+  *result_in_b = fc == f_b ? 1 : 0;
+  return 0;
+}
+
+}  // extern "C"

@@ -11,3 +11,9 @@ from .boundary_condition import (
     ExtrapolationOutflowBC as ExtrapolationOutflowBC,
     HybridBC as HybridBC,
 )
+from .scalar_boundary_condition import (
+    ScalarBoundaryCondition as ScalarBoundaryCondition,
+    ScalarDirichletBC as ScalarDirichletBC,
+    ScalarAdiabaticBC as ScalarAdiabaticBC,
+    ScalarDoNothingBC as ScalarDoNothingBC,
+)

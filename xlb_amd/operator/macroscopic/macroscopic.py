@@ -48,3 +48,12 @@ class SecondMoment(Operator):
     def hip_implementation(self, f, pi):
         _lib.check(_lib.load().xlbhip_second_moment(self._ctx.handle, self.velocity_set.hip_id, self._compute_code, f.handle, pi.handle))
         return pi
+
+
+class ScalarMoment(Operator):
+    """phi = sum_j g_j of a scalar-transport field g (cardinality 2 d + 1: ScalarTransportStepper), cardinality 1."""
+
+    @Operator.register_backend(ComputeBackend.HIP)
+    def hip_implementation(self, g, phi):
+        _lib.check(_lib.load().xlbhip_scalar_moment(self._ctx.handle, self.velocity_set.hip_id, self._compute_code, g.handle, phi.handle))
+        return phi
