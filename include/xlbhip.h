@@ -37,6 +37,7 @@ typedef struct xlbhip_stepper xlbhip_stepper;
 typedef struct xlbhip_ibm xlbhip_ibm;
 typedef struct xlbhip_stats xlbhip_stats;
 typedef struct xlbhip_scalar xlbhip_scalar;
+typedef struct xlbhip_adjoint xlbhip_adjoint;
 
 /* element types of a field; mirrors Precision in xlb/precision_policy.py:13-54 */
 enum {
@@ -516,6 +517,35 @@ int xlbhip_scalar_step(xlbhip_scalar* s, const xlbhip_field* f_src, xlbhip_field
 /* n_steps x (step, swap both pairs) enqueued without a host wait; *result_in_b: the result is in (f_b, g_b) */
 int xlbhip_scalar_run(xlbhip_scalar* s, xlbhip_field* f_a, xlbhip_field* f_b, xlbhip_field* g_a, xlbhip_field* g_b, const xlbhip_field* bc_mask,
                       const xlbhip_field* missing_mask, double omega, double omega_scalar, int64_t first_timestep, int64_t n_steps, int* result_in_b);
+
+/* ---- discrete adjoint of the fused BGK step ---------------------------------------------------------------------------------
+ * (the reference differentiates its stepper through jax.grad and ships a Warp forward / backward stepper pair,
+ * examples/out_of_core/autodiff_lbm.py; here the backward pass is hand-written HIP, pinned by the NumPy restatement
+ * tests/_adjoint_ref.py)  One forward step is f_{n+1} = S(f_n; omega): pull streaming, the streaming-step BCs, BGK, the fullway bounce.
+ * An adjoint step takes the forward state f_n and the cotangent lam_{n+1} = dL/df_{n+1} and gives lam_n = (dS/df_n)^T lam_{n+1}; its
+ * omega term sum_cells sum_l lam_l (feq_l - f*_l) is added, widened to fp64 and in a fixed order, to a device scalar of the object.
+ * The Jacobian is that of the exact-arithmetic map (casts count as the identity).  BGK without a force; fields without ghost planes;
+ * FP32FP32 / FP64FP64 / FP64FP32; bcs: as for xlbhip_stepper_create, kinds 1..4 only (equilibrium, halfway bounce-back with a constant
+ * wall velocity or none, fullway bounce-back, do-nothing).  State and cotangent fields have the lattice's cardinality and the store
+ * dtype. */
+int xlbhip_adjoint_create(xlbhip_ctx* ctx, int lattice, int compute_dtype, int store_dtype, int n_bc, const xlbhip_bc_desc* bcs, xlbhip_adjoint** out);
+int xlbhip_adjoint_destroy(xlbhip_adjoint* a);
+/* lam_out = (dS/df_n)^T lam_in; two launches through a scratch field of the object (the local transpose, the transposed streaming) */
+int xlbhip_adjoint_step(xlbhip_adjoint* a, const xlbhip_field* f_n, const xlbhip_field* lam_in, xlbhip_field* lam_out, const xlbhip_field* bc_mask,
+                        const xlbhip_field* missing_mask, double omega);
+/* The adjoint steps over states[0 .. n_states-1] = f_0 .. f_{N-1}, last first, enqueued without a host wait: lam_a holds lam_N on
+ * entry; one fused launch per step (the carried state is mu = dL/df*, in the store dtype) and one closing launch, ping-ponging
+ * between lam_a and lam_b (both overwritten); *result_in_b: lam_0 is in lam_b.  The bits are those of n_states chained
+ * xlbhip_adjoint_step calls. */
+int xlbhip_adjoint_run(xlbhip_adjoint* a, int64_t n_states, const xlbhip_field* const* states, xlbhip_field* lam_a, xlbhip_field* lam_b,
+                       const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, double omega, int* result_in_b);
+/* dL/domega accumulated by every step since the last reset (waits for the compute stream) / sets it to zero (enqueued) */
+int xlbhip_adjoint_omega_gradient(xlbhip_adjoint* a, double* out);
+int xlbhip_adjoint_reset(xlbhip_adjoint* a);
+/* MacroscopicAdjoint()(f, rho_bar, u_bar, lam): lam_l = rho_bar + sum_d u_bar_d (c_dl - u_d) / rho, the transpose of Macroscopic at f
+ * applied to (dL/drho, dL/du); rho_bar (cardinality 1) or u_bar (cardinality d) may be NULL for zero */
+int xlbhip_macroscopic_adjoint(xlbhip_ctx* ctx, int lattice, int compute_dtype, const xlbhip_field* f, const xlbhip_field* rho_bar, const xlbhip_field* u_bar,
+                               xlbhip_field* lam);
 
 #ifdef __cplusplus
 }

@@ -140,6 +140,13 @@ SIGNATURES = {
     "xlbhip_scalar_moment": [_p, _i, _i, _p, _p],
     "xlbhip_scalar_step": [_p, _p, _p, _p, _p, _p, _p, _d, _d, _i64],
     "xlbhip_scalar_run": [_p, _p, _p, _p, _p, _p, _p, _d, _d, _i64, _i64, C.POINTER(C.c_int)],
+    "xlbhip_adjoint_create": [_p, _i, _i, _i, _i, C.POINTER(BcDesc), _pp],
+    "xlbhip_adjoint_destroy": [_p],
+    "xlbhip_adjoint_step": [_p, _p, _p, _p, _p, _p, _d],
+    "xlbhip_adjoint_run": [_p, _i64, _pp, _p, _p, _p, _p, _d, C.POINTER(C.c_int)],
+    "xlbhip_adjoint_omega_gradient": [_p, C.POINTER(_d)],
+    "xlbhip_adjoint_reset": [_p],
+    "xlbhip_macroscopic_adjoint": [_p, _i, _i, _p, _p, _p, _p],
 }
 
 _lib = None
@@ -835,6 +842,50 @@ class Scalar:
             self.free()
         except Exception:
             pass
+
+
+class Adjoint:
+    """Native adjoint object (xlbhip_adjoint_create): the boundary tables of the fused adjoint step and the device scalar dL/domega."""
+
+    def __init__(self, ctx, lattice_id, compute_code, store_code, bc_descs):
+        self.ctx = ctx
+        n = len(bc_descs)
+        arr = (BcDesc * max(n, 1))(*bc_descs)
+        self._h = _p()
+        check(load().xlbhip_adjoint_create(ctx.handle, lattice_id, compute_code, store_code, n, arr, C.byref(self._h)))
+
+    def step(self, f_n, lam_in, lam_out, bc_mask, missing_mask, omega):
+        check(load().xlbhip_adjoint_step(self._h, _hf(f_n), _hf(lam_in), _hf(lam_out), _h(bc_mask), _h(missing_mask), float(omega)))
+
+    def run(self, states, lam_a, lam_b, bc_mask, missing_mask, omega):
+        """The adjoint steps over states = [f_0 .. f_{N-1}], last first, lam_N in lam_a; returns True when lam_0 is in lam_b."""
+        where = C.c_int()
+        arr = (C.c_void_p * max(len(states), 1))(*[_hf(f) for f in states])
+        check(load().xlbhip_adjoint_run(self._h, len(states), arr, _hf(lam_a), _hf(lam_b), _h(bc_mask), _h(missing_mask), float(omega), C.byref(where)))
+        return bool(where.value)
+
+    def omega_gradient(self):
+        out = _d()
+        check(load().xlbhip_adjoint_omega_gradient(self._h, C.byref(out)))
+        return out.value
+
+    def reset(self):
+        check(load().xlbhip_adjoint_reset(self._h))
+
+    def free(self):
+        if self._h:
+            load().xlbhip_adjoint_destroy(self._h)
+            self._h = _p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def macroscopic_adjoint(ctx, lattice_id, compute_code, f, rho_bar, u_bar, lam):
+    check(load().xlbhip_macroscopic_adjoint(ctx.handle, lattice_id, compute_code, _hf(f), _h(rho_bar), _h(u_bar), _hf(lam)))
 
 
 class Stats:

@@ -57,3 +57,14 @@ class ScalarMoment(Operator):
     def hip_implementation(self, g, phi):
         _lib.check(_lib.load().xlbhip_scalar_moment(self._ctx.handle, self.velocity_set.hip_id, self._compute_code, g.handle, phi.handle))
         return phi
+
+
+class MacroscopicAdjoint(Operator):
+    """The transpose of Macroscopic at f applied to (dL/drho, dL/du): dL/df_l = rho_bar + sum_d u_bar_d (c_dl - u_d) / rho, written into
+    the population-shaped field lam.  This is how a loss stated in rho and u enters an AdjointStepper sweep.  rho_bar (cardinality 1)
+    or u_bar (cardinality d) may be None for zero.  No counterpart in the reference, which gets it from jax.grad."""
+
+    @Operator.register_backend(ComputeBackend.HIP)
+    def hip_implementation(self, f, rho_bar, u_bar, lam):
+        _lib.macroscopic_adjoint(self._ctx, self.velocity_set.hip_id, self._compute_code, f, rho_bar, u_bar, lam)
+        return lam

@@ -1,7 +1,8 @@
-"""Steppers of the HIP backend: the fused incompressible Navier-Stokes step, the same with an immersed boundary, and the same
-with a transported scalar."""
+"""Steppers of the HIP backend: the fused incompressible Navier-Stokes step, the same with an immersed boundary, the same
+with a transported scalar, and the discrete adjoint of the plain BGK step."""
 
 from .stepper import Stepper as Stepper
 from .nse_stepper import IncompressibleNavierStokesStepper as IncompressibleNavierStokesStepper
 from .ibm_stepper import IBMStepper as IBMStepper, IBMBody as IBMBody, RigidMotion as RigidMotion, RigidDynamics as RigidDynamics
 from .scalar_stepper import ScalarTransportStepper as ScalarTransportStepper
+from .adjoint_stepper import AdjointStepper as AdjointStepper
