@@ -42,10 +42,18 @@ def main():
     lib = _lib.load()
     P, W, E = 6, 11, 8
     buf = (C.c_ulonglong * (P * W * E))()
-    lib.xlbhip_debug_step2_trace.argtypes = [C.c_void_p, C.c_int]
-    rc = lib.xlbhip_debug_step2_trace(buf, P * W * E)
-    assert rc == 0, rc
-    t = np.array(buf, dtype=np.int64).reshape(P, W, E)
+    # the stamp buffer is per translation unit: the strip-buffer instantiations (the default at this size) have their own reader
+    for name in ("xlbhip_debug_step2_trace_strips", "xlbhip_debug_step2_trace"):
+        fn = getattr(lib, name, None)
+        if fn is None:  # that translation unit was built without -DXLB_STEP2_TRACE
+            continue
+        fn.argtypes = [C.c_void_p, C.c_int]
+        rc = fn(buf, P * W * E)
+        assert rc == 0, rc
+        t = np.array(buf, dtype=np.int64).reshape(P, W, E)
+        if t.any():
+            print(f"# stamps from {name}")
+            break
     events = [e for e in range(E) if (t[:, :, e] != 0).all()]
     print(f"# {workload} {n}^3: cycles between stamps (mean over {P} planes), events present: {events}")
     print("wave " + " ".join(f"{a}->{b:>1d}".rjust(8) for a, b in zip(events[:-1], events[1:])) + "  7->0(next)".rjust(12) + "   plane".rjust(10))

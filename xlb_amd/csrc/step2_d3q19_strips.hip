@@ -22,3 +22,14 @@ int launch_step2_d3q19_bgk_strips(const Step2Launch& p) {
 }
 
 }  // namespace xlb
+
+#ifdef XLB_STEP2_TRACE
+// debug builds only (tools/step2_phase_trace.py): the phase stamps of the last launch of THIS translation unit's kernels (the stamp
+// buffer is per translation unit; step2_d3q19.hip has the reader of the instantiations without strip buffers)
+extern "C" int xlbhip_debug_step2_trace_strips(unsigned long long* out, int n) {
+  constexpr int N = xlb::TRACE_PLANES * xlb::TRACE_WAVES * xlb::TRACE_EVENTS;
+  if (n < N) return N;
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(xlb::g_step2_trace), sizeof(unsigned long long) * N) == hipSuccess ? 0 : -1;
+}
+#endif

@@ -27,7 +27,11 @@ namespace xlb {
 // from the collision (and perturbs the pipeline: the stores drain too).
 #ifdef XLB_STEP2_TRACE
 // TRACE_BLOCK: the block stamped (cavity 512^3, 8 x-segments of 512 tile columns, hull tiles first: 522 = a hull tile's second segment, 812 = a clean item)
-constexpr int TRACE_PLANES = 6, TRACE_EVENTS = 8, TRACE_WAVES = 11, TRACE_FIRST = 40, TRACE_BLOCK = 300;
+// (-DXLB_STEP2_TRACE_BLOCK=n picks another one)
+#ifndef XLB_STEP2_TRACE_BLOCK
+#define XLB_STEP2_TRACE_BLOCK 300
+#endif
+constexpr int TRACE_PLANES = 6, TRACE_EVENTS = 8, TRACE_WAVES = 11, TRACE_FIRST = 40, TRACE_BLOCK = XLB_STEP2_TRACE_BLOCK;
 static __device__ unsigned long long g_step2_trace[TRACE_PLANES * TRACE_WAVES * TRACE_EVENTS];
 __device__ __forceinline__ void trace_stamp(int d, int e) {
   __builtin_amdgcn_sched_barrier(0);
@@ -54,6 +58,13 @@ constexpr int nth_cz(int cz, int k) {  // k-th population (index order) with c_z
   for (int l = 0; l < L::Q; ++l)
     if (L::c(2, l) == cz && k-- == 0) return l;
   return 0;
+}
+
+template <class L>
+constexpr unsigned cz_mask(int cz) {  // bit l set: c_z(l) == cz
+  unsigned m = 0;
+  for (int l = 0; l < L::Q; ++l) m |= (L::c(2, l) == cz ? 1u : 0u) << l;
+  return m;
 }
 
 // LDS ring of f(t+1), packed by population LIFETIME.  Plane p of f(t+1) is produced by phase A of iteration p - 2 and
@@ -217,6 +228,30 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
     return (R::gbase(g) + R::template buf<life>(q) * R::gcount(g)) * NE + R::gidx(l) * NE;
   };
 
+  // Arms of a boundary wave (mall != 0: the wave's union of missing bits).  With the half-tile shift the z walls of a box sit in the
+  // middle of one tile column, where every row wave holds exactly one wall lane: its union is the c_z = +1 set (wall at z = 0) or the
+  // c_z = -1 set (z = nz - 1) — 5 of 19 populations.  Such a wave takes a FACE arm: only the populations of that set go through the
+  // per-lane redirect machinery (64-bit pull address, select-indexed LDS read, wall term), the others are handled exactly as in a
+  // fluid wave — their missing bit is 0 in every lane of the wave by definition of the union, so skipping their select is exact.
+  // Every other union (y / x faces, edges, corners, interior solids, both z walls in one wave) takes the generic arm: all Q
+  // populations.  fn is instantiated once per arm with the arm's population set as a compile-time mask.
+  // (D3Q19 only: the D3Q27 instantiation is on request, 181 VGPRs, and keeps the generic arm alone.)
+  constexpr unsigned CZP = cz_mask<L>(1), CZM = cz_mask<L>(-1), ALLQ = (1u << Q) - 1u;
+  constexpr bool FACE_ARMS = HASBC != 0 && !M::WIDE;
+  auto bc_arm = [&](unsigned mall, auto&& fn) __attribute__((always_inline)) {
+    if constexpr (FACE_ARMS) {
+      if ((mall & ~CZP) == 0u) {
+        fn(std::integral_constant<unsigned, CZP>{});
+        return;
+      }
+      if ((mall & ~CZM) == 0u) {
+        fn(std::integral_constant<unsigned, CZM>{});
+        return;
+      }
+    }
+    fn(std::integral_constant<unsigned, ALLQ>{});
+  };
+
   // tile of this block: from the launch's order table when there is one (hull tiles first — with boundary
   // conditions they are the expensive ones, and a CU that starts with one should get a cheap one next), else
   // a compact patch of tiles per XCD (blocks b and b + 8 share an XCD)
@@ -369,20 +404,28 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
     if constexpr (HASBC != 0) {
       if (mall != 0u) {
         // Boundary wave: a halfway-wall lane pulls each of its missing directions from its OWN cell's OPPOSITE population — inside the
-        // same pull instruction, through a per-lane 64-bit address (4 VALU per pull, boundary waves only).  Exactly Q loads on either
-        // side of this wave-uniform branch, all of them visible to the compiler, so its vmcnt model of the loop stays exact
-        // (round 2's extra inline-asm loads: measured and removed, profiles/r03/step2_redirect.md).
+        // same pull instruction, through a per-lane 64-bit address (4 VALU per pull, boundary waves only).  Exactly Q loads in every arm
+        // of this wave-uniform branch, in population order, all of them visible to the compiler, so its vmcnt model of the loop stays
+        // exact (round 2's extra inline-asm loads: measured and removed, profiles/r03/step2_redirect.md).  The populations outside the
+        // arm's set are pulled as in a fluid wave: uniform row base + 32-bit offset.
         const unsigned kind = M::kind(w);
         const unsigned m = (kind == K_HW || kind == M::K_HWM) ? M::missing(w) : 0u;
         const unsigned voff = cell_a * ES;
-        static_for<Q>([&](auto lc) {
-          constexpr int l = decltype(lc)::value;
-          constexpr int cx = L::c(0, l), cy = L::c(1, l), cz = L::c(2, l);
-          const S* row = pull_base + (size_t)l * pull_stride + (ptrdiff_t)Xs[cx + 1] * pull_pc;         // uniform
-          const S* own = a.src + (size_t)opp<L>(l) * a.plane_stride + (ptrdiff_t)x * pc;                // uniform (the field itself, also for the halo wave of a strip build)
-          const bool red = ((m >> l) & 1u) != 0u;
-          const char* p = reinterpret_cast<const char*>(red ? own : row) + (red ? voff : Yb[cy + 1] + Zb[cz + 1]);
-          raw[l] = *reinterpret_cast<const S*>(p);
+        bc_arm(mall, [&](auto mc) __attribute__((always_inline)) {
+          constexpr unsigned MASK = decltype(mc)::value;
+          static_for<Q>([&](auto lc) {
+            constexpr int l = decltype(lc)::value;
+            constexpr int cx = L::c(0, l), cy = L::c(1, l), cz = L::c(2, l);
+            const S* row = pull_base + (size_t)l * pull_stride + (ptrdiff_t)Xs[cx + 1] * pull_pc;         // uniform
+            if constexpr (((MASK >> l) & 1u) != 0u) {
+              const S* own = a.src + (size_t)opp<L>(l) * a.plane_stride + (ptrdiff_t)x * pc;              // uniform (the field itself, also for the halo wave of a strip build)
+              const bool red = ((m >> l) & 1u) != 0u;
+              const char* p = reinterpret_cast<const char*>(red ? own : row) + (red ? voff : Yb[cy + 1] + Zb[cz + 1]);
+              raw[l] = *reinterpret_cast<const S*>(p);
+            } else {
+              raw[l] = ld(row, Yb[cy + 1] + Zb[cz + 1]);
+            }
+          });
         });
         return;
       }
@@ -409,21 +452,27 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
   // halfway wall, population l of a lane whose missing bit is set: the redirected pull `got` (own cell, opposite
   // population) + the moving-wall term; the reference adds its 0.0 term for no-slip walls too (bc_halfway_bounce_back.py:116-134).
   // Branch-free over the wave: BRANCHES, not arithmetic, made boundary waves slow (z-face tiles cost 2.25x a fluid tile
-  // with per-population scalar branches in four places).  any_moving is wave-uniform.
-  auto hw_apply = [&](T(&f)[Q], const T(&got)[Q], unsigned mm, unsigned w, bool any_moving) __attribute__((always_inline)) {
+  // with per-population scalar branches in four places).  any_moving is wave-uniform.  mc: the arm's population set (bc_arm) — no
+  // lane of the wave has a missing bit outside it.
+  auto hw_apply = [&](auto mc, T(&f)[Q], const T(&got)[Q], unsigned mm, unsigned w, bool any_moving) __attribute__((always_inline)) {
+    constexpr unsigned MASK = decltype(mc)::value;
     if (!any_moving) {
       static_for<Q>([&](auto lc) {
         constexpr int l = decltype(lc)::value;
-        const T cand = got[l] + T(0);
-        f[l] = ((mm >> l) & 1u) ? cand : f[l];
+        if constexpr (((MASK >> l) & 1u) != 0u) {
+          const T cand = got[l] + T(0);
+          f[l] = ((mm >> l) & 1u) ? cand : f[l];
+        }
       });
     } else {
       const T* val = bcval + M::slot(w) * 32u;
       const bool mov = M::kind(w) == M::K_HWM;
       static_for<Q>([&](auto lc) {
         constexpr int l = decltype(lc)::value;
-        const T cand = got[l] + (mov ? val[l] : T(0));
-        f[l] = ((mm >> l) & 1u) ? cand : f[l];
+        if constexpr (((MASK >> l) & 1u) != 0u) {
+          const T cand = got[l] + (mov ? val[l] : T(0));
+          f[l] = ((mm >> l) & 1u) ? cand : f[l];
+        }
       });
     }
   };
@@ -440,7 +489,8 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
       if (mall != 0u) {  // wave-uniform: some halfway-wall lane of this wave had pulls redirected
         // the redirected values arrived with the pulls (issue_a): f[l] already IS the own cell's opposite population where the bit is set
         const unsigned mm = hw ? M::missing(w) : 0u;
-        hw_apply(f, f, mm, w, __builtin_amdgcn_ballot_w64(kind == M::K_HWM) != 0ull);
+        const bool any_moving = __builtin_amdgcn_ballot_w64(kind == M::K_HWM) != 0ull;
+        bc_arm(mall, [&](auto mc) __attribute__((always_inline)) { hw_apply(mc, f, f, mm, w, any_moving); });
       }
       if (kind != 0u) bc_regs(f, w, fullway);
     }
@@ -473,33 +523,49 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
       mm = (kind == K_HW || kind == M::K_HWM) ? M::missing(w) : 0u;
       mall = wave_or(mm);  // uniform; all lanes of the wave are active here (NB is a whole number of waves)
     }
-    if (mall == 0u) {  // fluid wave (or only fullway / equilibrium lanes): one scalar branch, then straight-line reads
-      // (pointer + immediate form; indexing one array with run-time buffer offsets — lds[ring(l, q) + ...] — compiles to
-      // the same instruction mix but measured 9 % slower on the periodic box: profiles/r02/step2_sweeps.txt)
-      const S* gb[3];  // group g = c_x + 1 comes from plane q0 - c_x
+    // the pull of population l in pointer + immediate form: gb[g], group g = c_x + 1, is the buffer of plane q0 - c_x
+    // (indexing one array with run-time buffer offsets — lds[ring(l, q) + ...] — compiles to the same instruction mix but measured
+    // 9 % slower on the periodic box: profiles/r02/step2_sweeps.txt)
+    auto group_bases = [&](const S*(&gb)[3]) __attribute__((always_inline)) {
       static_for<3>([&](auto gc) {
         constexpr int g = decltype(gc)::value, life = R::glife(g);
         const int qs = q0 - (g - 1);
         gb[g] = lds + (R::gbase(g) + R::template buf<life>(qs) * R::gcount(g)) * NE;
       });
-      static_for<Q>([&](auto lc) {
-        constexpr int l = decltype(lc)::value;
-        constexpr int cy = L::c(1, l), cz = L::c(2, l);
-        f[l] = to_compute<T, S>(gb[R::group(l)][R::gidx(l) * NE + ctr_b - cy * EZ - cz]);
-      });
+    };
+    auto pull_b = [&](auto lc, const S* const(&gb)[3]) __attribute__((always_inline)) -> T {
+      constexpr int l = decltype(lc)::value;
+      constexpr int cy = L::c(1, l), cz = L::c(2, l);
+      return to_compute<T, S>(gb[R::group(l)][R::gidx(l) * NE + ctr_b - cy * EZ - cz]);
+    };
+    if (mall == 0u) {  // fluid wave (or only fullway / equilibrium lanes): one scalar branch, then straight-line reads
+      const S* gb[3];
+      group_bases(gb);
+      static_for<Q>([&](auto lc) { f[decltype(lc)::value] = pull_b(lc, gb); });
     } else {
       // boundary wave: a lane whose missing bit l is set reads its own cell's opposite population instead (select on
-      // the LDS index, no branch), then the halfway-wall terms are applied to exactly those populations
-      T got[Q];
-      static_for<Q>([&](auto lc) {
-        constexpr int l = decltype(lc)::value;
-        constexpr int cx = L::c(0, l), cy = L::c(1, l), cz = L::c(2, l);
-        const int idx_pull = ring(lc, q0 - cx) + ctr_b - cy * EZ - cz;
-        const int idx_own = ring(std::integral_constant<int, opp<L>(l)>{}, q0) + ctr_b;
-        got[l] = to_compute<T, S>(lds[((mm >> l) & 1u) ? idx_own : idx_pull]);
-        f[l] = got[l];
+      // the LDS index, no branch), then the halfway-wall terms are applied to exactly those populations; the populations
+      // outside the arm's set are read as in a fluid wave
+      const bool any_moving = __builtin_amdgcn_ballot_w64(M::kind(w) == M::K_HWM) != 0ull;
+      bc_arm(mall, [&](auto mc) __attribute__((always_inline)) {
+        constexpr unsigned MASK = decltype(mc)::value;
+        const S* gb[3];
+        if constexpr (MASK != ALLQ) group_bases(gb);
+        T got[Q];
+        static_for<Q>([&](auto lc) {
+          constexpr int l = decltype(lc)::value;
+          if constexpr (((MASK >> l) & 1u) != 0u) {
+            constexpr int cx = L::c(0, l), cy = L::c(1, l), cz = L::c(2, l);
+            const int idx_pull = ring(lc, q0 - cx) + ctr_b - cy * EZ - cz;
+            const int idx_own = ring(std::integral_constant<int, opp<L>(l)>{}, q0) + ctr_b;
+            got[l] = to_compute<T, S>(lds[((mm >> l) & 1u) ? idx_own : idx_pull]);
+          } else {
+            got[l] = pull_b(lc, gb);
+          }
+          f[l] = got[l];
+        });
+        hw_apply(mc, f, got, mm, w, any_moving);
       });
-      hw_apply(f, got, mm, w, __builtin_amdgcn_ballot_w64(M::kind(w) == M::K_HWM) != 0ull);
     }
     bool fullway = false;
     if constexpr (HASBC != 0) {
@@ -547,8 +613,6 @@ __device__ __forceinline__ void step2_body(const StepArgs<T, S>& a, S* lds, unsi
   auto flush_strips = [&](int x, int d) __attribute__((always_inline)) {
     if constexpr (SW) {
       if (act_b) return;
-      constexpr unsigned CZP = [] { unsigned m = 0; for (int l = 0; l < Q; ++l) m |= (L::c(2, l) == 1 ? 1u : 0u) << l; return m; }();
-      constexpr unsigned CZM = [] { unsigned m = 0; for (int l = 0; l < Q; ++l) m |= (L::c(2, l) == -1 ? 1u : 0u) << l; return m; }();
       const int tl = t - G::NB, g = tl >> 4, i = tl & 15, r = i >> 1, e = i & 1;
       int yy = ty0 + r;
       yy = yy >= ny ? yy - ny : yy;
