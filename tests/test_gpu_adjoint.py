@@ -160,6 +160,28 @@ def test_native_backward_equals_chained_single_steps():
     assert adjoint.omega_gradient() == d_chained
 
 
+def test_sweep_over_rows_of_two_blocks_the_second_part_empty():
+    """(3, 320) in two dimensions: a row of 320 cells is two blocks of 192 threads (160 rounded up to whole waves), the second holding
+    128 cells, and the three rows make six per-block partial sums of the omega terms per launch"""
+    adjoint, forward, (f_0, f_1, bc_mask, missing_mask), (lat, obcs, bm, mm, f_np) = setup("cavity-halfway", "D2Q9", "FP64FP64", (3, 320))
+    lam_np = np.random.default_rng(3).uniform(-1, 1, f_np.shape).astype(np.float64)
+    states_np, _ = ref.forward_states(f_np, bm, mm, obcs, OMEGA, lat, 2, "FP64FP64")
+    lam_e, terms = ref.backward(states_np, lam_np, bm, mm, obcs, OMEGA, lat, "FP64FP64")
+    exact, bound = omega_bound(terms)
+    states = []
+    for s in states_np:
+        states.append(adjoint.create_cotangent())
+        states[-1].assign(s)
+    a, b = adjoint.create_cotangent(), adjoint.create_cotangent()
+    a.assign(lam_np)
+    adjoint.reset()
+    lam_0, _ = adjoint.backward(states, a, b, bc_mask, missing_mask, OMEGA)
+    assert_same_bits(lam_0.numpy(), lam_e, "lam_0")
+    d_omega = adjoint.omega_gradient()
+    assert abs(d_omega - exact) <= bound, f"dL/domega {d_omega!r} against {exact!r}: off by {abs(d_omega - exact):.3e}, bound {bound:.3e}"
+    assert np.abs(lam_e).max() > 0.1 and exact != 0.0
+
+
 # ---- 9. MacroscopicAdjoint ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("lattice,policy,shape", [("D2Q9", "FP64FP64", (70, 11)), ("D3Q19", "FP32FP32", (4, 5, 261)), ("D3Q27", "FP64FP32", (35, 9, 6))])
 def test_macroscopic_adjoint_matches_the_restatement_bit_for_bit(lattice, policy, shape):

@@ -191,6 +191,11 @@ def test_walled_box_in_two_dimensions():
     run_walled(heated_box, "D2Q9", "BGK", "FP64FP64", (7, 8), steps=5)
 
 
+def test_walled_box_with_rows_of_two_blocks_the_second_part_empty():
+    # a row of 320 cells is two blocks of 192 threads (160 rounded up to whole waves); the second holds 128 cells
+    run_walled(heated_box, "D2Q9", "BGK", "FP64FP64", (3, 320), steps=3)
+
+
 # ---- 3. buoyancy ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("policy", ["FP32FP32", "FP64FP64"])
 def test_buoyant_box_matches_the_restatement(policy):

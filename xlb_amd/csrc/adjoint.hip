@@ -1,23 +1,17 @@
-// libxlbhip: the discrete adjoint of the fused BGK step.  The object owns the boundary tables (built from the same descriptors as a
-// stepper's), the carried-state scratch field of a single adjoint step, the per-block partial sums and the device scalar dL/domega;
+// libxlbhip: the discrete adjoint of the fused BGK step.  The object owns the boundary tables (a BcTables like a stepper's,
+// stepper_tables.hpp), the carried-state scratch field of a single adjoint step, the per-block partial sums and the device scalar dL/domega;
 // a step enqueues its kernels on the context's compute stream, and only omega_gradient waits for the device.
-#include <cmath>
 #include <memory>
-#include <vector>
 
 #include "adjoint_launch.hpp"
-#include "api_internal.hpp"
+#include "stepper_tables.hpp"
 
 using namespace xlb;
 
 struct xlbhip_adjoint {
   xlbhip_ctx* ctx = nullptr;
   int lattice = 0, cdt = 0, sdt = 0;
-  int n_bc = 0;
-  unsigned long long ids_packed = 0;
-  unsigned kinds_packed = 0;
-  DeviceBuf tab_kind;    // uint8 [256]
-  DeviceBuf tab_values;  // [256][27] compute dtype
+  BcTables bc;
   DeviceBuf mu;          // the carried state between the two launches of a single step (store dtype, q planes)
   size_t mu_elems = 0;
   DeviceBuf partial;     // fp64 [blocks], then [chunks of blocks]: the two levels below the device scalar
@@ -60,19 +54,7 @@ static int check_adjoint_fields(const xlbhip_adjoint* s, const xlbhip_field* f_n
     XLB_REQUIRE(f->halo == 0, "adjoint step: fields without ghost planes only (single rank)");
     XLB_REQUIRE(same_grid(f, lin), "the fields of an adjoint step must share one grid");
   }
-  // the kernel's per-thread offsets inside an x plane are 32-bit byte offsets (8-byte elements, 4-byte missing words)
-  XLB_REQUIRE((size_t)lin->ny * lin->nz <= ((size_t)1 << 28), "adjoint step: an x plane of %d x %d cells is too large for the kernel", lin->ny, lin->nz);
-  XLB_REQUIRE(s->lattice != XLBHIP_D2Q9 || lin->nx == 1, "a 2-D grid is stored as one x plane (%d given)", lin->nx);
-  if (s->n_bc > 0) {
-    XLB_REQUIRE(bcm && bcm->dtype == XLBHIP_U8 && bcm->card == 1 && same_grid(bcm, lin) && bcm->halo == 0, "bad or missing bc_mask field");
-    XLB_REQUIRE(miss && miss->dtype == XLBHIP_MISSING && same_grid(miss, lin) && miss->halo == 0, "bad or missing missing_mask field");
-  }
-  return 0;
-}
-
-static int check_omega(double omega) {
-  XLB_REQUIRE(std::isfinite(omega) && omega > 0.0 && omega <= 2.0, "omega %g outside (0, 2]", omega);
-  return 0;
+  return check_single_rank_grid("adjoint step", "kernel", s->lattice, s->bc.n_bc, lin, bcm, miss);
 }
 
 static int ensure_partials(xlbhip_adjoint* s, const xlbhip_field* f) {
@@ -86,7 +68,7 @@ static int ensure_partials(xlbhip_adjoint* s, const xlbhip_field* f) {
 
 // the gather bits for this pair of masks: built on first use and again when either mask was written since
 static int ensure_gather_mask(xlbhip_adjoint* s, const xlbhip_field* bcm, const xlbhip_field* miss) {
-  if (s->n_bc == 0) return 0;
+  if (s->bc.n_bc == 0) return 0;
   const size_t n = bcm->cells();
   if (s->gmask && s->gmask_bc == bcm->data && s->gmask_miss == miss->data && s->gmask_bc_version == bcm->version &&
       s->gmask_miss_version == miss->version && s->gmask_cells == n)
@@ -95,7 +77,7 @@ static int ensure_gather_mask(xlbhip_adjoint* s, const xlbhip_field* bcm, const 
   s->gmask_cells = n;
   const int rc = by_lattice(s->lattice, [&](auto L) {
     hipLaunchKernelGGL((k_adjoint_gather_mask<decltype(L)>), blocks_for(n), 256, 0, s->ctx->stream, static_cast<const uint8_t*>(bcm->data),
-                       static_cast<const uint32_t*>(miss->data), s->tab_kind.get<const uint8_t>(), s->gmask.get<uint32_t>(), dims(bcm));
+                       static_cast<const uint32_t*>(miss->data), s->bc.tab_kind.get<const uint8_t>(), s->gmask.get<uint32_t>(), dims(bcm));
     XLB_HIP(hipGetLastError());
     return 0;
   });
@@ -114,24 +96,11 @@ static int adjoint_launch_once(xlbhip_adjoint* s, const xlbhip_field* f_n, const
   xlbhip_ctx* c = s->ctx;
   AdjointLaunch q = {};
   StepLaunch& p = q.f;
-  p.src = f_n ? f_n->data : nullptr;
-  p.bc = s->n_bc > 0 ? static_cast<const uint8_t*>(bcm->data) : nullptr;
-  p.miss = s->n_bc > 0 ? static_cast<const uint32_t*>(miss->data) : nullptr;
-  p.tab_kind = s->tab_kind.get<uint8_t>();
-  p.tab_values = s->tab_values.get();
-  p.ids_packed = s->ids_packed;
-  p.kinds_packed = s->kinds_packed;
-  p.n_bc = s->n_bc;
+  p = bc_launch(c, s->bc, s->cdt, s->sdt, bcm, miss, grid_of);
+  p.src = f_n ? f_n->data : nullptr;  // (no dst: the launch writes q.out)
   p.plane_stride = f_n ? f_n->plane_stride : 0;
-  p.nx = grid_of->nx;
-  p.ny = grid_of->ny;
-  p.nz = grid_of->nz;
-  p.x_count = grid_of->nx;
   p.omega = omega;
-  p.compute_dtype = s->cdt;
-  p.store_dtype = s->sdt;
-  p.has_bc = s->n_bc > 0 ? 1 : 0;
-  p.stream = c->stream;
+  p.has_bc = s->bc.n_bc > 0 ? 1 : 0;
   q.in = in;
   q.out = out;
   q.in_stride = in_stride;
@@ -173,31 +142,19 @@ int xlbhip_adjoint_create(xlbhip_ctx* c, int lattice, int cdt, int sdt, int n_bc
   XLB_REQUIRE((cdt == XLBHIP_F32 && sdt == XLBHIP_F32) || (cdt == XLBHIP_F64 && (sdt == XLBHIP_F64 || sdt == XLBHIP_F32)),
               "the adjoint step is built for FP32FP32, FP64FP64 and FP64FP32 only (got compute=%d store=%d)", cdt, sdt);
   XLB_REQUIRE(n_bc == 0 || bcs, "null bc list");
-  auto s = std::make_unique<xlbhip_adjoint>();
-  const int q = lattice_q(lattice);
-  std::vector<uint8_t> kind(256, 0);
-  std::vector<double> vals(256 * 27, 0.0);
-  for (int i = 0; i < n_bc; ++i) {
-    const xlbhip_bc_desc& b = bcs[i];
-    XLB_REQUIRE(b.id >= 1 && b.id <= 255, "bc id %d out of range 1..255", b.id);
-    XLB_REQUIRE(kind[b.id] == 0, "bc id %d used twice", b.id);
-    XLB_REQUIRE(b.kind >= XLBHIP_BC_EQUILIBRIUM && b.kind <= XLBHIP_BC_DO_NOTHING,
-                "adjoint step: bc kind %d is not supported (equilibrium, halfway and fullway bounce-back and do-nothing only)", b.kind);
-    kind[b.id] = (uint8_t)b.kind;
-    for (int l = 0; l < q; ++l) vals[b.id * 27 + l] = b.values[l];
-  }
-  for (int i = 0; i < n_bc && i < 8; ++i) {
-    s->ids_packed |= (unsigned long long)(bcs[i].id & 0xff) << (8 * i);
-    s->kinds_packed |= (unsigned)(bcs[i].kind & 0xf) << (4 * i);
-  }
+  BcImage image;
+  const auto refusal = [](int kind) {
+    return bc_adjoint_accepts(kind) ? nullptr
+                                    : "adjoint step: bc kind %d is not supported (equilibrium, halfway and fullway bounce-back and do-nothing only)";
+  };
+  if (int rc = bc_image(lattice, n_bc, bcs, refusal, image)) return rc;
   XLB_HIP(hipSetDevice(c->device));
+  auto s = std::make_unique<xlbhip_adjoint>();
   s->ctx = c;
   s->lattice = lattice;
   s->cdt = cdt;
   s->sdt = sdt;
-  s->n_bc = n_bc;
-  if (int rc = upload_bytes(kind.data(), 256, s->tab_kind)) return rc;
-  if (int rc = upload_values(cdt, vals, s->tab_values)) return rc;
+  if (int rc = s->bc.upload(cdt, image)) return rc;
   XLB_HIP(s->domega.alloc(sizeof(double)));
   XLB_HIP(hipMemset(s->domega.get(), 0, sizeof(double)));
   *out = s.release();
@@ -216,7 +173,7 @@ int xlbhip_adjoint_step(xlbhip_adjoint* s, const xlbhip_field* f_n, const xlbhip
                         const xlbhip_field* missing_mask, double omega) {
   XLB_REQUIRE(f_n, "null argument");
   if (int rc = check_adjoint_fields(s, f_n, lam_in, lam_out, bc_mask, missing_mask)) return rc;
-  if (int rc = check_omega(omega)) return rc;
+  if (int rc = check_relaxation("omega", omega)) return rc;
   XLB_HIP(hipSetDevice(s->ctx->device));
   if (int rc = ensure_partials(s, f_n)) return rc;
   if (int rc = ensure_gather_mask(s, bc_mask, missing_mask)) return rc;
@@ -239,7 +196,7 @@ int xlbhip_adjoint_run(xlbhip_adjoint* s, int64_t n_states, const xlbhip_field* 
     XLB_REQUIRE(states[i] && states[i] != lam_a && states[i] != lam_b, "adjoint run: state %lld is null or one of the cotangent fields", (long long)i);
     if (int rc = check_adjoint_fields(s, states[i], lam_a, lam_b, bc_mask, missing_mask)) return rc;
   }
-  if (int rc = check_omega(omega)) return rc;
+  if (int rc = check_relaxation("omega", omega)) return rc;
   *result_in_b = 0;
   if (n_states == 0) return 0;
   XLB_HIP(hipSetDevice(s->ctx->device));

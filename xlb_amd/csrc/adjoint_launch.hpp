@@ -1,5 +1,5 @@
 // Type-erased launch descriptor of the fused adjoint step and the per-lattice dispatcher that each adjoint_<lattice>.hip
-// instantiates (the scheme of step_launch.hpp).
+// instantiates (the scheme of step_launch.hpp; the forward part's arguments are step_args', the block is launch_shape.hpp's).
 #pragma once
 #include "adjoint_step_kernel.hpp"
 #include "common.hpp"
@@ -17,55 +17,27 @@ struct AdjointLaunch {
   const uint32_t* gmask;  // gather bits (IN_MU with boundary conditions)
 };
 
-// One cell per thread, lanes along z: a row in equal chunks of whole waves, rows stacked to fill the block (launch_typed's shape)
-inline void adjoint_geometry(int nx, int ny, int nz, dim3& block, dim3& grid) {
-  int tz = nz;
-  if (tz > ADJ_BLOCK) {
-    const int chunks = (nz + ADJ_BLOCK - 1) / ADJ_BLOCK;
-    tz = (nz + chunks - 1) / chunks;
-    tz = (tz + 63) / 64 * 64;
-    if (tz > ADJ_BLOCK) tz = ADJ_BLOCK;
-  }
-  int ty = ADJ_BLOCK / tz;
-  if (ty < 1) ty = 1;
-  if (ty > ny) ty = ny;
-  block = dim3(tz, ty, 1);
-  grid = dim3((nz + tz - 1) / tz, (ny + ty - 1) / ty, nx);
-}
+// One cell per thread, lanes along z, blocks of ADJ_BLOCK threads in the row kernels' shape (launch_shape.hpp): the launch and the
+// count of per-block partial sums both come from here
+inline RowBlockShape adjoint_geometry(int nx, int ny, int nz) { return row_block_shape(nz, ny, nx, ADJ_BLOCK, 0); }
 inline size_t adjoint_blocks(int nx, int ny, int nz) {
-  dim3 block, grid;
-  adjoint_geometry(nx, ny, nz, block, grid);
-  return (size_t)grid.x * grid.y * grid.z;
+  const RowBlockShape sh = adjoint_geometry(nx, ny, nz);
+  return (size_t)sh.gx * sh.gy * sh.gz;
 }
 
 template <class L, class T, class S, int IN, int OUT, int HASBC>
 int launch_adjoint_typed(const AdjointLaunch& q) {
   const StepLaunch& p = q.f;
   AdjointArgs<T, S> aa = {};
-  StepArgs<T, S>& a = aa.f;
-  a.src = static_cast<const S*>(p.src);
-  a.bc = p.bc;
-  a.miss = p.miss;
-  a.bc_kind = p.tab_kind;
-  a.bc_values = static_cast<const T*>(p.tab_values);
-  a.ids_packed = p.ids_packed;
-  a.kinds_packed = p.kinds_packed;
-  a.n_bc = p.n_bc;
-  a.plane_stride = p.plane_stride;
-  a.nx = p.nx;
-  a.ny = p.ny;
-  a.nz = p.nz;
-  a.x_count = p.nx;
-  a.nzq = p.nz;
-  a.omega = static_cast<T>(p.omega);
+  aa.f = step_args<T, S>(p, 1);  // (nzq = nz: one cell per thread; no dst: p.dst is null, the kernel writes aa.out)
   aa.in = static_cast<const S*>(q.in);
   aa.out = static_cast<S*>(q.out);
   aa.in_stride = q.in_stride;
   aa.out_stride = q.out_stride;
   aa.partial = q.partial;
   aa.gmask = q.gmask;
-  dim3 block, grid;
-  adjoint_geometry(p.nx, p.ny, p.nz, block, grid);
+  const RowBlockShape sh = adjoint_geometry(p.nx, p.ny, p.nz);
+  const dim3 block(sh.tz, sh.ty, 1), grid(sh.gx, sh.gy, sh.gz);
   XLB_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "grid too large: ny/ty=%u nx=%u", grid.y, grid.z);
   hipLaunchKernelGGL((k_adjoint_step<L, T, S, IN, OUT, HASBC>), grid, block, 0, p.stream, aa);
   XLB_HIP(hipGetLastError());

@@ -1,7 +1,8 @@
-// What api.hip, masker.hip and stepper.hip share and the public header does not show: field helpers, the dispatchers on
-// lattice and compute dtype, and the owners of device / pinned memory.
+// What the library's translation units share and the public header does not show: field helpers, the argument checks more than one
+// stepper makes, the dispatchers on lattice and compute dtype, and the owners of device / pinned memory.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <utility>
 #include <vector>
 
@@ -33,6 +34,27 @@ static unsigned blocks_capped(size_t n, int threads = 256) { return (unsigned)st
 #define XLB_CHECK_POP(f, lattice, what)                                                                     \
   XLB_REQUIRE((f) && is_float((f)->dtype) && (f)->card == lattice_q(lattice), "%s: expected a %d-population float field", \
               what, lattice_q(lattice))
+
+// a relaxation rate, `name` as the caller's argument is called
+static int check_relaxation(const char* name, double omega) {
+  XLB_REQUIRE(std::isfinite(omega) && omega > 0.0 && omega <= 2.0, "%s %g outside (0, 2]", name, omega);
+  return 0;
+}
+
+// What the single-rank steppers (scalar transport, adjoint) ask of the grid `g` of their fields and of the two masks: an x plane the
+// row kernels can address, a 2-D grid as one x plane, and with boundary conditions both masks on that grid without ghost planes.
+// `who` / `kernel`: how the caller's plane-size message names itself and its kernel.
+static int check_single_rank_grid(const char* who, const char* kernel, int lattice, int n_bc, const xlbhip_field* g, const xlbhip_field* bcm,
+                                  const xlbhip_field* miss) {
+  // the kernel's per-thread offsets inside an x plane are 32-bit byte offsets (8-byte elements, 4-byte missing words)
+  XLB_REQUIRE((size_t)g->ny * g->nz <= ((size_t)1 << 28), "%s: an x plane of %d x %d cells is too large for the %s", who, g->ny, g->nz, kernel);
+  XLB_REQUIRE(lattice != XLBHIP_D2Q9 || g->nx == 1, "a 2-D grid is stored as one x plane (%d given)", g->nx);
+  if (n_bc > 0) {
+    XLB_REQUIRE(bcm && bcm->dtype == XLBHIP_U8 && bcm->card == 1 && same_grid(bcm, g) && bcm->halo == 0, "bad or missing bc_mask field");
+    XLB_REQUIRE(miss && miss->dtype == XLBHIP_MISSING && same_grid(miss, g) && miss->halo == 0, "bad or missing missing_mask field");
+  }
+  return 0;
+}
 
 template <class F>
 static int by_lattice(int lattice, F&& f) {

@@ -10,6 +10,7 @@
 #include <hip/hip_fp16.h>
 
 #include "../../include/xlbhip.h"
+#include "bc_kinds.hpp"
 #include "lattice.hpp"
 
 namespace xlb {
@@ -850,15 +851,6 @@ __device__ __forceinline__ int prof_find(const uint32_t* keys, int n, uint32_t k
   }
   return lo;
 }
-
-// ---- kind predicates (host and device) ----
-constexpr bool bc_is_known(int k) { return k >= XLBHIP_BC_EQUILIBRIUM && k <= XLBHIP_BC_HALFWAY_BB_PROFILE; }
-constexpr bool bc_is_zouhe_family(int k) { return k >= XLBHIP_BC_ZOUHE_VELOCITY && k <= XLBHIP_BC_REGULARIZED_PRESSURE; }
-constexpr bool bc_is_hybrid(int k) { return k >= XLBHIP_BC_HYBRID_BB_REGULARIZED && k <= XLBHIP_BC_HYBRID_NEQ_REGULARIZED; }
-constexpr bool bc_is_extended(int k) { return k >= XLBHIP_BC_ZOUHE_VELOCITY; }  // the extended step-kernel variant's: all but the four basic kinds
-constexpr bool bc_reads_missing(int k) { return k == XLBHIP_BC_HALFWAY_BB || bc_is_extended(k); }
-constexpr bool bc_is_edge_kind(int k) { return bc_is_extended(k) || k == XLBHIP_BC_DO_NOTHING; }  // not evaluated by the two-step kernel itself
-constexpr bool bc_has_wall_table(int k) { return bc_is_hybrid(k) || k == XLBHIP_BC_HALFWAY_BB_PROFILE; }  // cells may sit in the sparse tables
 
 // The cell's entry of the profile table (sorted storage cells, 3 values each) into uw[0..2]; nothing without a table
 template <class T>

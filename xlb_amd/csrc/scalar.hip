@@ -1,27 +1,21 @@
-// libxlbhip: scalar transport.  The object owns the boundary tables of the coupled step (the fluid's, built from the same descriptors
-// as a stepper's, and the scalar's rule and value by bc id); a step enqueues the coupled kernel and the fluid's outflow pass on the
+// libxlbhip: scalar transport.  The object owns the boundary tables of the coupled step (the fluid's: a BcTables like a stepper's,
+// stepper_tables.hpp; and the scalar's rule and value by bc id); a step enqueues the coupled kernel and the fluid's outflow pass on the
 // context's compute stream, and nothing here waits for the device.
 #include <cmath>
 #include <memory>
 #include <vector>
 
-#include "api_internal.hpp"
 #include "scalar_launch.hpp"
+#include "stepper_tables.hpp"
 
 using namespace xlb;
 
 struct xlbhip_scalar {
   xlbhip_ctx* ctx = nullptr;
   int lattice = 0, collision = 0, cdt = 0, sdt = 0;
-  int n_bc = 0;
-  bool has_outflow = false;
-  unsigned long long ids_packed = 0;
-  unsigned kinds_packed = 0;
-  DeviceBuf tab_kind;    // uint8 [256]
-  DeviceBuf tab_values;  // [256][27] compute dtype
-  DeviceBuf sc_rule;     // uint8 [256] SCALAR_*
-  DeviceBuf sc_value;    // [256] compute dtype
-  std::vector<uint8_t> kind_host = std::vector<uint8_t>(256, 0);
+  BcTables bc;         // the fluid's
+  DeviceBuf sc_rule;   // uint8 [256] SCALAR_*
+  DeviceBuf sc_value;  // [256] compute dtype
   bool forced = false;
   ScalarCoupling cp{{0, 0, 0}, {0, 0, 0}, 0.0};
   double smag_cs = 0.17;
@@ -49,20 +43,12 @@ static int check_scalar_fields(const xlbhip_scalar* s, const xlbhip_field* fa, c
     XLB_REQUIRE(same_grid(f, fa), "the fields of a scalar-transport step must share one grid");
   }
   XLB_REQUIRE(fa->plane_stride == fb->plane_stride && ga->plane_stride == gb->plane_stride, "f_0 / f_1 or g_0 / g_1 layouts differ");
-  // the kernel's per-thread offsets inside an x plane are 32-bit byte offsets (8-byte elements, 4-byte missing words)
-  XLB_REQUIRE((size_t)fa->ny * fa->nz <= ((size_t)1 << 28), "scalar transport: an x plane of %d x %d cells is too large for the step kernel", fa->ny, fa->nz);
-  XLB_REQUIRE(s->lattice != XLBHIP_D2Q9 || fa->nx == 1, "a 2-D grid is stored as one x plane (%d given)", fa->nx);
-  if (s->n_bc > 0) {
-    XLB_REQUIRE(bcm && bcm->dtype == XLBHIP_U8 && bcm->card == 1 && same_grid(bcm, fa) && bcm->halo == 0, "bad or missing bc_mask field");
-    XLB_REQUIRE(miss && miss->dtype == XLBHIP_MISSING && same_grid(miss, fa) && miss->halo == 0, "bad or missing missing_mask field");
-  }
-  return 0;
+  return check_single_rank_grid("scalar transport", "step kernel", s->lattice, s->bc.n_bc, fa, bcm, miss);
 }
 
 static int check_omegas(double omega, double omega_s) {
-  XLB_REQUIRE(std::isfinite(omega) && omega > 0.0 && omega <= 2.0, "omega %g outside (0, 2]", omega);
-  XLB_REQUIRE(std::isfinite(omega_s) && omega_s > 0.0 && omega_s <= 2.0, "omega_scalar %g outside (0, 2]", omega_s);
-  return 0;
+  if (int rc = check_relaxation("omega", omega)) return rc;
+  return check_relaxation("omega_scalar", omega_s);
 }
 
 // one coupled step (f, g)(t) -> (f, g)(t + 1), then the auxiliary data of the fluid's ExtrapolationOutflowBC cells
@@ -73,30 +59,14 @@ static int scalar_step_once(xlbhip_scalar* s, const xlbhip_field* fs, xlbhip_fie
   touch(gd);
   ScalarLaunch q;
   StepLaunch& p = q.f;
-  p = StepLaunch();
+  p = bc_launch(c, s->bc, s->cdt, s->sdt, bcm, miss, fs);
   p.src = fs->data;
   p.dst = fd->data;
-  p.bc = s->n_bc > 0 ? static_cast<const uint8_t*>(bcm->data) : nullptr;
-  p.miss = s->n_bc > 0 ? static_cast<const uint32_t*>(miss->data) : nullptr;
-  p.tab_kind = s->tab_kind.get<uint8_t>();
-  p.tab_values = s->tab_values.get();
-  p.ids_packed = s->ids_packed;
-  p.kinds_packed = s->kinds_packed;
-  p.n_bc = s->n_bc;
   p.plane_stride = fs->plane_stride;
-  p.nx = fs->nx;
-  p.ny = fs->ny;
-  p.nz = fs->nz;
-  p.halo = 0;
-  p.x_begin = 0;
-  p.x_count = fs->nx;
   p.omega = omega;
   p.smag_cs = s->smag_cs;
-  p.compute_dtype = s->cdt;
-  p.store_dtype = s->sdt;
   p.vec = (int)opt(c, "vec", 0);
-  p.has_bc = s->n_bc > 0 ? 2 : 0;
-  p.stream = c->stream;
+  p.has_bc = s->bc.n_bc > 0 ? 2 : 0;
   q.gsrc = gs->data;
   q.gdst = gd->data;
   q.g_plane_stride = gs->plane_stride;
@@ -112,17 +82,8 @@ static int scalar_step_once(xlbhip_scalar* s, const xlbhip_field* fs, xlbhip_fie
     rc = launch_scalar_d3q19(q, coll);
   else
     rc = launch_scalar_d3q27(q, coll);
-  if (rc || !s->has_outflow) return rc;
-  const size_t n = fd->cells();
-  return by_lattice(s->lattice, [&](auto L) {
-    return by_compute(s->cdt, [&](auto T) {
-      using TT = decltype(T);
-      const BcView<TT> tb = {s->tab_kind.get<uint8_t>(), s->tab_values.get<const TT>(), nullptr, nullptr, 0, nullptr, nullptr, 0};
-      hipLaunchKernelGGL((k_outflow_aux<decltype(L), TT>), blocks_for(n), BC_BLOCK, 0, c->stream, view(fs), view(fd), view(bcm), view(miss), dims(fd), tb);
-      XLB_HIP(hipGetLastError());
-      return 0;
-    });
-  });
+  if (rc) return rc;
+  return outflow_aux(c, s->lattice, s->cdt, s->bc, CellTables(), fs, fd, bcm, miss);
 }
 
 }  // namespace xlb
@@ -137,33 +98,19 @@ int xlbhip_scalar_create(xlbhip_ctx* c, int lattice, int collision, int cdt, int
   XLB_REQUIRE((cdt == XLBHIP_F32 && sdt == XLBHIP_F32) || (cdt == XLBHIP_F64 && (sdt == XLBHIP_F64 || sdt == XLBHIP_F32)),
               "scalar transport is built for FP32FP32, FP64FP64 and FP64FP32 only (got compute=%d store=%d)", cdt, sdt);
   XLB_REQUIRE(n_bc == 0 || bcs, "null bc list");
-  auto s = std::make_unique<xlbhip_scalar>();
-  const int q = lattice_q(lattice);
-  std::vector<double> vals(256 * 27, 0.0);
-  for (int i = 0; i < n_bc; ++i) {
-    const xlbhip_bc_desc& b = bcs[i];
-    XLB_REQUIRE(b.id >= 1 && b.id <= 255, "bc id %d out of range 1..255", b.id);
-    XLB_REQUIRE(s->kind_host[b.id] == 0, "bc id %d used twice", b.id);
-    const bool supported = (b.kind >= XLBHIP_BC_EQUILIBRIUM && b.kind <= XLBHIP_BC_DO_NOTHING) || bc_is_zouhe_family(b.kind) ||
-                           b.kind == XLBHIP_BC_EXTRAPOLATION_OUTFLOW;
-    XLB_REQUIRE(supported, "scalar transport: bc kind %d (HybridBC, profile walls) is not supported by the coupled step", b.kind);
-    if (b.kind == XLBHIP_BC_EXTRAPOLATION_OUTFLOW) s->has_outflow = true;
-    s->kind_host[b.id] = (uint8_t)b.kind;
-    for (int l = 0; l < q; ++l) vals[b.id * 27 + l] = b.values[l];
-  }
-  for (int i = 0; i < n_bc && i < 8; ++i) {
-    s->ids_packed |= (unsigned long long)(bcs[i].id & 0xff) << (8 * i);
-    s->kinds_packed |= (unsigned)(bcs[i].kind & 0xf) << (4 * i);
-  }
+  BcImage image;
+  const auto refusal = [](int kind) {
+    return bc_scalar_accepts(kind) ? nullptr : "scalar transport: bc kind %d (HybridBC, profile walls) is not supported by the coupled step";
+  };
+  if (int rc = bc_image(lattice, n_bc, bcs, refusal, image)) return rc;
   XLB_HIP(hipSetDevice(c->device));
+  auto s = std::make_unique<xlbhip_scalar>();
   s->ctx = c;
   s->lattice = lattice;
   s->collision = collision;
   s->cdt = cdt;
   s->sdt = sdt;
-  s->n_bc = n_bc;
-  if (int rc = upload_bytes(s->kind_host.data(), 256, s->tab_kind)) return rc;
-  if (int rc = upload_values(cdt, vals, s->tab_values)) return rc;
+  if (int rc = s->bc.upload(cdt, image)) return rc;
   if (int rc = upload_rules(s.get(), std::vector<uint8_t>(256, SCALAR_ADIABATIC), std::vector<double>(256, 0.0))) return rc;
   *out = s.release();
   return 0;
@@ -183,9 +130,9 @@ int xlbhip_scalar_set_rules(xlbhip_scalar* s, int n, const int32_t* bc_ids, cons
   std::vector<double> value(256, 0.0);
   for (int i = 0; i < n; ++i) {
     const int id = bc_ids[i];
-    XLB_REQUIRE(id >= 1 && id <= 255 && s->kind_host[id] != 0, "scalar rule for bc id %d, which is none of this stepper's boundary conditions", id);
+    XLB_REQUIRE(id >= 1 && id <= 255 && s->bc.kind_host[id] != 0, "scalar rule for bc id %d, which is none of this stepper's boundary conditions", id);
     XLB_REQUIRE(rules[i] >= SCALAR_ADIABATIC && rules[i] <= SCALAR_DO_NOTHING, "unknown scalar rule %d", rules[i]);
-    XLB_REQUIRE(!(rules[i] == SCALAR_DIRICHLET && s->kind_host[id] == XLBHIP_BC_FULLWAY_BB),
+    XLB_REQUIRE(!(rules[i] == SCALAR_DIRICHLET && s->bc.kind_host[id] == XLBHIP_BC_FULLWAY_BB),
                 "a Dirichlet scalar rule cannot sit on a fullway bounce-back wall (bc id %d): the scalar is bounced fullway there", id);
     XLB_REQUIRE(std::isfinite(values[i]), "scalar rule of bc id %d: value is not finite", id);
     rule[id] = (uint8_t)rules[i];

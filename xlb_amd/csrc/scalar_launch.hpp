@@ -1,5 +1,5 @@
 // Type-erased launch descriptor of the coupled fluid + scalar step and the per-lattice dispatcher that each scalar_<lattice>.hip
-// instantiates (the scheme of step_launch.hpp).
+// instantiates (the scheme of step_launch.hpp; the fluid's arguments are step_args', the block is launch_shape.hpp's).
 #pragma once
 #include "common.hpp"
 #include "scalar_step_kernel.hpp"
@@ -22,25 +22,7 @@ template <class L, class T, class S, int VEC, int COLL, int HASBC>
 int launch_scalar_typed(const ScalarLaunch& q) {
   const StepLaunch& p = q.f;
   ScalarStepArgs<T, S> sa = {};
-  StepArgs<T, S>& a = sa.f;
-  a.src = static_cast<const S*>(p.src);
-  a.dst = static_cast<S*>(p.dst);
-  a.bc = p.bc;
-  a.miss = p.miss;
-  a.bc_kind = p.tab_kind;
-  a.bc_values = static_cast<const T*>(p.tab_values);
-  a.ids_packed = p.ids_packed;
-  a.kinds_packed = p.kinds_packed;
-  a.n_bc = p.n_bc;
-  a.plane_stride = p.plane_stride;
-  a.nx = p.nx;
-  a.ny = p.ny;
-  a.nz = p.nz;
-  a.x_begin = 0;
-  a.x_count = p.nx;
-  a.nzq = p.nz / VEC;
-  a.omega = static_cast<T>(p.omega);
-  a.extra.smag_cs = p.smag_cs;
+  sa.f = step_args<T, S>(p, VEC);
   sa.gsrc = static_cast<const S*>(q.gsrc);
   sa.gdst = static_cast<S*>(q.gdst);
   sa.g_plane_stride = q.g_plane_stride;
@@ -48,20 +30,8 @@ int launch_scalar_typed(const ScalarLaunch& q) {
   sa.sc_value = static_cast<const T*>(q.sc_value);
   sa.cp = q.cp;
   sa.omega_s = static_cast<T>(q.omega_s);
-  // threads along z: a row in equal chunks of whole waves, as launch_typed does
-  const int threads = 256;
-  int tz = a.nzq;
-  if (tz > threads) {
-    const int chunks = (a.nzq + threads - 1) / threads;
-    tz = (a.nzq + chunks - 1) / chunks;
-    tz = (tz + 63) / 64 * 64;
-    if (tz > threads) tz = threads;
-  }
-  int ty = threads / tz;
-  if (ty < 1) ty = 1;
-  if (ty > p.ny) ty = p.ny;
-  dim3 block(tz, ty, 1);
-  dim3 grid((a.nzq + tz - 1) / tz, (p.ny + ty - 1) / ty, p.nx);
+  const RowBlockShape sh = row_block_shape(sa.f.nzq, p.ny, p.nx, 256, 0);
+  const dim3 block(sh.tz, sh.ty, 1), grid(sh.gx, sh.gy, sh.gz);
   XLB_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "grid too large: ny/ty=%u nx=%u", grid.y, grid.z);
   hipLaunchKernelGGL((k_step_scalar<L, T, S, VEC, COLL, HASBC>), grid, block, 0, p.stream, sa);
   XLB_HIP(hipGetLastError());

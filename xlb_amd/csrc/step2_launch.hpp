@@ -1,4 +1,5 @@
-// Launcher of the two-steps-per-pass kernel, shared by its per-lattice translation units (step2_*.hip).
+// Launcher of the two-steps-per-pass kernel, shared by its per-lattice translation units (step2_*.hip); what it shares with the
+// single-step launcher comes from step_launch.hpp's step_args.
 #pragma once
 #include "step2_kernel.hpp"
 #include "step_launch.hpp"
@@ -29,13 +30,11 @@ static int launch2(const Step2Launch& p) {
 template <class L, int HASBC, int TY, int TZ, bool SLAB, bool FAST, class T, int COLL, int STRIPS>
 static int launch2f(const Step2Launch& p) {
   static_assert(HASBC == 0 || (sizeof(T) == 4 && COLL == XLBHIP_BGK), "boundary-condition tables of the two-step kernel are fp32 / BGK");
-  StepArgs<T, float> a;
+  StepArgs<T, float> a = step_args<T, float>(p, 1);
   // SLAB: pointers advanced to interior plane 0 (the kernel addresses the ghost planes with negative indices)
   const size_t ghost = (size_t)p.halo * p.ny * p.nz;
-  a.src = static_cast<const float*>(p.src) + ghost;
-  a.dst = static_cast<float*>(p.dst) + ghost;
-  a.bc = p.bc;
-  a.miss = p.miss;
+  a.src += ghost;
+  a.dst += ghost;
   a.meta = p.meta ? p.meta + ghost : nullptr;
   a.tile_order = p.tile_order;
   a.clean = (HASBC != 0) ? p.clean : nullptr;
@@ -50,28 +49,12 @@ static int launch2f(const Step2Launch& p) {
   a.x_cap = step2_eff_cap(p);
   a.tile_oy = p.tile_oy;
   a.tile_oz = p.tile_oz;
-  a.bc_kind = p.tab_kind;
-  a.bc_values = static_cast<const T*>(p.tab_values);
-  a.prof_keys = nullptr;  // (profile BCs are Zou-He / Regularized: single-step kernel)
+  a.prof_keys = nullptr;  // (profile BCs are Zou-He / Regularized: single-step kernel; no force either: extra.force stays zero)
   a.prof_vals = nullptr;
   a.n_prof = 0;
   a.dist_keys = nullptr;
   a.dist_vals = nullptr;
   a.n_dist = 0;
-  a.ids_packed = p.ids_packed;
-  a.kinds_packed = p.kinds_packed;
-  a.n_bc = p.n_bc;
-  a.plane_stride = p.plane_stride;
-  a.nx = p.nx;
-  a.ny = p.ny;
-  a.nz = p.nz;
-  a.halo = p.halo;
-  a.x_begin = p.x_begin;
-  a.x_count = p.x_count;
-  a.nzq = p.nz;
-  a.omega = static_cast<T>(p.omega);
-  a.extra.force[0] = a.extra.force[1] = a.extra.force[2] = 0.0;
-  a.extra.smag_cs = p.smag_cs;
   const unsigned tiles = (unsigned)(p.ny / TY) * (unsigned)(p.nz / TZ);
   a.xcd_swizzle = step2_eff_swizzle(p, tiles);
   hipLaunchKernelGGL((k_step2<L, T, float, COLL, HASBC, TY, TZ, SLAB, FAST, STRIPS>), dim3(tiles * (unsigned)a.x_segments), dim3(S2Geom<L, HASBC, TY, TZ>::THREADS), 0, p.stream, a);

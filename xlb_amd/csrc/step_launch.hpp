@@ -1,7 +1,9 @@
 // Type-erased launch descriptor + the per-(lattice, collision) dispatcher that each
-// step_*.hip translation unit instantiates.
+// step_*.hip translation unit instantiates.  step_args is the one copy StepLaunch -> StepArgs of every launcher of a StepLaunch (this
+// file's, scalar_launch.hpp, adjoint_launch.hpp, step2_launch.hpp); the block shape of the row kernels is launch_shape.hpp's.
 #pragma once
 #include "common.hpp"
+#include "launch_shape.hpp"
 #include "step_kernel.hpp"
 
 namespace xlb {
@@ -72,21 +74,17 @@ inline int pick_vec(int compute_dtype, int nz, int requested, int collision) {
   return v;
 }
 
-template <class L, class T, class S, int VEC, int COLL, int HASBC, int FLAGS>
-int launch_typed(const StepLaunch& p) {
-  StepArgs<T, S> a;
+// The kernel arguments every launcher of a StepLaunch fills alike (launch_typed, launch_scalar_typed, launch_adjoint_typed, launch2f):
+// everything else starts as zero / nullptr, and each launcher sets what is its own.  vec: cells per thread along z.
+template <class T, class S>
+StepArgs<T, S> step_args(const StepLaunch& p, int vec) {
+  StepArgs<T, S> a = {};
   a.src = static_cast<const S*>(p.src);
   a.dst = static_cast<S*>(p.dst);
   a.bc = p.bc;
   a.miss = p.miss;
   a.bc_kind = p.tab_kind;
   a.bc_values = static_cast<const T*>(p.tab_values);
-  a.prof_keys = p.prof_keys;
-  a.prof_vals = static_cast<const T*>(p.prof_vals);
-  a.n_prof = p.n_prof;
-  a.dist_keys = p.dist_keys;
-  a.dist_vals = p.dist_vals;
-  a.n_dist = p.n_dist;
   a.ids_packed = p.ids_packed;
   a.kinds_packed = p.kinds_packed;
   a.n_bc = p.n_bc;
@@ -97,27 +95,27 @@ int launch_typed(const StepLaunch& p) {
   a.halo = p.halo;
   a.x_begin = p.x_begin;
   a.x_count = p.x_count;
-  a.nzq = p.nz / VEC;
+  a.nzq = p.nz / vec;
   a.omega = static_cast<T>(p.omega);
+  a.extra.smag_cs = p.smag_cs;
+  return a;
+}
+
+template <class L, class T, class S, int VEC, int COLL, int HASBC, int FLAGS>
+int launch_typed(const StepLaunch& p) {
+  StepArgs<T, S> a = step_args<T, S>(p, VEC);
+  a.prof_keys = p.prof_keys;
+  a.prof_vals = static_cast<const T*>(p.prof_vals);
+  a.n_prof = p.n_prof;
+  a.dist_keys = p.dist_keys;
+  a.dist_vals = p.dist_vals;
+  a.n_dist = p.n_dist;
   a.extra.force[0] = p.force[0];
   a.extra.force[1] = p.force[1];
   a.extra.force[2] = p.force[2];
-  a.extra.smag_cs = p.smag_cs;
   const int threads = p.block_threads > 0 ? p.block_threads : 256;
-  // threads along z: split a row into equal chunks of whole waves (nz = 384 -> 2 x 192, not 256 + 128)
-  int tz = a.nzq;
-  if (tz > threads) {
-    const int chunks = (a.nzq + threads - 1) / threads;
-    tz = (a.nzq + chunks - 1) / chunks;
-    tz = (tz + 63) / 64 * 64;
-    if (tz > threads) tz = threads;
-  }
-  if (p.block_tz > 0 && p.block_tz < tz) tz = p.block_tz;
-  int ty = threads / tz;
-  if (ty < 1) ty = 1;
-  if (ty > p.ny) ty = p.ny;
-  dim3 block(tz, ty, 1);
-  dim3 grid((a.nzq + tz - 1) / tz, (p.ny + ty - 1) / ty, p.x_count);
+  const RowBlockShape sh = row_block_shape(a.nzq, p.ny, p.x_count, threads, p.block_tz);
+  const dim3 block(sh.tz, sh.ty, 1), grid(sh.gx, sh.gy, sh.gz);
   XLB_REQUIRE(threads <= (VEC == 1 ? XLB_LB1 : 256), "block_threads %d exceeds the kernel's launch bound", threads);
   a.xcd_swizzle = (p.xcd_swizzle && grid.x > 1 && grid.y % 8 == 0) ? 1 : 0;
   XLB_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "grid too large: ny/ty=%u x_count=%u", grid.y, grid.z);

@@ -1,5 +1,6 @@
-// libxlbhip: the stepper.  Its tables and caches, the launches of one step and of a fused pair of steps, the slab halo protocol,
-// the fuse decision (step2_plan.hpp), and the stepper's C entry points.  The profile tables have their own owner (profile_tables.hpp).
+// libxlbhip: the stepper.  Its caches, the launches of one step and of a fused pair of steps, the slab halo protocol, the fuse
+// decision (step2_plan.hpp), and the stepper's C entry points.  The boundary tables (stepper_tables.hpp: BcTables, parsed by
+// bc_tables.hpp) and the profile tables (profile_tables.hpp) have their own owners.
 #include <array>
 #include <map>
 #include <memory>
@@ -8,7 +9,7 @@
 #include "api_internal.hpp"
 #include "comm.hpp"
 #include "profile_tables.hpp"
-#include "step_launch.hpp"
+#include "stepper_tables.hpp"
 
 using namespace xlb;
 
@@ -25,20 +26,6 @@ struct MetaKey {
   FieldKey bc, miss;
   bool external_halo = false;
   bool operator==(const MetaKey& o) const { return bc == o.bc && miss == o.miss && external_halo == o.external_halo; }
-};
-
-// The boundary conditions of a stepper: their kinds and values by id, and what the kernels look up in their arguments
-struct BcTables {
-  int n_bc = 0;
-  bool needs_missing = false;
-  bool extended_bcs = false;
-  bool has_outflow = false;     // ExtrapolationOutflowBC present: k_outflow_aux runs after every step
-  bool has_edge_kinds = false;  // kinds the two-step kernel does not evaluate itself: Zou-He family, outflow, do-nothing
-  DeviceBuf tab_kind;           // uint8 [256]
-  unsigned long long ids_packed = 0;
-  unsigned kinds_packed = 0;
-  unsigned moving_mask = 0;  // slots (first 8 BCs) whose halfway wall has a non-zero moving-wall term
-  DeviceBuf tab_values;      // [256][27] compute dtype
 };
 
 // What the two-step kernel needs beyond the fields, cached between pairs (rules: the comment block below)
@@ -139,16 +126,9 @@ static int check_step_fields(const xlbhip_stepper* s, const xlbhip_field* a, con
 static StepLaunch make_launch(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
                               double omega, int64_t t) {
   xlbhip_ctx* c = s->ctx;
-  StepLaunch p;
+  StepLaunch p = bc_launch(c, s->bc, s->cdt, s->sdt, bcm, miss, src);
   p.src = src->data;
   p.dst = dst->data;
-  p.bc = (s->bc.n_bc > 0 && bcm) ? static_cast<const uint8_t*>(bcm->data) : nullptr;
-  p.miss = miss ? static_cast<const uint32_t*>(miss->data) : nullptr;
-  p.tab_kind = s->bc.tab_kind.get<uint8_t>();
-  p.ids_packed = s->bc.ids_packed;
-  p.kinds_packed = s->bc.kinds_packed;
-  p.n_bc = s->bc.n_bc;
-  p.tab_values = s->bc.tab_values.get();
   p.prof_keys = s->prof.keys.get<uint32_t>();
   p.prof_vals = s->prof.table_at(t);  // (time-dependent walls: t's slot of the ring, checked resident by the caller)
   p.n_prof = s->prof.n;
@@ -156,17 +136,11 @@ static StepLaunch make_launch(xlbhip_stepper* s, const xlbhip_field* src, xlbhip
   p.dist_vals = s->dist_vals.get<float>();
   p.n_dist = s->n_dist;
   p.plane_stride = src->plane_stride;
-  p.nx = src->nx;
-  p.ny = src->ny;
-  p.nz = src->nz;
-  p.halo = src->halo;
   p.omega = omega;
   p.force[0] = s->force[0];
   p.force[1] = s->force[1];
   p.force[2] = s->force[2];
   p.smag_cs = s->smag_cs;
-  p.compute_dtype = s->cdt;
-  p.store_dtype = s->sdt;
   p.vec = (int)opt(c, "vec", 0);
   p.has_bc = p.bc != nullptr ? (s->bc.extended_bcs ? 2 : 1) : 0;
   p.flags = (opt(c, "nt_store", 1) ? 1 : 0) | (int)(opt(c, "nt_load", 0) << 1);
@@ -174,9 +148,6 @@ static StepLaunch make_launch(xlbhip_stepper* s, const xlbhip_field* src, xlbhip
   p.block_tz = (int)opt(c, "block_tz", 0);
   p.xcd_swizzle = (int)opt(c, "xcd_swizzle", 0);
   p.fast_math = opt(c, "exact_math", 0) ? 0 : 1;
-  p.stream = c->stream;
-  p.x_begin = 0;
-  p.x_count = src->nx;
   return p;
 }
 
@@ -222,30 +193,18 @@ static Step2Launch make_launch2(xlbhip_stepper* s, const Step2Case& pc, const xl
   return p;
 }
 
-// the stepper's boundary tables for the whole-field kernels; prof_vals: the profile table of the timestep in question
-template <class T>
-static BcView<T> bc_view(const xlbhip_stepper* s, const void* prof_vals) {
-  return {s->bc.tab_kind.get<uint8_t>(), s->bc.tab_values.get<const T>(), s->prof.keys.get<uint32_t>(), static_cast<const T*>(prof_vals), s->prof.n,
-          s->dist_keys.get<uint32_t>(),  s->dist_vals.get<float>(),       s->n_dist};
+// the stepper's sparse tables for the whole-field kernels; prof_vals: the profile table of the timestep in question
+static CellTables cell_tables(const xlbhip_stepper* s, const void* prof_vals) {
+  return {s->prof.keys.get<uint32_t>(), prof_vals, s->prof.n, s->dist_keys.get<uint32_t>(), s->dist_vals.get<float>(), s->n_dist};
 }
 
-// assemble_auxiliary_data of the ExtrapolationOutflowBC cells after a step src -> dst (nse_stepper.py:270-272)
+// the outflow pass (stepper_tables.hpp: outflow_aux) after a step src -> dst at timestep t
 static int outflow_aux(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
                        int64_t t) {
   if (!s->bc.has_outflow) return 0;
-  xlbhip_ctx* c = s->ctx;
-  const size_t n = dst->cells();
   const void* pv = s->prof.table_at(t);
   XLB_REQUIRE(s->prof.n == 0 || pv, "outflow pass without its profile table (timestep %lld not staged)", (long long)t);
-  return by_lattice(s->lattice, [&](auto L) {
-    return by_compute(s->cdt, [&](auto T) {
-      using TT = decltype(T);
-      hipLaunchKernelGGL((k_outflow_aux<decltype(L), TT>), blocks_for(n), BC_BLOCK, 0, c->stream, view(src), view(dst), view(bcm), view(miss), dims(dst),
-                         bc_view<TT>(s, pv));
-      XLB_HIP(hipGetLastError());
-      return 0;
-    });
-  });
+  return outflow_aux(s->ctx, s->lattice, s->cdt, s->bc, cell_tables(s, pv), src, dst, bcm, miss);
 }
 
 static int launch_step2(xlbhip_stepper* s, Step2Launch p) {
@@ -546,34 +505,8 @@ int xlbhip_stepper_create(xlbhip_ctx* c, int lattice, int collision, int cdt, in
   XLB_REQUIRE(cdt == XLBHIP_F32 || cdt == XLBHIP_F64, "bad compute dtype %d", cdt);
   XLB_REQUIRE(is_float(sdt) && dtype_size(sdt) <= dtype_size(cdt), "bad store dtype %d for compute dtype %d", sdt, cdt);
   XLB_REQUIRE(n_bc == 0 || bcs, "null bc list");
-  std::vector<uint8_t> kind(256, 0);
-  const int q = lattice_q(lattice);
-  std::vector<double> vals(256 * 27, 0.0);
-  bool needs_missing = false, extended = false, has_outflow = false, has_edge_kinds = false;
-  for (int i = 0; i < n_bc; ++i) {
-    const xlbhip_bc_desc& b = bcs[i];
-    XLB_REQUIRE(b.id >= 1 && b.id <= 255, "bc id %d out of range 1..255", b.id);
-    XLB_REQUIRE(bc_is_known(b.kind), "unknown bc kind %d", b.kind);
-    XLB_REQUIRE(!bc_is_hybrid(b.kind) || lattice_d(lattice) == 3,
-                "This BC is not implemented in 2D!");  // bc_hybrid.py:119-120
-    if (b.kind == XLBHIP_BC_EXTRAPOLATION_OUTFLOW) has_outflow = true;
-    if (bc_is_edge_kind(b.kind)) has_edge_kinds = true;
-    XLB_REQUIRE(kind[b.id] == 0, "bc id %d used twice", b.id);
-    if (bc_is_extended(b.kind)) extended = true;
-    kind[b.id] = (uint8_t)b.kind;
-    for (int l = 0; l < q; ++l) vals[b.id * 27 + l] = b.values[l];
-    if (bc_reads_missing(b.kind)) needs_missing = true;
-  }
-  unsigned long long ids_packed = 0;
-  unsigned kinds_packed = 0;
-  unsigned moving_mask = 0;
-  for (int i = 0; i < n_bc && i < 8; ++i) {
-    ids_packed |= (unsigned long long)(bcs[i].id & 0xff) << (8 * i);
-    kinds_packed |= (unsigned)(bcs[i].kind & 0xf) << (4 * i);
-    if (bcs[i].kind == XLBHIP_BC_HALFWAY_BB)
-      for (int l = 0; l < q; ++l)
-        if (bcs[i].values[l] != 0.0) moving_mask |= 1u << i;
-  }
+  BcImage image;
+  if (int rc = bc_image(lattice, n_bc, bcs, [&](int kind) { return bc_stepper_refusal(lattice_q(lattice), kind); }, image)) return rc;
   XLB_HIP(hipSetDevice(c->device));
   auto s = std::make_unique<xlbhip_stepper>();  // (a failure below releases it and the tables uploaded so far)
   s->ctx = c;
@@ -581,18 +514,9 @@ int xlbhip_stepper_create(xlbhip_ctx* c, int lattice, int collision, int cdt, in
   s->collision = collision;
   s->cdt = cdt;
   s->sdt = sdt;
-  s->bc.n_bc = n_bc;
-  s->bc.needs_missing = needs_missing;
-  s->bc.extended_bcs = extended;
-  s->bc.has_outflow = has_outflow;
-  s->bc.has_edge_kinds = has_edge_kinds;
   s->prof.ctx = c;
   s->prof.cdt = cdt;
-  s->bc.ids_packed = ids_packed;
-  s->bc.kinds_packed = kinds_packed;
-  s->bc.moving_mask = moving_mask;
-  if (int rc = upload_bytes(kind.data(), 256, s->bc.tab_kind)) return rc;
-  if (int rc = upload_values(cdt, vals, s->bc.tab_values)) return rc;
+  if (int rc = s->bc.upload(cdt, image)) return rc;
   *out = s.release();
   return 0;
 }
@@ -620,8 +544,7 @@ int xlbhip_stepper_set_bc_profile_cells(xlbhip_stepper* s, int bc_id, int64_t n,
   XLB_REQUIRE(s && bc_id >= 1 && bc_id <= 255, "bad argument");
   XLB_REQUIRE(n == 0 || storage_cells, "null cell list");
   XLB_HIP(hipSetDevice(s->ctx->device));
-  uint8_t kind = 0;
-  XLB_HIP(hipMemcpy(&kind, s->bc.tab_kind.get<uint8_t>() + bc_id, 1, hipMemcpyDeviceToHost));
+  const uint8_t kind = s->bc.kind_host[bc_id];
   XLB_REQUIRE(bc_has_wall_table(kind),
               "time-dependent wall velocities: bc %d is of kind %d (HybridBC / HalfwayBounceBackBC with a profile)", bc_id, (int)kind);
   if (int rc = s->prof.declare_time_dependent(bc_id, n, storage_cells)) return rc;
@@ -655,9 +578,8 @@ int xlbhip_stepper_momentum_transfer_at(xlbhip_stepper* s, int bc_id, int64_t ti
   XLB_REQUIRE(bcm && bcm->dtype == XLBHIP_U8 && bcm->card == 1 && same_grid(bcm, f_0) && bcm->halo == f_0->halo, "momentum_transfer: bad bc_mask field");
   XLB_REQUIRE(miss && miss->dtype == XLBHIP_MISSING && same_grid(miss, f_0) && miss->halo == f_0->halo, "momentum_transfer: needs the missing_mask field");
   XLB_REQUIRE(f_0->halo == 0, "momentum_transfer through the stepper's tables: fields without ghost planes (mesh / profile BCs live on one rank)");
-  uint8_t kind = 0;
+  const uint8_t kind = s->bc.kind_host[bc_id];
   XLB_HIP(hipSetDevice(c->device));
-  XLB_HIP(hipMemcpy(&kind, s->bc.tab_kind.get<uint8_t>() + bc_id, 1, hipMemcpyDeviceToHost));
   XLB_REQUIRE(bc_has_wall_table(kind),
               "momentum_transfer through the stepper: bc %d is of kind %d (HybridBC / profile walls; plain walls use xlbhip_momentum_transfer)", bc_id,
               (int)kind);
@@ -671,7 +593,7 @@ int xlbhip_stepper_momentum_transfer_at(xlbhip_stepper* s, int bc_id, int64_t ti
     return by_compute(s->cdt, [&](auto T) {
       using TT = decltype(T);
       hipLaunchKernelGGL((k_momentum_transfer_tab<decltype(L), TT>), blocks_for(n), BC_BLOCK, 0, c->stream, view(f_0), view(bcm), view(miss), dims(f_0), bc_id,
-                         bc_view<TT>(s, pv), dforce.get<double>());
+                         bc_view<TT>(s->bc, cell_tables(s, pv)), dforce.get<double>());
       XLB_HIP(hipGetLastError());
       return 0;
     });
