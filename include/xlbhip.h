@@ -38,6 +38,7 @@ typedef struct xlbhip_ibm xlbhip_ibm;
 typedef struct xlbhip_stats xlbhip_stats;
 typedef struct xlbhip_scalar xlbhip_scalar;
 typedef struct xlbhip_adjoint xlbhip_adjoint;
+typedef struct xlbhip_multiphase xlbhip_multiphase;
 
 /* element types of a field; mirrors Precision in xlb/precision_policy.py:13-54 */
 enum {
@@ -546,6 +547,42 @@ int xlbhip_adjoint_reset(xlbhip_adjoint* a);
  * applied to (dL/drho, dL/du); rho_bar (cardinality 1) or u_bar (cardinality d) may be NULL for zero */
 int xlbhip_macroscopic_adjoint(xlbhip_ctx* ctx, int lattice, int compute_dtype, const xlbhip_field* f, const xlbhip_field* rho_bar, const xlbhip_field* u_bar,
                                xlbhip_field* lam);
+
+/* ---- Shan-Chen pseudopotential flow (single component, liquid-vapour) ----------------------------------------------------------
+ * (no counterpart in the reference; the interaction force is Shan and Chen's, Phys. Rev. E 47, 1815 (1993), applied through the
+ * exact-difference forcing the reference has for a constant force, xlb/operator/force/exact_difference_force.py; the Carnahan-Starling
+ * pseudopotential follows Yuan and Schaefer, Phys. Fluids 18, 042101 (2006); pinned by the NumPy restatement tests/_multiphase_ref.py)
+ * One step on the post-streaming populations (pull, then the streaming-step boundary rules): rho, u = moments; psi = Psi(rho);
+ * F_a = (-G psi(x)) sum_{i >= 1} (w_i psi(x + c_i)) c_ai with the fluid lattice's weights; the cell collides by BGK with the
+ * exact-difference acceleration force_a + F_a / rho.  A neighbour behind a missing direction (bit opp(i) of the cell's missing mask)
+ * counts with the wall value Psi(rho_w) of the cell's own bc id; fullway bounce-back cells and solid cells (bc id 255) carry their
+ * Psi(rho_w) as psi and feel no force.  The bulk pressure is cs^2 rho + (G cs^2 / 2) psi^2, cs^2 = 1/3.  Two launches per step (psi, then
+ * the step that reads the neighbours' psi); the psi field is the object's.  Fields without ghost planes, FP32FP32 / FP64FP64 /
+ * FP64FP32.  bcs: as for xlbhip_stepper_create, kinds 2 and 3 only (halfway bounce-back with a constant wall velocity or none, fullway
+ * bounce-back). */
+int xlbhip_multiphase_create(xlbhip_ctx* ctx, int lattice, int compute_dtype, int store_dtype, int n_bc, const xlbhip_bc_desc* bcs, xlbhip_multiphase** out);
+int xlbhip_multiphase_destroy(xlbhip_multiphase* m);
+/* form 0: psi = rho0 (1 - exp(-rho / rho0)), params = {rho0};  1: psi = rho, no params;  2: Carnahan-Starling, params = {T, a, b, R}:
+ * p = rho R T (1 + eta + eta^2 - eta^3) / (1 - eta)^3 - a rho^2, eta = b rho / 4, psi = sqrt(2 (p - cs^2 rho) / (G cs^2)), g must be -1.
+ * force: 3 doubles (internal 3-component form) or NULL, the constant acceleration added to F / rho */
+int xlbhip_multiphase_set_model(xlbhip_multiphase* m, int form, double g, int n_params, const double* params, const double* force);
+/* The wall densities: rho_w[i] for bc id bc_ids[i] (one of this object's BCs, or 255 for solid cells), with psi_w[i] = Psi(rho_w[i]) as
+ * the caller evaluates its model in the compute dtype: these bits go into the table, so that a host restatement shares them.  Every
+ * other id has Psi = 0 (a wall that neither attracts nor repels beyond the missing neighbour).  Replaces all values set before. */
+int xlbhip_multiphase_set_wall_density(xlbhip_multiphase* m, int n, const int32_t* bc_ids, const double* rho_w, const double* psi_w);
+/* one step f(t) -> f(t + 1); omega in (0, 2] */
+int xlbhip_multiphase_step(xlbhip_multiphase* m, const xlbhip_field* f_src, xlbhip_field* f_dst, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask,
+                           double omega, int64_t timestep);
+/* n_steps x (step, swap) enqueued without a host wait; *result_in_b: the result is in f_b */
+int xlbhip_multiphase_run(xlbhip_multiphase* m, xlbhip_field* f_a, xlbhip_field* f_b, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, double omega,
+                          int64_t first_timestep, int64_t n_steps, int* result_in_b);
+/* Outputs of the post-streaming state of the stored field f, in the compute dtype: psi (cardinality 1); the interaction force F without
+ * the force vector (cardinality d; zero at wall cells); rho (cardinality 1) and the physical velocity u = u_bare + F / (2 rho)
+ * (cardinality d) */
+int xlbhip_multiphase_psi(xlbhip_multiphase* m, const xlbhip_field* f, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, xlbhip_field* psi);
+int xlbhip_multiphase_force(xlbhip_multiphase* m, const xlbhip_field* f, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, xlbhip_field* force);
+int xlbhip_multiphase_macroscopic(xlbhip_multiphase* m, const xlbhip_field* f, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, xlbhip_field* rho,
+                                  xlbhip_field* u);
 
 #ifdef __cplusplus
 }

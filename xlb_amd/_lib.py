@@ -147,6 +147,15 @@ SIGNATURES = {
     "xlbhip_adjoint_omega_gradient": [_p, C.POINTER(_d)],
     "xlbhip_adjoint_reset": [_p],
     "xlbhip_macroscopic_adjoint": [_p, _i, _i, _p, _p, _p, _p],
+    "xlbhip_multiphase_create": [_p, _i, _i, _i, _i, C.POINTER(BcDesc), _pp],
+    "xlbhip_multiphase_destroy": [_p],
+    "xlbhip_multiphase_set_model": [_p, _i, _d, _i, _p, _p],
+    "xlbhip_multiphase_set_wall_density": [_p, _i, _p, _p, _p],
+    "xlbhip_multiphase_step": [_p, _p, _p, _p, _p, _d, _i64],
+    "xlbhip_multiphase_run": [_p, _p, _p, _p, _p, _d, _i64, _i64, C.POINTER(C.c_int)],
+    "xlbhip_multiphase_psi": [_p, _p, _p, _p, _p],
+    "xlbhip_multiphase_force": [_p, _p, _p, _p, _p],
+    "xlbhip_multiphase_macroscopic": [_p, _p, _p, _p, _p, _p],
 }
 
 _lib = None
@@ -875,6 +884,61 @@ class Adjoint:
     def free(self):
         if self._h:
             load().xlbhip_adjoint_destroy(self._h)
+            self._h = _p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Multiphase:
+    """Native Shan-Chen object (xlbhip_multiphase_create): the boundary tables, the wall pseudopotentials and the psi field of the step."""
+
+    EXPONENTIAL, DENSITY, CARNAHAN_STARLING = 0, 1, 2  # PSI_* of csrc/multiphase_kernels.hpp
+
+    def __init__(self, ctx, lattice_id, compute_code, store_code, bc_descs):
+        self.ctx = ctx
+        n = len(bc_descs)
+        arr = (BcDesc * max(n, 1))(*bc_descs)
+        self._h = _p()
+        check(load().xlbhip_multiphase_create(ctx.handle, lattice_id, compute_code, store_code, n, arr, C.byref(self._h)))
+
+    def set_model(self, form, g, params, force3):
+        p = np.ascontiguousarray(params, dtype=np.float64)
+        f = None if force3 is None else np.ascontiguousarray(force3, dtype=np.float64)
+        check(load().xlbhip_multiphase_set_model(self._h, int(form), float(g), len(p), p.ctypes.data if len(p) else None, None if f is None else f.ctypes.data))
+
+    def set_wall_density(self, walls):
+        """walls: [(bc id, rho_w, Psi(rho_w) in the compute dtype)]"""
+        ids = np.array([w[0] for w in walls], dtype=np.int32)
+        rho = np.array([w[1] for w in walls], dtype=np.float64)
+        psi = np.array([w[2] for w in walls], dtype=np.float64)
+        check(load().xlbhip_multiphase_set_wall_density(self._h, len(walls), ids.ctypes.data, rho.ctypes.data, psi.ctypes.data))
+
+    def step(self, f_src, f_dst, bc_mask, missing_mask, omega, timestep):
+        check(load().xlbhip_multiphase_step(self._h, _hf(f_src), _hf(f_dst), _h(bc_mask), _h(missing_mask), float(omega), int(timestep)))
+
+    def run(self, f_a, f_b, bc_mask, missing_mask, omega, first_timestep, n_steps):
+        """n steps; returns True when the result is in f_b."""
+        where = C.c_int()
+        check(load().xlbhip_multiphase_run(self._h, _hf(f_a), _hf(f_b), _h(bc_mask), _h(missing_mask), float(omega), int(first_timestep), int(n_steps),
+                                           C.byref(where)))
+        return bool(where.value)
+
+    def psi(self, f, bc_mask, missing_mask, out):
+        check(load().xlbhip_multiphase_psi(self._h, _hf(f), _h(bc_mask), _h(missing_mask), _hf(out)))
+
+    def force(self, f, bc_mask, missing_mask, out):
+        check(load().xlbhip_multiphase_force(self._h, _hf(f), _h(bc_mask), _h(missing_mask), _hf(out)))
+
+    def macroscopic(self, f, bc_mask, missing_mask, rho, u):
+        check(load().xlbhip_multiphase_macroscopic(self._h, _hf(f), _h(bc_mask), _h(missing_mask), _hf(rho), _hf(u)))
+
+    def free(self):
+        if self._h:
+            load().xlbhip_multiphase_destroy(self._h)
             self._h = _p()
 
     def __del__(self):

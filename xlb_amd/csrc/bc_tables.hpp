@@ -41,6 +41,9 @@ constexpr bool bc_is_basic(int k) { return k >= XLBHIP_BC_EQUILIBRIUM && k <= XL
 constexpr bool bc_scalar_accepts(int k) { return bc_is_basic(k) || bc_is_zouhe_family(k) || k == XLBHIP_BC_EXTRAPOLATION_OUTFLOW; }
 // the adjoint step: equilibrium, halfway and fullway bounce-back and do-nothing
 constexpr bool bc_adjoint_accepts(int k) { return bc_is_basic(k); }
+// the Shan-Chen step: walls only, halfway (constant wall velocity or none) and fullway bounce-back — the missing directions of every
+// other kind have no agreed neighbour pseudopotential
+constexpr bool bc_multiphase_accepts(int k) { return k == XLBHIP_BC_HALFWAY_BB || k == XLBHIP_BC_FULLWAY_BB; }
 
 // The image of `bcs` for a lattice of q populations.  refusal(kind): nullptr for a kind the caller takes, else the format of its message
 // (one %d, the kind).  Returns the error text; empty: `out` is complete.

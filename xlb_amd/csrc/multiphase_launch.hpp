@@ -1,0 +1,73 @@
+// Type-erased launch descriptor of the Shan-Chen step's kernels and the per-lattice dispatcher that each multiphase_<lattice>.hip
+// instantiates (the scheme of scalar_launch.hpp; the fluid's arguments are step_args', the block is launch_shape.hpp's).  One cell per
+// thread: there are no `vec` variants.
+#pragma once
+#include "common.hpp"
+#include "multiphase_step_kernel.hpp"
+#include "step_launch.hpp"
+
+namespace xlb {
+
+enum class MultiphaseKernel : int { psi = 0, step = 1, out = 2 };
+
+struct MultiphaseLaunch {
+  StepLaunch f;  // the fluid's part (f.halo == 0, all of x); f.dst only for MultiphaseKernel::step
+  void* psi;
+  const void* psi_wall;  // compute dtype [256]
+  int form;              // PSI_*
+  double g;
+  double par[4];
+  double force[3];
+  void *out_rho, *out_u, *out_force;  // MultiphaseKernel::out, compute dtype, each may be nullptr
+  size_t u_stride, force_stride;
+};
+
+template <class L, class T, class S, int HASBC>
+int launch_multiphase_typed(const MultiphaseLaunch& q, MultiphaseKernel which) {
+  const StepLaunch& p = q.f;
+  MultiphaseArgs<T, S> ma = {};
+  ma.f = step_args<T, S>(p, 1);
+  ma.psi = static_cast<T*>(q.psi);
+  ma.psi_wall = static_cast<const T*>(q.psi_wall);
+  ma.model.form = q.form;
+  ma.model.neg_g = static_cast<T>(-q.g);
+  for (int k = 0; k < 4; ++k) ma.model.par[k] = static_cast<T>(q.par[k]);
+  for (int k = 0; k < 3; ++k) ma.model.force[k] = static_cast<T>(q.force[k]);
+  ma.out_rho = static_cast<T*>(q.out_rho);
+  ma.out_u = static_cast<T*>(q.out_u);
+  ma.out_force = static_cast<T*>(q.out_force);
+  ma.u_stride = q.u_stride;
+  ma.force_stride = q.force_stride;
+  const RowBlockShape sh = row_block_shape(p.nz, p.ny, p.nx, 256, 0);
+  const dim3 block(sh.tz, sh.ty, 1), grid(sh.gx, sh.gy, sh.gz);
+  XLB_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "grid too large: ny/ty=%u nx=%u", grid.y, grid.z);
+  if (which == MultiphaseKernel::psi)
+    hipLaunchKernelGGL((k_psi<L, T, S, HASBC>), grid, block, 0, p.stream, ma);
+  else if (which == MultiphaseKernel::step)
+    hipLaunchKernelGGL((k_step_multiphase<L, T, S, HASBC>), grid, block, 0, p.stream, ma);
+  else
+    hipLaunchKernelGGL((k_multiphase_out<L, T, S, HASBC>), grid, block, 0, p.stream, ma);
+  XLB_HIP(hipGetLastError());
+  return 0;
+}
+
+template <class L, class T, class S>
+int launch_multiphase_policy(const MultiphaseLaunch& q, MultiphaseKernel which) {
+  return q.f.has_bc ? launch_multiphase_typed<L, T, S, 1>(q, which) : launch_multiphase_typed<L, T, S, 0>(q, which);
+}
+
+template <class L>
+int launch_multiphase_lattice(const MultiphaseLaunch& q, MultiphaseKernel which) {
+  const int c = q.f.compute_dtype, s = q.f.store_dtype;
+  if (c == XLBHIP_F32 && s == XLBHIP_F32) return launch_multiphase_policy<L, float, float>(q, which);
+  if (c == XLBHIP_F64 && s == XLBHIP_F64) return launch_multiphase_policy<L, double, double>(q, which);
+  if (c == XLBHIP_F64 && s == XLBHIP_F32) return launch_multiphase_policy<L, double, float>(q, which);
+  XLB_FAIL("the multiphase step is built for FP32FP32, FP64FP64 and FP64FP32 only (got compute=%d store=%d)", c, s);
+}
+
+// defined one per translation unit (multiphase_<lattice>.hip)
+int launch_multiphase_d2q9(const MultiphaseLaunch& q, MultiphaseKernel which);
+int launch_multiphase_d3q19(const MultiphaseLaunch& q, MultiphaseKernel which);
+int launch_multiphase_d3q27(const MultiphaseLaunch& q, MultiphaseKernel which);
+
+}  // namespace xlb

@@ -1,8 +1,14 @@
 """Steppers of the HIP backend: the fused incompressible Navier-Stokes step, the same with an immersed boundary, the same
-with a transported scalar, and the discrete adjoint of the plain BGK step."""
+with a transported scalar, the discrete adjoint of the plain BGK step, and the Shan-Chen liquid-vapour step."""
 
 from .stepper import Stepper as Stepper
 from .nse_stepper import IncompressibleNavierStokesStepper as IncompressibleNavierStokesStepper
 from .ibm_stepper import IBMStepper as IBMStepper, IBMBody as IBMBody, RigidMotion as RigidMotion, RigidDynamics as RigidDynamics
 from .scalar_stepper import ScalarTransportStepper as ScalarTransportStepper
 from .adjoint_stepper import AdjointStepper as AdjointStepper
+from .multiphase_stepper import (
+    MultiphaseStepper as MultiphaseStepper,
+    ShanChenExponential as ShanChenExponential,
+    ShanChenDensity as ShanChenDensity,
+    CarnahanStarling as CarnahanStarling,
+)
