@@ -308,6 +308,18 @@ int xlbhip_step2_eligible(xlbhip_stepper* s, const xlbhip_field* f_src, xlbhip_f
                           const xlbhip_field* missing_mask);
 int xlbhip_step2(xlbhip_stepper* s, const xlbhip_field* f_src, xlbhip_field* f_dst, const xlbhip_field* bc_mask,
                  const xlbhip_field* missing_mask, double omega, int64_t timestep);
+/* Read-only report of the two-step launches the next pass f_src -> f_dst would make (same arguments as xlbhip_step2_eligible, which
+ * must say 1).  Nothing is stepped and no field changes; the meta words, the tile order and the clean flags are built through the
+ * caches a pass uses, so the report is what the next xlbhip_run / xlbhip_step2 on these fields and options launches.  Covers fields
+ * without ghost planes, the slab launches of fields with two (interior + two edges, or whole) and the middle launch of the
+ * inlet / outlet path (the end planes' single steps are not listed).  int32 words: [0] = launches; per launch x_begin, x_count,
+ * effective x segments, effective cap (planes of the thin end segments, 0 = uniform cuts), tile_ty, tile_tz, tile_oy, tile_oz (the
+ * tiling's shift), strips mode (0 none, 2 write, 3 read + write, 4 row-aligned lanes only; as if the strip buffers can be allocated),
+ * items; then per item, in block order: tile index (ty * tiles_z + tz), x_lo, x_hi (planes [x_lo, x_hi)) and the clean flag the block
+ * reads (1 = it runs the body without boundary conditions; 0 also where the launch has no flags).  *n_words = words of the report;
+ * they are written to out when capacity >= *n_words (call with capacity 0 to size the buffer). */
+int xlbhip_step2_plan(xlbhip_stepper* s, const xlbhip_field* f_src, xlbhip_field* f_dst, const xlbhip_field* bc_mask,
+                      const xlbhip_field* missing_mask, int32_t* out, int64_t capacity, int64_t* n_words);
 /* as xlbhip_run without the placement contract: every pair of steps may be fused (xlbhip_run keeps an even number of fused
  * passes and finishes with single steps to honour its contract); *result_in_b = 1 when the result is in f_b */
 int xlbhip_run_any(xlbhip_stepper* s, xlbhip_field* f_a, xlbhip_field* f_b, const xlbhip_field* bc_mask,

@@ -105,6 +105,7 @@ SIGNATURES = {
     "xlbhip_halo_exchange": [_p, _i, _p],
     "xlbhip_halo_exchange_wide": [_p, _i, _p],
     "xlbhip_step2_eligible": [_p, _p, _p, _p, _p],
+    "xlbhip_step2_plan": [_p, _p, _p, _p, _p, _p, _i64, C.POINTER(_i64)],
     "xlbhip_step2": [_p, _p, _p, _p, _p, _d, _i64],
     "xlbhip_ibm_create": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _d, _pp],
     "xlbhip_ibm_destroy": [_p],
@@ -625,6 +626,25 @@ class Stepper:
 
     def step2_eligible(self, f_src, f_dst, bc_mask, missing_mask):
         return bool(load().xlbhip_step2_eligible(self._h, f_src.handle, f_dst.handle, _h(bc_mask), _h(missing_mask)))
+
+    def step2_plan(self, f_src, f_dst, bc_mask, missing_mask):
+        """The two-step launches the next pass f_src -> f_dst would make (xlbhip_step2_plan; nothing is stepped): a list of dicts
+        with x_begin, x_count, segments, cap, tile (ty, tz), shift (oy, oz), strips and items, an (n, 4) int32 array of
+        (tile index, x_lo, x_hi, clean flag) per block."""
+        args = (self._h, f_src.handle, f_dst.handle, _h(bc_mask), _h(missing_mask))
+        n = _i64()
+        check(load().xlbhip_step2_plan(*args, None, 0, C.byref(n)))
+        words = np.zeros(n.value, dtype=np.int32)
+        check(load().xlbhip_step2_plan(*args, words.ctypes.data, n.value, C.byref(n)))
+        assert n.value == words.size
+        launches, o = [], 1
+        for _ in range(int(words[0])):
+            h = [int(v) for v in words[o : o + 10]]
+            items = words[o + 10 : o + 10 + 4 * h[9]].reshape(h[9], 4).copy()
+            launches.append(dict(x_begin=h[0], x_count=h[1], segments=h[2], cap=h[3], tile=(h[4], h[5]), shift=(h[6], h[7]), strips=h[8], items=items))
+            o += 10 + 4 * h[9]
+        assert o == words.size
+        return launches
 
     def step2(self, f_src, f_dst, bc_mask, missing_mask, omega, timestep):
         """Two steps in one pass: f(t) in f_src -> f(t+2) in f_dst."""

@@ -198,6 +198,7 @@ int launch_step2_d3q27_bgk(const Step2Launch& p);
 int launch_step2_d3q27_kbc(const Step2Launch& p);
 int step2_build_clean(const Step2Launch& p, uint8_t* out);
 int step2_items(const Step2Launch& p);
+int step2_report_items(const Step2Launch& p, int32_t* out, int* eff_segments, int* eff_cap);  // out: device memory, 3 words per item
 int launch_step_d2q9_ext(const StepLaunch& p, int coll);
 int launch_step_d3q19_ext(const StepLaunch& p, int coll);
 int launch_step_d3q27_ext(const StepLaunch& p, int coll);

@@ -207,8 +207,35 @@ static int outflow_aux(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field*
   return outflow_aux(s->ctx, s->lattice, s->cdt, s->bc, cell_tables(s, pv), src, dst, bcm, miss);
 }
 
-static int launch_step2(xlbhip_stepper* s, Step2Launch p) {
-  if (s->lattice == XLBHIP_D3Q27 && s->collision == XLBHIP_KBC) return launch_step2_d3q27_kbc(p);
+// The plan report (xlbhip_step2_plan): step_twice run with a Step2Report takes every decision of a pass and builds the cached tables
+// a pass builds, but each two-step launch is written down here instead of being enqueued, and nothing else is launched or touched.
+// Words: [0] = launches; per launch x_begin, x_count, effective segments, effective cap, tile_ty, tile_tz, tile_oy, tile_oz,
+// strips mode, items, then per item (= block) tile, x_lo, x_hi, clean flag as the kernel reads it (0 where the launch has no flags).
+struct Step2Report {
+  std::vector<int32_t> words = std::vector<int32_t>(1, 0);
+};
+
+static int report_step2(const Step2Launch& p, Step2Report& rep) {
+  const int items = step2_items(p);
+  DeviceBuf d_items;
+  XLB_HIP(d_items.alloc((size_t)items * 3 * sizeof(int32_t)));
+  int segments = 0, cap = 0;  // the effective ones, from the launcher's own rules (step2_launch.hpp)
+  if (int rc = step2_report_items(p, d_items.get<int32_t>(), &segments, &cap)) return rc;
+  std::vector<int32_t> host((size_t)items * 3);
+  std::vector<uint8_t> flags((size_t)items, 0);
+  XLB_HIP(hipMemcpyAsync(host.data(), d_items.get(), host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, p.stream));
+  if (p.clean) XLB_HIP(hipMemcpyAsync(flags.data(), p.clean, flags.size(), hipMemcpyDeviceToHost, p.stream));
+  XLB_HIP(hipStreamSynchronize(p.stream));
+  for (int v : {p.x_begin, p.x_count, segments, cap, p.tile_ty, p.tile_tz, p.tile_oy, p.tile_oz, (int)p.strips, items})
+    rep.words.push_back(v);
+  for (int i = 0; i < items; ++i)
+    for (int v : {host[3 * i], host[3 * i + 1], host[3 * i + 2], (int)flags[i]}) rep.words.push_back(v);
+  rep.words[0] += 1;
+  return 0;
+}
+
+static int launch_step2(xlbhip_stepper* s, Step2Launch p, Step2Report* rep = nullptr) {
+  if (s->lattice == XLBHIP_D3Q27 && s->collision == XLBHIP_KBC) return rep ? report_step2(p, *rep) : launch_step2_d3q27_kbc(p);
   p.clean = nullptr;
   if (p.has_bc && p.meta && opt(s->ctx, "fuse2_clean", 1)) {
     // what the block -> (tile, x-segment) mapping depends on and may differ between the launches of one stepper (tile, shift and
@@ -223,6 +250,7 @@ static int launch_step2(xlbhip_stepper* s, Step2Launch p) {
     }
     p.clean = it->second.get<uint8_t>();
   }
+  if (rep) return report_step2(p, *rep);
   if (s->lattice == XLBHIP_D3Q27) return launch_step2_d3q27_bgk(p);
   return p.strips != Strips::none ? launch_step2_d3q19_bgk_strips(p) : launch_step2_d3q19_bgk(p);
 }
@@ -247,12 +275,13 @@ static bool ensure_strips(xlbhip_field* f) {
 // single-step kernel twice with a third population field holding their f(t+1).  The first of those launches reads the
 // profile table of timestep t, the second that of t + 1 (time-dependent walls on the end planes).
 static int step_twice_edge_ext(xlbhip_stepper* s, const Step2Case& pc, Step2Launch p, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm,
-                               const xlbhip_field* miss, double omega, int64_t t) {
+                               const xlbhip_field* miss, double omega, int64_t t, Step2Report* rep) {
   XLB_REQUIRE(s->pairs.scratch && s->pairs.scratch->plane_stride == src->plane_stride, "scratch field missing (can_fuse2 allocates it)");
   const int nx = src->nx;
   p.x_begin = 2;
   p.x_count = nx - 4;
   p.x_segments = fuse2_segments(s, pc, p.x_count);
+  if (rep) return report_step2(p, *rep);
   if (int rc = launch_step2_d3q19_bgk(p)) return rc;  // (directly: no clean flags, no strips)
   // end planes, step 1: f(t+1) on the planes nx-3 .. nx-1 and 0 .. 2 -> scratch
   StepLaunch q = make_launch(s, src, s->pairs.scratch, bcm, miss, omega, t);
@@ -327,13 +356,14 @@ struct Fuse2 {
 };
 
 // two steps in one pass (a -> scratch-free: src -> dst holds f(t+2)); `how`: the caller's can_fuse2 of these fields (how.fuse)
+// rep: write the pass's two-step launches down instead of running it (Step2Report)
 static int step_twice(xlbhip_stepper* s, Fuse2 how, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm,
-                      const xlbhip_field* miss, double omega, int64_t t) {
+                      const xlbhip_field* miss, double omega, int64_t t, Step2Report* rep = nullptr) {
   const Step2Case pc = plan_case(s, src, s->bc.n_bc > 0 && bcm, how.edge_ext);
   Step2Launch p = make_launch2(s, pc, src, dst, bcm, miss, omega, t);
   xlbhip_ctx* c = s->ctx;
-  touch(dst);  // (new contents: whatever was cached on the old ones — its strip buffer — is stale)
-  if (how.edge_ext) return step_twice_edge_ext(s, pc, p, src, dst, bcm, miss, omega, t);
+  if (!rep) touch(dst);  // (new contents: whatever was cached on the old ones — its strip buffer — is stale)
+  if (how.edge_ext) return step_twice_edge_ext(s, pc, p, src, dst, bcm, miss, omega, t, rep);
   // strip buffers (step2_kernel.hpp): phase A's halo columns come from src's strips, phase B writes dst's.  D3Q19, the
   // bit-exact body, (8 x 64) tiles; a field whose strips are not those of its current contents gets them rebuilt first.
   xlbhip_field* srcw = const_cast<xlbhip_field*>(src);
@@ -343,12 +373,12 @@ static int step_twice(xlbhip_stepper* s, Fuse2 how, const xlbhip_field* src, xlb
   // fuse2_strips = 2 forces them for every D3Q19 stepper.
   const int64_t strips_opt = opt(c, "fuse2_strips", 1);
   const bool strips = (strips_opt == 2 || (strips_opt == 1 && p.has_bc)) && s->lattice == XLBHIP_D3Q19 && !p.fast_bgk && p.tile_ty == 8 && p.tile_tz == 64 &&
-                      (src->halo == 0 || native_slab) && src->nx >= 8 && ensure_strips(srcw) && ensure_strips(dst);
+                      (src->halo == 0 || native_slab) && src->nx >= 8 && (rep || (ensure_strips(srcw) && ensure_strips(dst)));  // (a report allocates none)
   // q writes dst's strips, and reads src's when they are those of src's current contents (all interior planes).  After anything but
   // a strip-writing pass wrote src — a single step, an upload — the first pass only WRITES strips (no separate rebuild pass: at 512^3
   // that would cost 1.5 ms, a third of a pair, inside e.g. the driver's 20-step timed region after its 5 warm-up steps).
   auto read_strips = [&](Step2Launch& q) {
-    const bool valid = srcw->strips_version == srcw->version && srcw->strips_oz == q.tile_oz;
+    const bool valid = srcw->strips && srcw->strips_version == srcw->version && srcw->strips_oz == q.tile_oz;
     q.strips = valid ? Strips::read_write : Strips::write;
     q.strips_src = valid ? srcw->strips : nullptr;
     q.strips_dst = dst->strips;
@@ -361,8 +391,8 @@ static int step_twice(xlbhip_stepper* s, Fuse2 how, const xlbhip_field* src, xlb
   };
   if (src->halo == 0 || opt(c, "external_halo", 0)) {
     if (strips) read_strips(p);
-    if (int rc = launch_step2(s, p)) return rc;
-    if (strips) dst_strips_done();
+    if (int rc = launch_step2(s, p, rep)) return rc;
+    if (strips && !rep) dst_strips_done();
     return 0;
   }
   // slab protocol for a PAIR of steps: the two ghost planes per side of src are refilled (depth 2) while the planes whose
@@ -380,8 +410,14 @@ static int step_twice(xlbhip_stepper* s, Fuse2 how, const xlbhip_field* src, xlb
       q.strips = Strips::write;
       q.strips_dst = dst->strips;
     }
-    return launch_step2(s, q);
+    return launch_step2(s, q, rep);
   };
+  if (rep) {  // slab_pass's launches in its order, without the exchange
+    if (!overlap) return launch(0, src->nx, SlabRole::whole);
+    if (int rc = launch(2, src->nx - 4, SlabRole::interior)) return rc;
+    if (int rc = launch(0, 2, SlabRole::edge)) return rc;
+    return launch(src->nx - 2, 2, SlabRole::edge);
+  }
   if (int rc = slab_pass(c, s->lattice, srcw, 2, 2, overlap, launch)) return rc;
   if (strips) dst_strips_done();
   return 0;
@@ -727,6 +763,20 @@ int xlbhip_step2(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, 
   XLB_REQUIRE(how.fuse, "this stepper / field layout has no two-step kernel (see xlbhip_step2_eligible)");
   if (int rc = prepare_fuse2(s, bcm, miss)) return rc;
   return step_twice(s, how, src, dst, bcm, miss, omega, timestep);
+}
+
+int xlbhip_step2_plan(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,
+                      int32_t* out, int64_t capacity, int64_t* n_words) {
+  XLB_REQUIRE(n_words && (out || capacity == 0), "null argument");
+  if (int rc = check_step_fields(s, src, dst, bcm, miss)) return rc;
+  const Fuse2 how = can_fuse2(s, src, bcm);
+  XLB_REQUIRE(how.fuse, "this stepper / field layout has no two-step kernel (see xlbhip_step2_eligible)");
+  if (int rc = prepare_fuse2(s, bcm, miss)) return rc;
+  Step2Report rep;
+  if (int rc = step_twice(s, how, src, dst, bcm, miss, 1.0, 0, &rep)) return rc;
+  *n_words = (int64_t)rep.words.size();
+  if (capacity >= *n_words) std::copy(rep.words.begin(), rep.words.end(), out);
+  return 0;
 }
 
 int xlbhip_run_timed(xlbhip_stepper* s, xlbhip_field* a, xlbhip_field* b, const xlbhip_field* bcm, const xlbhip_field* miss, double omega,
