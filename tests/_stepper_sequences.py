@@ -1,0 +1,785 @@
+"""Seeded operation sequences on ONE stepper's fields, and the plain model each sequence is checked against.  No GPU and no xlb_amd here:
+tests/test_stepper_sequences_cases.py checks the table with the oracle alone, tests/test_gpu_stepper_sequences.py replays every sequence
+through the public API and compares every read with the model, bit for bit.
+
+The stepper is the part whose answer depends on its history.  Natively it keeps caches (csrc/stepper.hip, the comment block above
+xlbhip_stepper: meta words, tile order, clean flags, the edge-kind scan, the scratch field, the fields' strip buffers, the profile ring);
+in Python it defers a reference-style call, fuses it with the next one, exchanges the two fields' buffers and leaves one field holding
+f(t+1) only virtually (operator/stepper/nse_stepper.py).  A stale cache or a step that runs too late gives fluid-looking numbers.
+
+The model (Sim) is eager and keyed by field object: a step is orc.run(state, bc_mask, missing_mask, bcs, omega, lattice, 1) with the
+masks as they are when the call is made; stepper(a, b, ...) means b := step(a); run(a, b, ..., n) returns (cur, oth) with
+cur := step^n(a), and for n >= 1 `oth` is UNDEFINED (the documentation promises nothing about it): no sequence reads an undefined field
+before it was wholly overwritten.  Next to the contents Sim restates what the implementation is expected to do, for the counters and
+the plan report only: the lazy states of the Python layer (nothing pending / a step deferred / a field virtual, as hooks on field
+objects), whether a pass is fused, where run() leaves its result, and which field carries valid strips.
+
+Mask variants: the set-up's background plus a one-cell fullway probe (the last BC of the list, fixed at construction) at a rim position
+of the restated plan, one cell further out, in another tile, at another x, or nowhere; the inlet / outlet channel also with an inlet cell
+in the interior (the edge-kind scan must then refuse to fuse, and allow it again when the mask returns).
+
+Set-ups (SETUPS): pairs, fullway, open (a periodic box with three x segments: the only one with clean work items, so the only one where
+stale clean flags can show), slab, inout, two_grids (ONE native stepper driven on three field sets of different shapes), two_channels
+(the same with the inlet / outlet channel on two shapes: the scratch field of the end planes), singles (D3Q27 KBC FP64FP32: never
+defers, never fuses), walls_in_time (a halfway wall whose velocity depends on the timestep: the model's step takes the BC list of its
+timestep, calls come on consecutive timesteps and with one skipped, a long run reuses every slot of the profile ring), pairs_two (pairs,
+opened through the second stepper object)."""
+
+import functools
+from collections import namedtuple
+
+import numpy as np
+
+import _step2_matrix as m
+from oracle import xlb_numpy as orc
+
+# ---- set-ups -----------------------------------------------------------------------------------------------------------------------
+# grids: ((shape), ...) — more than one only for two_grids.  lazy: reference-style calls are deferred and paired.  calls: the sequences
+# use reference-style calls (slab: run only).  native: the ops go to stepper._native_stepper() (two_grids).
+SeqSetup = namedtuple("SeqSetup", "name lattice policy collision grids halo background xseg lazy calls native base_options n_sequences")
+SETUPS = (
+    SeqSetup("pairs", "D3Q19", "FP32FP32", "BGK", ((12, 16, 64),), 0, "cavity_hw", 0, True, True, False, (("fuse2", 2),), 34),
+    SeqSetup("fullway", "D3Q19", "FP32FP32", "BGK", ((12, 16, 64),), 0, "cavity_fw", 0, True, True, False, (("fuse2", 2),), 30),
+    SeqSetup("open", "D3Q19", "FP32FP32", "BGK", ((24, 16, 64),), 0, "bare", 3, True, True, False, (("fuse2", 2), ("fuse2_xseg", 3)), 16),
+    SeqSetup("slab", "D3Q19", "FP32FP32", "BGK", ((16, 16, 64),), 2, "cavity_hw", 0, False, False, False, (("fuse2", 2),), 10),
+    SeqSetup("inout", "D3Q19", "FP32FP32", "BGK", ((24, 16, 64),), 0, "inout", 2, True, True, False, (("fuse2", 2), ("fuse2_xseg", 2)), 12),
+    SeqSetup("two_grids", "D3Q19", "FP32FP32", "BGK", ((12, 16, 64), (12, 8, 128), (10, 16, 64)), 0, "cavity_hw", 0, False, False, True, (("fuse2", 2),), 10),
+    SeqSetup("two_channels", "D3Q19", "FP32FP32", "BGK", ((24, 16, 64), (16, 16, 64)), 0, "inout", 2, False, False, True, (("fuse2", 2), ("fuse2_xseg", 2)), 4),
+    SeqSetup("singles", "D3Q27", "FP64FP32", "KBC", ((7, 6, 8),), 0, "cavity_hw", 0, False, True, False, (("fuse2", 2), ("exact_math", 1)), 8),
+    # (last, so that the sequences above keep their numbers) the smallest box the two-step kernel takes with a time-dependent halfway
+    # wall: the wall on the plane x = 0, which goes through the single-step kernel (nx >= 16), as in tests/test_gpu_time_dependent_profiles.py
+    SeqSetup("walls_in_time", "D3Q19", "FP32FP32", "BGK", ((16, 16, 64),), 0, "plate_td", 2, True, True, False, (("fuse2", 2), ("fuse2_xseg", 2)), 12),
+    # pairs again, opened by the second stepper object: it flushes the first one's deferred step, defers, fuses and materialises itself
+    SeqSetup("pairs_two", "D3Q19", "FP32FP32", "BGK", ((12, 16, 64),), 0, "cavity_hw", 0, True, True, False, (("fuse2", 2),), 4),
+)
+RING_SLOTS = 64  # prof_ring.hpp: the ring of per-timestep tables of a wall this small; run() stages chunks of half of it
+OPTION_DEFAULTS = {"fuse2": 1, "fuse2_xseg": 0, "fuse2_clean": 1, "fuse2_strips": 1, "fuse2_rowmap": 0, "vec": 0, "overlap": 1, "exact_math": 0}
+OMEGAS = (1.2, 1.7)
+VARIANTS = ("rim", "out", "tile", "xseg", "none")
+STATES = ("none", "deferred", "virtual")
+# the rules of the comment block above xlbhip_stepper (stepper.hip) a sequence may target, and RULE_SETUPS: where each can be hit
+TAGS_BESIDE_RULES = ("second_stepper",)
+RULES = ("meta", "tile_order", "clean", "scan", "scratch", "strips", "profile_ring", "virtual_masks")
+OP_CLASS = {
+    "call": "calls", "call_noswap": "calls", "call_omega": "calls", "call_second": "calls", "call_gap": "calls", "run": "calls",
+    "numpy": "reads", "get_plane": "reads", "macro": "reads", "sync": "reads", "mask_numpy": "reads",
+    "assign": "writes", "set_plane": "writes", "fill": "writes", "copy_from": "writes", "equilibrium": "writes", "stream": "writes", "touch": "writes",
+    "mask_assign": "masks", "mask_new": "masks",
+    "fields_new": "fields", "pin": "fields",
+    "option": "options", "plan": "plan", "grid": "grids",
+}
+
+
+def m_setup(s, g=0):
+    """the set-up as tests/_step2_matrix.py describes one (for its masks, seams and restated plan)"""
+    return m.Setup(f"{s.name}{g}", s.lattice, s.grids[g], s.halo, 1, s.xseg, s.background in ("inout", "plate_td"), (s.background,))
+
+
+def time_dependent(s):
+    return s.background == "plate_td"
+
+
+def plate(cells, t):
+    """the wall velocity of the plate x = 0 of walls_in_time at timestep t (period 6: consecutive timesteps differ)"""
+    y = cells[1].astype(np.float64)
+    w = np.sin(2.0 * np.pi * t / 6.0)
+    return np.stack([np.zeros_like(y), 0.01 * w * np.ones_like(y), 0.03 * w * (1.0 + 0.5 * np.cos(y))])
+
+
+def specs_of(s, g, pos):
+    """the BC list of grid g with the probe at pos (None: the background alone); ids 1, 2, ... in list order"""
+    ms = m_setup(s, g)
+    if not time_dependent(s):
+        return m.bc_specs(ms, s.background, "fw" if pos else None, pos)
+    box, box_ne = orc.bounding_box_indices(ms.shape), orc.bounding_box_indices(ms.shape, remove_edges=True)
+    walls = np.unique(np.concatenate([np.asarray(box[f]) for f in ("bottom", "top", "front", "back")], axis=1), axis=-1).tolist()
+    raw = [(orc.KIND_HALFWAY_BB, walls, {}), (orc.KIND_HALFWAY_BB, box_ne["left"], dict(profile=True)), (orc.KIND_HALFWAY_BB, box_ne["right"], {})]
+    if pos:
+        raw.append(m.probe_spec("fw", pos, ms.shape))
+    return [m.BCSpec(kind, i + 1, idx, params) for i, (kind, idx, params) in enumerate(raw)]
+
+
+def _oracle_bcs(specs):
+    return [orc.BC(sp.kind, sp.id, sp.indices, **{k: v for k, v in sp.params.items() if k != "profile"}) for sp in specs]
+
+
+@functools.lru_cache(maxsize=8)
+def bcs_at(s, g, t):
+    """the oracle's BC list of the step from f(t) to f(t+1): the time-dependent wall with its velocities at t"""
+    from oracle import mesh_bc as mb
+
+    lat, obcs, _ = setup_masks(s, g)
+    shape = s.grids[g]
+    cells = np.stack(np.meshgrid(*[np.arange(n) for n in shape], indexing="ij")).reshape(3, -1)
+    u_wall = np.asarray(plate(cells, t), np.float64).reshape((3,) + tuple(shape))
+    profile_id = next(sp.id for sp in specs_of(s, g, None) if sp.params.get("profile"))
+    return [mb.HalfwayProfileBC(bc.id, None, u_wall) if bc.id == profile_id else bc for bc in obcs]
+
+
+def variant_pos(s, g, variant):
+    ms = m_setup(s, g)
+    nx, ny, nz = ms.shape
+    if s.lattice != "D3Q19":  # singles: no tiles, any four distinct interior cells
+        return {"rim": (3, 2, 3), "out": (3, 3, 3), "tile": (4, 3, 5), "xseg": (2, 2, 2)}.get(variant)
+    sy, sz = m.seams(ms, 1), m.seams(ms, 2)
+    x_in, x_far = nx // 2, (nx - 2 if s.halo else nx - 5)
+    y_rim = (sy[0] - 1) % ny
+    y_rim = y_rim if 0 < y_rim < ny - 1 else 3  # (a single y tile: its seam is the wrap; the walls sit there)
+    z_a, z_b = (sz[0] - 12) % nz, (sz[0] + 13) % nz
+    return {"rim": (x_in, y_rim, z_a), "out": (x_in, y_rim - 1, z_a), "tile": (x_in, (y_rim + 7) % ny, z_b), "xseg": (x_far, (y_rim + 7) % ny, z_b)}.get(variant)
+
+
+Variant = namedtuple("Variant", "bc_mask missing_mask fuses")
+
+
+@functools.lru_cache(maxsize=None)
+def setup_masks(s, g=0):
+    """(lattice, oracle BCs, {variant: Variant}) of grid g; the BC list — background, then the probe — is the same for every variant"""
+    ms = m_setup(s, g)
+    lat = orc.Lattice(s.lattice)
+    obcs = _oracle_bcs(specs_of(s, g, variant_pos(s, g, "rim")))
+    out = {}
+    for v in VARIANTS + (("inlet_in",) if s.background == "inout" else ()):
+        pos = variant_pos(s, g, v)
+        specs = specs_of(s, g, pos)
+        fuses = True
+        if v == "inlet_in":  # one cell of the inlet's id inside the box
+            inlet = next(i for i, sp in enumerate(specs) if sp.kind == orc.KIND_REGULARIZED_VELOCITY)
+            idx = [list(a) + [b] for a, b in zip(specs[inlet].indices, (ms.shape[0] // 2, 5, 40))]
+            specs[inlet] = specs[inlet]._replace(indices=idx)
+            fuses = False
+        if specs:
+            bm, mm = orc.build_masks(ms.shape, lat, _oracle_bcs(specs))
+        else:
+            bm, mm = np.zeros((1,) + ms.shape, np.uint8), np.zeros((lat.q,) + ms.shape, bool)
+        bm.setflags(write=False)
+        mm.setflags(write=False)
+        out[v] = Variant(bm, mm, fuses)
+    return lat, obcs, out
+
+
+@functools.lru_cache(maxsize=None)
+def needs_missing(s):
+    return m.needs_missing(specs_of(s, 0, (1, 1, 1)))
+
+
+@functools.lru_cache(maxsize=64)
+def init_field(s, g, seed):
+    f = orc.perturbed_init(s.grids[g], orc.Lattice(s.lattice), policy=s.policy, seed=seed)
+    f.setflags(write=False)
+    return f
+
+
+def restated_plan(s, g, variant, options, strips_valid):
+    """[(Launch, clean flags)] of the next pass: pass_launches / clean_flags of tests/_step2_matrix.py under the options of the moment"""
+    ms = m_setup(s, g)
+    knobs = m.Knobs("now", options["fuse2_clean"], options["fuse2_strips"], options["fuse2_rowmap"])
+    ls = m.pass_launches(s.lattice, ms.shape, s.halo, options["overlap"], options["fuse2_xseg"], knobs, needs_missing(s), ms.inout, strips_valid)
+    tagged = setup_masks(s, g)[2][variant].bc_mask[0] != 0
+    return [(l, m.clean_flags(tagged, l, s.halo > 0)) for l in ls]
+
+
+def writes_strips(s, g, options):
+    """does a fused pass on grid g leave valid strips in its destination (stepper.hip step_twice; never on the edge_ext path)"""
+    if s.background in ("inout", "plate_td"):
+        return False
+    ls = m.pass_launches(s.lattice, s.grids[g], s.halo, options["overlap"], options["fuse2_xseg"],
+                         m.Knobs("now", options["fuse2_clean"], options["fuse2_strips"], options["fuse2_rowmap"]), needs_missing(s), False, False)
+    return any(l.strips in (m.STRIPS_WRITE, m.STRIPS_READ_WRITE) for l in ls)
+
+
+_memo = {}  # one oracle step per (set-up, grid, variant, omega, input): the replays of a sequence share their prefixes
+
+
+def _step(s, g, variant, omega, f, t=0):
+    import hashlib
+
+    t = t if time_dependent(s) else None  # (the timestep enters the step only through a time-dependent wall)
+    key = (s.name, g, variant, omega, t, hashlib.blake2b(np.ascontiguousarray(f).view(np.uint8), digest_size=16).digest())
+    out = _memo.get(key)
+    if out is None:
+        lat, obcs, variants = setup_masks(s, g)
+        v = variants[variant]
+        with np.errstate(all="ignore"):  # (the Zou-He expressions are evaluated on every cell and selected afterwards)
+            if t is None:
+                out = orc.run(f, v.bc_mask, v.missing_mask, obcs, omega, lat, 1, s.policy, s.collision)
+            else:
+                from oracle import mesh_bc as mb
+
+                out = mb.step(f, v.bc_mask, v.missing_mask, bcs_at(s, g, t), omega, lat, s.policy, s.collision)
+        out.setflags(write=False)
+        if len(_memo) >= 96:
+            _memo.pop(next(iter(_memo)))
+        _memo[key] = out
+    return out
+
+
+# ---- the model -------------------------------------------------------------------------------------------------------------------
+class Grid:
+    """the fields of one grid as the driver holds them: two population objects, the mask objects, the variant they hold, the timestep"""
+
+    def __init__(self, cur, oth, masks, variant):
+        self.cur, self.oth, self.masks, self.variant, self.t = cur, oth, masks, variant, 0
+
+
+class Sim:
+    """Contents (eager, keyed by field object id) + the restated implementation state.  apply(op) returns what the op observes:
+    None, or a dict of expected values (arrays for reads, the plan, where run() left its result)."""
+
+    def __init__(self, s, seed0, keep_masks_at=None, contents=True):
+        self.s = s
+        self.contents = contents  # False: the generator's dry run — fields are only defined (True) or undefined (None), no oracle
+        self.options = dict(OPTION_DEFAULTS)
+        self.options.update(dict(s.base_options))
+        self.pops = {}  # population object id -> array, or None: undefined
+        self.next_id = 0
+        self.grids = []
+        for g in range(len(s.grids)):
+            a, b = self._new_pop(self._init(g, seed0 + g)), self._new_pop(self._zeros(g))
+            self.grids.append(Grid(a, b, self._new_id(), "rim"))
+        self.g = 0
+        # restated Python layer: hooks on objects (("f", id) / ("bm", id) / ("mm", id)), one deferred record per stepper object
+        self.hooks, self.deferred, self.flushers, self.pinned = {}, {0: None, 1: None}, [], set()
+        self.n_fused, self.n_materialised = {0: 0, 1: 0}, {0: 0, 1: 0}
+        self.strips = {}  # population object id -> its strips are those of its contents
+        self.stale = {}  # population object id -> it carries strips of EARLIER contents (a write came after the pass that made them)
+        self.base = {}  # virtual field -> (the f(t) its f(t+1) is owed from, omega, t)
+        self.stamp = {}  # population object id -> index of the op whose step wrote its contents (-1: not a step's result)
+        self.events = []  # (op index, kind, detail): fused passes, materialisations, ... — what the tags are checked on
+        self.i = -1
+        self.keep_masks_at = keep_masks_at  # (the discrimination check: the mask edit at this op index is left out)
+
+    # -- bookkeeping
+    def _new_id(self):
+        self.next_id += 1
+        return self.next_id
+
+    def _new_pop(self, arr):
+        i = self._new_id()
+        self.pops[i] = arr
+        return i
+
+    @property
+    def G(self):
+        return self.grids[self.g]
+
+    def masks_now(self, g=None):
+        lat, obcs, variants = setup_masks(self.s, self.g if g is None else g)
+        return lat, obcs, variants[self.grids[self.g if g is None else g].variant]
+
+    def _init(self, g, seed):
+        return init_field(self.s, g, seed) if self.contents else True
+
+    def _zeros(self, g):
+        return np.zeros_like(init_field(self.s, g, 0)) if self.contents else True
+
+    def step(self, f, omega=OMEGAS[0], n=1):
+        """n steps from the grid's timestep"""
+        if not self.contents:
+            return True
+        for j in range(n):
+            f = _step(self.s, self.g, self.G.variant, omega, f, self.G.t + j)
+        return f
+
+    def state(self):
+        if any(h[0] == "mat" for h in self.hooks.values()):
+            return "virtual"
+        return "deferred" if any(d is not None for d in self.deferred.values()) else "none"
+
+    def fuses(self, g=None):
+        """xlbhip_step2_eligible with fuse2 = 0 / 2 at these shapes: the two-step kernel exists and the masks allow it"""
+        g = self.g if g is None else g
+        return self.s.lattice == "D3Q19" and self.options["fuse2"] == 2 and setup_masks(self.s, g)[2][self.grids[g].variant].fuses
+
+    # -- restated hooks (Field.handle, nse_stepper.py _lazy_pair / _flush_deferred / _materialise)
+    def _use(self, *objs):
+        for o in objs:
+            h = self.hooks.pop(o, None)
+            if h is not None:
+                self._fire(h)
+
+    def _fire(self, h):
+        if h[0] == "flush":
+            self._flush(h[1])
+        else:
+            _, k, field, bm, mm = h
+            for o in (("f", field), bm, mm):  # the hook is shared: used once, released everywhere
+                if self.hooks.get(o) is h:
+                    del self.hooks[o]
+            self.n_materialised[k] += 1
+            self.strips[field] = self.stale[field] = False  # (the field adopts the temporary's buffer)
+            self.events.append((self.i, "materialise", field))
+
+    def _flush(self, k):
+        d, self.deferred[k] = self.deferred[k], None
+        if d is not None:
+            for o in d["objs"]:
+                self.hooks.pop(o, None)
+            self._no_strips(d["dst"])
+            self.events.append((self.i, "single", dict(k=k, fuses=self.fuses(), fuse2=self.options["fuse2"])))
+
+    def _drop_virtual(self, f):
+        h = self.hooks.get(("f", f))
+        if h is not None and h[0] == "mat":
+            for o in (("f", h[2]), h[3], h[4]):
+                if self.hooks.get(o) is h:
+                    del self.hooks[o]
+
+    def _mask_objs(self):
+        return ("bm", self.G.masks), ("mm", self.G.masks)
+
+    def _pass2(self, k, src, dst):
+        """a fused pass src -> dst of stepper k"""
+        valid = bool(self.strips.get(src)) and self.options["fuse2_strips"] != 0
+        self.events.append((self.i, "pass2", dict(k=k, g=self.g, variant=self.G.variant, masks=self.G.masks, strips_read=valid,
+                                                 stale_src=bool(self.stale.get(src)), options=dict(self.options))))
+        self.strips[dst] = writes_strips(self.s, self.g, self.options)
+        self.stale[dst] = False
+
+    def _call(self, k, f0, f1, omega):
+        """hip_implementation / _lazy_pair of stepper k, contents aside"""
+        G = self.G
+        in_time = lambda d: not time_dependent(self.s) or G.t == d["t"] + 1  # noqa: E731 (nse_stepper.py pairs_in_time)
+        bm, mm = self._mask_objs()
+        self._drop_virtual(f1)
+        d = self.deferred[k]
+        if d is not None:
+            if d["src"] == f1 and d["dst"] == f0 and d["masks"] == G.masks and d["omega"] == omega and f0 not in self.pinned and f1 not in self.pinned and in_time(d):
+                self.deferred[k] = None
+                for o in d["objs"]:
+                    self.hooks.pop(o, None)
+                if self.fuses():
+                    self.n_fused[k] += 1
+                    self._pass2(k, d["src"], d["dst"])
+                    # the buffers are exchanged: the strips follow the buffer that received f(t+2), now held by d["src"]
+                    for tab in (self.strips, self.stale):
+                        tab[d["src"]], tab[d["dst"]] = bool(tab.get(d["dst"])), bool(tab.get(d["src"]))
+                    h = ("mat", k, d["dst"], bm, mm)
+                    for o in (("f", d["dst"]), bm, mm):
+                        self.hooks[o] = h
+                    return
+                self._no_strips(d["dst"])  # (an option changed in between: the deferred step alone, then this call's)
+                self.events.append((self.i, "single", dict(k=k, fuses=False, fuse2=self.options["fuse2"])))
+                self._single(k, f0, f1)
+                return
+            self._flush(k)
+        if self.s.lazy and f0 not in self.pinned and f1 not in self.pinned:
+            self._use(("f", f0), ("f", f1), bm, mm)  # step2_eligible
+            if self.fuses():
+                objs = (("f", f0), ("f", f1), bm, mm)
+                self.deferred[k] = dict(src=f0, dst=f1, masks=G.masks, omega=omega, objs=objs, t=G.t)
+                for o in objs:
+                    self.hooks[o] = ("flush", k)
+                if k not in self.flushers:
+                    self.flushers.append(k)
+                return
+        self._single(k, f0, f1)
+
+    def _single(self, k, f0, f1):
+        self._use(("f", f0), ("f", f1), *self._mask_objs())
+        self._no_strips(f1)
+        self.events.append((self.i, "single", dict(k=k, fuses=self.fuses(), fuse2=self.options["fuse2"])))
+
+    def _sync(self):
+        for k in self.flushers:
+            self._flush(k)
+
+    def _no_strips(self, f):
+        if self.strips.get(f):
+            self.stale[f] = True
+        self.strips[f] = False
+
+    def _write(self, f, from_step=False):
+        self._use(("f", f))
+        self._no_strips(f)
+        if not from_step:
+            self.stamp[f] = -1
+
+    # -- the ops
+    def apply(self, op):
+        self.i += 1
+        kind, G, P = op[0], self.G, self.pops
+        if kind in ("call", "call_noswap", "call_omega", "call_second", "call_gap"):
+            if kind == "call_gap":  # the driver skips a timestep: this call is not the deferred one's successor
+                G.t += 1
+            omega = OMEGAS[1] if kind == "call_omega" else OMEGAS[0]
+            k = 1 if kind == "call_second" else 0
+            before = P[G.oth]
+            P[G.oth] = self.step(P[G.cur], omega=omega)
+            self.stamp[G.oth] = self.i
+            self._call(k, G.cur, G.oth, omega)
+            if self.hooks.get(("f", G.cur), ("",))[0] == "mat":  # fused: G.cur holds f(t+1) virtually, a step from what G.oth held
+                self.base[G.cur] = (before, omega, G.t - 1)
+            if kind != "call_noswap":
+                G.cur, G.oth = G.oth, G.cur
+                G.t += 1
+            return None
+        if kind == "run":
+            n = op[1]
+            a, b = G.cur, G.oth
+            self._flush(0)
+            if n >= 1:
+                self._drop_virtual(b)
+            if n or not time_dependent(self.s):  # (the chunked run of time-dependent walls: no chunk, no use of the fields)
+                self._use(("f", a), ("f", b), *self._mask_objs())
+            self.events.append((self.i, "run", dict(n=n, g=self.g)))
+            for f in (a, b):
+                if f in self.pinned:  # (an exported field counts as written every time it is used)
+                    self._no_strips(f)
+            fused = n >= 2 and self.fuses()
+            flips = (n // 2 + n % 2) if fused else n
+            cur, oth = a, b
+            for j in range(flips):
+                if fused and j < n // 2:
+                    self._pass2(0, cur, oth)
+                else:
+                    self._no_strips(oth)
+                    self.events.append((self.i, "single", dict(k=0, fuses=self.fuses(), fuse2=self.options["fuse2"])))
+                cur, oth = oth, cur
+            result = self.step(P[a], n=n) if n else P[a]
+            if n >= 1:
+                P[oth] = None
+                self.stamp[cur], self.stamp[oth] = self.i, -1
+            P[cur] = result
+            G.cur, G.oth, G.t = cur, oth, G.t + n
+            return dict(result_in_b=cur == b)
+        if kind == "numpy":
+            f = getattr(G, op[1])
+            self._use(("f", f))
+            return dict(value=P[f], stamp=self.stamp.get(f, -1))
+        if kind == "get_plane":
+            f = getattr(G, op[1])
+            self._use(("f", f))
+            return dict(value=P[f][op[2], op[3]] if self.contents else None)
+        if kind == "macro":
+            f = getattr(G, op[1])
+            self._use(("f", f))
+            rho, u = orc.macroscopic(P[f], setup_masks(self.s, self.g)[0]) if self.contents else (None, None)
+            return dict(rho=rho, u=u, stamp=self.stamp.get(f, -1))
+        if kind == "sync":
+            self._sync()
+            return None
+        if kind == "mask_numpy":
+            self._use((op[1], G.masks))
+            v = self.masks_now()[2]
+            return dict(value=(v.bc_mask if op[1] == "bm" else v.missing_mask.astype(np.uint8)) if self.contents else None)
+        if kind == "assign":
+            f = getattr(G, op[1])
+            self._write(f)
+            P[f] = self._init(self.g, op[2])
+            return None
+        if kind == "set_plane":
+            f = getattr(G, op[1])
+            self._write(f, from_step=True)  # (one plane: the rest is still what it was)
+            if self.contents:
+                new = P[f].copy()
+                new[op[2], op[3]] = init_field(self.s, self.g, op[4])[op[2], op[3]]
+                P[f] = new
+            return None
+        if kind == "fill":
+            f = getattr(G, op[1])
+            self._write(f)
+            P[f] = np.full_like(init_field(self.s, self.g, 0), op[2]) if self.contents else True
+            return None
+        if kind == "copy_from":  # oth <- cur
+            self._use(("f", G.oth), ("f", G.cur))
+            self._no_strips(G.oth)
+            P[G.oth], self.stamp[G.oth] = P[G.cur], self.stamp.get(G.cur, -1)
+            return None
+        if kind == "equilibrium":  # the operator's output is the field: feq(rho, u) of the seed's (rho, u) == perturbed_init(seed)
+            f = getattr(G, op[1])
+            self._write(f)
+            P[f] = self._init(self.g, op[2])
+            return None
+        if kind == "stream":  # oth <- Stream(cur)
+            self._use(("f", G.cur), ("f", G.oth))
+            self._no_strips(G.oth)
+            P[G.oth], self.stamp[G.oth] = (orc.stream(P[G.cur], setup_masks(self.s, self.g)[0]) if self.contents else True), self.stamp.get(G.cur, -1)
+            return None
+        if kind == "touch":
+            self._write(getattr(G, op[1]), from_step=True)
+            return None
+        if kind == "mask_assign":
+            self._use(*self._mask_objs())
+            if self.keep_masks_at != self.i:
+                G.variant = op[1]
+            return None
+        if kind == "mask_new":  # the old objects are freed (Field.free runs what is owed on them), new ones uploaded
+            self._use(*self._mask_objs())
+            G.masks = self._new_id()
+            if self.keep_masks_at != self.i:
+                G.variant = op[1]
+            return None
+        if kind == "fields_new":  # both population objects freed, two new ones: the seed's field and zeros
+            self._use(("f", G.cur), ("f", G.oth))
+            for f in (G.cur, G.oth):
+                del P[f]
+                self.pinned.discard(f)
+            G.cur = self._new_pop(self._init(self.g, op[1]))
+            G.oth = self._new_pop(self._zeros(self.g))
+            return None
+        if kind == "pin":  # __cuda_array_interface__: info() uses the field, then ctx.sync()
+            f = getattr(G, op[1])
+            self._use(("f", f))
+            self.pinned.add(f)
+            self._sync()
+            return None
+        if kind == "option":
+            self.options[op[1]] = op[2]
+            return None
+        if kind == "plan":
+            self._use(("f", G.cur), ("f", G.oth), *self._mask_objs())
+            return dict(plan=restated_plan(self.s, self.g, G.variant, self.options, bool(self.strips.get(G.cur)) and self.options["fuse2_strips"] != 0))
+        if kind == "grid":
+            self.g = op[1]
+            return None
+        raise ValueError(kind)
+
+    def final(self):
+        """per grid the fields (None: undefined) and the mask variant at the end.  Looking at them is a use like any other: every defined
+        field, then both masks (what is still owed runs now, and counts)"""
+        self.i += 1
+        for G in self.grids:
+            self._use(*[("f", f) for f in (G.cur, G.oth) if self.pops[f] is not None], ("bm", G.masks), ("mm", G.masks))
+        return [dict(cur=self.pops[G.cur], oth=self.pops[G.oth], variant=G.variant, stamps=(self.stamp.get(G.cur, -1), self.stamp.get(G.oth, -1))) for G in self.grids]
+
+
+# ---- the generator ---------------------------------------------------------------------------------------------------------------
+Sequence = namedtuple("Sequence", "n setup seed ops tags")
+
+
+def seq_id(q):
+    return f"{q.n:03d}-{q.setup.name}-{'+'.join(q.tags) if q.tags else 'mix'}"
+
+
+def _defined(sim, slot):
+    return sim.pops[getattr(sim.G, slot)] is not None
+
+
+def _candidates(sim, rng, cls):
+    """the ops of class `cls` that are possible now, in a seeded order"""
+    s, G, out = sim.s, sim.G, []
+    slots = [sl for sl in ("cur", "oth") if _defined(sim, sl)]
+    nx = s.grids[sim.g][0]
+    q = orc.Lattice(s.lattice).q
+    seed = int(rng.integers(100, 10**6))
+    plane = (int(rng.integers(0, q)), int(rng.integers(1, nx - 1)))
+    if cls == "calls":
+        if s.calls:
+            out += [("call",), ("call",), ("call_noswap",), ("call_omega",), ("call_second",)] + ([("call_gap",)] if time_dependent(s) else [])
+        out += [("run", int(n)) for n in rng.permutation(6)[:3]]
+    elif cls == "reads":
+        out += [("numpy", sl) for sl in slots] + [("get_plane", sl) + plane for sl in slots] + [("sync",), ("mask_numpy", "bm"), ("mask_numpy", "mm")]
+        if s.policy == "FP32FP32":
+            out += [("macro", sl) for sl in slots]
+    elif cls == "writes":
+        out += [("assign", sl, seed) for sl in ("cur", "oth")] + [("fill", "oth", 0.05 + 0.001 * int(rng.integers(1, 9))), ("touch", "cur"), ("copy_from",), ("stream",)]
+        out += [("set_plane", sl) + plane + (seed,) for sl in slots]
+        if s.policy == "FP32FP32":
+            out += [("equilibrium", "oth", seed)]
+    elif cls == "masks":
+        others = [v for v in setup_masks(s, sim.g)[2] if v != G.variant]
+        out += [("mask_assign", others[int(rng.integers(len(others)))]), ("mask_new", others[int(rng.integers(len(others)))])]
+    elif cls == "fields":
+        out += [("fields_new", seed)] + ([("pin", "cur"), ("pin", "oth")] if s.halo == 0 else [])
+    elif cls == "options":
+        o = sim.options
+        out += [("option", "fuse2", 0 if o["fuse2"] else 2), ("option", "vec", {0: 1, 1: 4, 4: 0}[o["vec"]])]
+        for key, values in (("fuse2_xseg", (0, 1, 2, 3)), ("fuse2_clean", (0, 1)), ("fuse2_strips", (0, 1, 2)), ("overlap", (0, 1))):
+            if key == "overlap" and not s.halo:
+                continue
+            for v in values:
+                if v != o[key] and _plan_changes(sim, key, v):
+                    out.append(("option", key, v))
+    elif cls == "plan":
+        if sim.fuses() and _defined(sim, "oth"):
+            out.append(("plan",))
+    elif cls == "grids":
+        out += [("grid", g) for g in range(len(s.grids)) if g != sim.g]
+    return [out[i] for i in rng.permutation(len(out))]
+
+
+def _plan_key(s, g, variant, options):
+    return [(l, tuple(f)) for l, f in restated_plan(s, g, variant, options, False)]
+
+
+def _plan_changes(sim, key, value):
+    if sim.s.lattice != "D3Q19":
+        return False
+    return _plan_key(sim.s, sim.g, sim.G.variant, sim.options) != _plan_key(sim.s, sim.g, sim.G.variant, dict(sim.options, **{key: value}))
+
+
+def _allowed(sim, op):
+    """an op must not read an undefined field"""
+    if op[0] in ("call", "call_noswap", "call_omega", "call_second", "call_gap", "run", "copy_from", "stream") and not _defined(sim, "cur"):
+        return False
+    return True
+
+
+# scripted openings per targeted rule: the op pattern that defines the tag (tests/test_stepper_sequences_cases.py checks it is there)
+def _opening(s, tag, rng):
+    v = ["out", "tile", "xseg", "none"][int(rng.integers(4))]
+    edit = ("mask_assign", v) if int(rng.integers(2)) else ("mask_new", v)
+    if tag == "virtual_masks":  # a fused pair, then a mask edit while one field is virtual, then that field is read
+        return [("call",), ("call",), edit, ("numpy", "oth")]
+    if tag == "meta":  # two fused passes of one stepper with a mask edit in between
+        return [("run", 2), edit, ("run", 2 + int(rng.integers(3))), ("numpy", "cur")]
+    if tag == "clean":  # ... whose clean flags differ, and the segments changed in between as well
+        return [("run", 2), ("numpy", "cur"), ("mask_assign", v), ("run", 2), ("numpy", "cur"), ("option", "fuse2_xseg", 0), ("run", 2),
+                ("option", "fuse2_xseg", 3), ("assign", "oth", 77), ("plan",), ("run", 2), ("numpy", "cur")]
+    if tag == "scan":  # the inlet cell moves inside and back, fused passes around it
+        return [("run", 2), ("mask_assign", "inlet_in"), ("run", 2), ("numpy", "cur"), ("mask_assign", v), ("run", 4), ("numpy", "cur")]
+    if tag == "scratch":  # one native stepper of the channel: the end planes' third field follows the shape of the fields
+        return [("run", 2), ("grid", 1), ("run", 2), ("numpy", "cur"), ("grid", 0), ("run", 3), ("numpy", "cur"), ("grid", 1), ("run", 2), ("numpy", "cur")]
+    if tag == "strips":  # a strip-writing pass, a write to its result, a pass that would read the strips
+        w = [("set_plane", "cur", 3, s.grids[0][0] // 2, 901), ("assign", "cur", 902)][int(rng.integers(2))]
+        return [("run", 2), w, ("run", 2), ("numpy", "cur")]
+    if tag == "profile_ring":  # more steps than the ring holds (every slot reused), a fused pair at the timesteps after, its virtual field read;
+        # then a deferred call whose successor skips a timestep (no pair: pairs_in_time), and the call after that one (a pair again)
+        return [("run", RING_SLOTS + 2 + int(rng.integers(4))), ("numpy", "cur"), ("call",), ("call",), ("numpy", "oth"), ("call",), ("call_gap",), ("call",), ("numpy", "cur")]
+    if tag == "second_stepper":  # a deferred step of the first object, then the second: flushes it, defers, fuses; its virtual field is read
+        return [("call",), ("call_second",), ("call_second",), ("numpy", "oth"), ("call_second",), ("call",), ("numpy", "cur")]
+    if tag == "tile_order":  # one native stepper: a fused pass on one tiling, then on another, then back
+        return [("run", 2), ("grid", 1), ("run", 2), ("numpy", "cur"), ("grid", 2), ("run", 3), ("numpy", "cur"), ("grid", 0), ("run", 2), ("numpy", "cur")]
+    raise ValueError(tag)
+
+
+RULE_SETUPS = {"virtual_masks": ("pairs", "fullway", "open", "walls_in_time"), "meta": ("pairs", "fullway", "slab", "open", "walls_in_time"),
+               "profile_ring": ("walls_in_time",), "second_stepper": ("pairs_two",), "clean": ("open",), "scan": ("inout",),
+               "strips": ("pairs", "fullway", "slab", "open"), "tile_order": ("two_grids",), "scratch": ("two_channels",)}
+
+
+def _generate(s, n, seed, tags, coverage):
+    """one sequence: the scripted openings of its tags, then 10-16 ops in all.  Where reference-style calls pair, every other op is a call
+    that moves the lazy state on (nothing -> deferred -> virtual); the ops in between come from the (lazy state, op class) cell least used
+    so far.  A dry run of the model (no oracle) says what is possible and which state each op meets."""
+    rng = np.random.default_rng(seed)
+    sim = Sim(s, seed, contents=False)
+    ops = []
+
+    def take(op):
+        cell = (s.name, sim.state(), OP_CLASS[op[0]])
+        coverage[cell] = coverage.get(cell, 0) + 1
+        coverage[cell[:2] + (op[0],)] = coverage.get(cell[:2] + (op[0],), 0) + 1  # (the kind of op as well: the rarest goes first)
+        sim.apply(op)
+        ops.append(op)
+
+    for tag in tags:
+        for op in _opening(s, tag, rng):
+            take(op)
+    length = max(len(ops) + 2, int(rng.integers(10, 17)))
+    classes = ["calls", "reads", "writes", "masks", "fields", "options", "plan"] + (["grids"] if len(s.grids) > 1 else [])
+
+    def owed():
+        """what the last mask edit still needs so that it can be told from the masks before: steps under it, then a look at their result"""
+        last = max((i for i, op in enumerate(ops) if OP_CLASS[op[0]] == "masks"), default=None)
+        if last is None:
+            return []
+        after = ops[last + 1 :]
+        steps = [i for i, op in enumerate(after) if op[0] == "call" or (op[0] == "run" and op[1] >= 1)]
+        if not steps:
+            return ([("call",), ("call",)] if s.calls else [("run", 2 + int(rng.integers(3)))]) + [("numpy", "cur")]
+        if s.lazy and len(steps) < 2 and len(after) == 1:
+            return [("call",), ("numpy", "cur")]
+        if not any(op in (("numpy", "cur"), ("macro", "cur")) for op in after[steps[0] + 1 :]) and len(after) == (2 if s.lazy else 1):
+            return [("numpy", "cur")]
+        return []
+
+    while len(ops) < length or owed():
+        state = sim.state()
+        due = owed()
+        if due:
+            take(due[0])
+            continue
+        if s.lazy and _defined(sim, "cur") and sim.fuses() and not (sim.pinned & {sim.G.cur, sim.G.oth}) and len(ops) % 2 == 0 and state != "virtual":
+            take(("call",))
+            continue
+        order = sorted(classes, key=lambda c: (coverage.get((s.name, state, c), 0), rng.random()))
+        if not s.lazy and len(ops) % 2 == 0:
+            order = ["calls"] + order
+        for cls in order:
+            cand = [op for op in _candidates(sim, rng, cls) if _allowed(sim, op)]
+            if cand:
+                take(min(cand, key=lambda op: coverage.get((s.name, state, op[0]), 0)))
+                break
+    return Sequence(n, s, seed, tuple(ops), tuple(tags))
+
+
+# seeds that gave a sequence unable to tell (discrimination_failures) are stepped over: {sequence number: seeds to skip}.  Found by running
+# find_seed_skips() after a change of the generator; tests/test_stepper_sequences_cases.py checks that every sequence of the table tells.
+SEED_SKIPS = {}
+
+
+@functools.lru_cache(maxsize=None)
+def sequences(skips=None):
+    out, coverage = [], {}
+    for s in SETUPS:
+        tags_for = [t for t in RULES + TAGS_BESIDE_RULES if s.name in RULE_SETUPS.get(t, ())]
+        for j in range(s.n_sequences):
+            # the first sequences of a set-up open with one targeted rule each (three rounds), the rest are coverage-driven mixes
+            tags = [tags_for[j % len(tags_for)]] if tags_for and j < 3 * len(tags_for) else []
+            n = len(out)
+            out.append(_generate(s, n, 7000 + 100 * n + (SEED_SKIPS if skips is None else dict(skips)).get(n, 0), tags, coverage))
+    return tuple(out)
+
+
+def find_seed_skips():
+    """SEED_SKIPS for the generator as it stands (minutes of oracle time: not run by the tests)"""
+    skips = {}
+    while True:
+        bad = [q.n for q in sequences(tuple(sorted(skips.items()))) if discrimination_failures(q)]
+        if not bad:
+            return skips
+        skips[bad[0]] = skips.get(bad[0], 0) + 1
+
+
+# ---- what the table must be able to tell ----------------------------------------------------------------------------------------------
+def replay(q, keep_masks_at=None):
+    """[(op, what it observes)] and the final state"""
+    sim = Sim(q.setup, q.seed, keep_masks_at)
+    seen = [(op, sim.apply(op)) for op in q.ops]
+    return sim, seen
+
+
+def _observations(q, keep_masks_at=None):
+    """(op index, array, index of the step that wrote it) of every whole-field observation — numpy(), Macroscopic, the final comparison"""
+    sim, seen = replay(q, keep_masks_at)
+    obs = []
+    for i, (op, exp) in enumerate(seen):
+        if exp and op[0] in ("numpy", "macro"):
+            obs.append((i, exp["value"] if op[0] == "numpy" else exp["u"], exp["stamp"]))
+    for fin in sim.final():
+        for slot, stamp in zip(("cur", "oth"), fin["stamps"]):
+            if fin[slot] is not None:
+                obs.append((len(q.ops), fin[slot], stamp))
+    return obs
+
+
+def discrimination_failures(q):
+    """why the sequence could not tell a wrong implementation from a right one ([] when it can): a mask edit after which the next observed
+    field that a later step wrote is the same under the old masks; a write that changes nothing; a plan option that changes no plan"""
+    bad = []
+    base = _observations(q)
+    sim = Sim(q.setup, q.seed)
+    for i, op in enumerate(q.ops):
+        kind = op[0]
+        if kind in ("mask_assign", "mask_new"):
+            other = _observations(q, keep_masks_at=i)
+            later = [(a, b) for (ia, a, sa), (ib, b, sb) in zip(base, other) if ia > i and sa > i]
+            if len(base) != len(other) or not later or np.array_equal(*later[0]):
+                bad.append((i, op, "the next observed field is the same under the old masks"))
+        before = dict(sim.pops)
+        if kind == "option" and op[1] in ("fuse2_xseg", "fuse2_clean", "fuse2_strips", "overlap") and not _plan_changes(sim, op[1], op[2]):
+            bad.append((i, op, "the restated plan does not change"))
+        sim.apply(op)
+        if OP_CLASS[kind] == "writes" and kind != "touch":
+            f = sim.G.oth if kind in ("copy_from", "stream") else getattr(sim.G, op[1])
+            if before.get(f) is not None and np.array_equal(before[f], sim.pops[f]):
+                bad.append((i, op, "the write changes nothing"))
+    return bad
+
+
+def predicted_counts(q):
+    sim, _ = replay(q)
+    sim.final()
+    return dict(sim.n_fused), dict(sim.n_materialised)

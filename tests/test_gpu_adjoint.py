@@ -160,6 +160,37 @@ def test_native_backward_equals_chained_single_steps():
     assert adjoint.omega_gradient() == d_chained
 
 
+def test_masks_edited_in_place_between_two_sweeps():
+    """AdjointStepper keeps the gathered masks of its boundary cells, keyed on the masks' addresses and contents versions (adjoint.hip):
+    a sweep, both masks re-assigned IN PLACE to another variant (a solid cell of the walls' id inside the box), a second sweep through the
+    same objects — both equal the restatement with the masks of their moment; a cache that kept the first variant gives the first sweep twice."""
+    adjoint, forward, (f_0, f_1, bc_mask, missing_mask), (lat, obcs, bm, mm, f_np) = setup("cavity-halfway", "D3Q19", "FP32FP32", (35, 9, 6))
+    walls = obcs[1]
+    obcs_2 = [obcs[0], orc.BC(walls.kind, walls.id, np.concatenate([walls.indices, [[17], [4], [3]]], axis=1))]
+    bm_2, mm_2 = cases.masks((35, 9, 6), lat, obcs_2)
+    assert not np.array_equal(bm, bm_2) and not np.array_equal(mm, mm_2)
+    lam_np = np.random.default_rng(3).uniform(-1, 1, f_np.shape).astype(np.float32)
+    states_np, _ = ref.forward_states(f_np, bm, mm, obcs, OMEGA, lat, 3, "FP32FP32")
+    states = []
+    for s in states_np:
+        states.append(adjoint.create_cotangent())
+        states[-1].assign(s)
+    a, b = adjoint.create_cotangent(), adjoint.create_cotangent()
+    expected = []
+    for o_bm, o_mm in ((bm, mm), (bm_2, mm_2), (bm, mm)):
+        bc_mask.assign(o_bm)
+        missing_mask.assign(o_mm.astype(np.uint8))
+        a.assign(lam_np)
+        adjoint.reset()
+        lam_0, _ = adjoint.backward(states, a, b, bc_mask, missing_mask, OMEGA)
+        exp, terms = ref.backward(states_np, lam_np, o_bm, o_mm, obcs, OMEGA, lat, "FP32FP32")
+        assert_same_bits(lam_0.numpy(), exp, f"sweep {len(expected)}")
+        exact, bound = omega_bound(terms)
+        assert abs(adjoint.omega_gradient() - exact) <= bound
+        expected.append(exp)
+    assert not np.array_equal(expected[0], expected[1]), "the two variants give the same cotangent: the test could not tell"
+
+
 def test_sweep_over_rows_of_two_blocks_the_second_part_empty():
     """(3, 320) in two dimensions: a row of 320 cells is two blocks of 192 threads (160 rounded up to whole waves), the second holding
     128 cells, and the three rows make six per-block partial sums of the omega terms per launch"""

@@ -125,6 +125,50 @@ def test_editing_the_masks_flushes_the_deferred_step():
     assert np.array_equal(f_1.numpy(), orc.run(f_np, o_bm, o_mm, obcs, 1.2, lat, 1))
 
 
+def test_editing_or_freeing_the_masks_materialises_the_virtual_field_first():
+    """After a fused pair one field holds f(t+1) only virtually: that step was issued with the masks as they were.  Re-assigning the
+    masks (another variant: a solid cell of the walls' id inside the box) or freeing them before the field is read must run it first —
+    once it computed f(t+1) with the edited masks (found by tests/test_gpu_stepper_sequences.py)."""
+    stepper, (a, b, bm, mm), lat, obcs, f_np, o_bm, o_mm = setup()
+    walls = obcs[1]
+    bm_2, mm_2 = orc.build_masks(SHAPE, lat, [obcs[0], orc.BC(walls.kind, walls.id, np.concatenate([walls.indices, [[6], [7], [30]]], axis=1))])
+    exp1 = orc.run(f_np, o_bm, o_mm, obcs, 1.2, lat, 1)
+    exp2 = orc.run(exp1, o_bm, o_mm, obcs, 1.2, lat, 1)
+    assert not np.array_equal(exp1, orc.run(f_np, bm_2, mm_2, obcs, 1.2, lat, 1))  # (the edited masks would show)
+    stepper(a, b, bm, mm, 1.2, 0)
+    stepper(b, a, bm, mm, 1.2, 1)  # fused: b holds f(t+1) virtually
+    assert stepper._n_fused_pairs == 1 and stepper._n_materialised == 0
+    bm.assign(bm_2)
+    assert stepper._n_materialised == 1  # the first use of either mask
+    mm.assign(mm_2.astype(np.uint8))
+    assert np.array_equal(b.numpy(), exp1) and np.array_equal(a.numpy(), exp2) and stepper._n_materialised == 1
+    stepper(a, b, bm, mm, 1.2, 2)  # and the loop goes on under the new masks
+    assert np.array_equal(b.numpy(), orc.run(exp2, bm_2, mm_2, obcs, 1.2, lat, 1))
+    # freed masks: the owed step runs while they still exist
+    stepper2, (c, d, bm2, mm2), *_ = setup()
+    stepper2(c, d, bm2, mm2, 1.2, 0)
+    stepper2(d, c, bm2, mm2, 1.2, 1)
+    mm2.free()
+    bm2.free()
+    assert stepper2._n_materialised == 1 and np.array_equal(d.numpy(), exp1) and np.array_equal(c.numpy(), exp2)
+    # a field abandoned while virtual goes at once, with its device memory: the masks know it only weakly (no reference cycle that
+    # would wait for the cycle collector), and using them afterwards owes nothing
+    import gc
+    import weakref
+
+    stepper3, (e, g, bm3, mm3), _, _, _, o_bm3, _ = setup()  # (its BCs have ids of their own)
+    stepper3(e, g, bm3, mm3, 1.2, 0)
+    stepper3(g, e, bm3, mm3, 1.2, 1)
+    gone = weakref.ref(g)
+    gc.disable()
+    try:
+        del g
+        assert gone() is None
+    finally:
+        gc.enable()
+    assert np.array_equal(bm3.numpy(), o_bm3) and stepper3._n_materialised == 0 and np.array_equal(e.numpy(), exp2)
+
+
 def test_failed_materialisation_keeps_the_step_owed(monkeypatch):
     """reading the virtual f(t+1) allocates a temporary third field.  If that allocation fails the hook
     must stay: the next reader raises again (or succeeds once memory is back) — it is never handed f(t) for f(t+1)."""

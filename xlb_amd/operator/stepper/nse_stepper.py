@@ -21,7 +21,8 @@ population fields swapped (same masks, same omega) both steps run as one fused p
 field, ``ctx.sync()``, a different call — the deferred step runs first as a single step.  The results are bit-identical
 to single steps.  After a fused pair the field that received step t+1 in the reference's protocol holds it only virtually
 (the fused pass writes f(t+2) next to f(t), and the two field objects exchange their device buffers): if it is read
-before the next call overwrites it, it is materialised through a temporary third field.  Fields exported through DLPack /
+before the next call overwrites it, it is materialised through a temporary third field — also when one of the two masks is used
+first (edited, read, freed): the step that is owed was issued with the masks as they were.  Fields exported through DLPack /
 ``__cuda_array_interface__`` are never deferred (their memory must stay put); ``backend_config={"lazy_pairs": False}``
 switches the mechanism off.
 
@@ -64,14 +65,55 @@ def pairs_in_time(t_deferred, timestep, time_dependent):
 
 
 class _Materialise:
-    """Hook of a field that holds f(t+1) only virtually after a fused pair (its buffer holds f(t)): see _lazy_pair."""
+    """Hook of a field that holds f(t+1) only virtually after a fused pair (its buffer holds f(t)): see _lazy_pair.  The step that is
+    owed was issued with the masks as they were, so the two masks carry a hook of their own (_MasksOfVirtual) that leads here: whoever
+    uses a mask first — to edit it, to free it, to read it — makes the step run first.  References go one way only, field -> this hook
+    -> masks -> (weakly) field: a field abandoned while virtual is released at once, with its device memory, not by the cycle collector."""
 
-    def __init__(self, stepper, bcm, miss, omega, t):
+    def __init__(self, stepper, field, bcm, miss, omega, t):
         self.args = (stepper, bcm, miss, omega, t)
+        self.of_masks = _MasksOfVirtual(field)
+        for fld in (field, bcm, miss):
+            if fld is not None and fld._hook is not None:
+                fld.handle  # (whatever else is owed on it runs first; a pair has just used all three, so normally nothing is)
+        field._hook = self
+        self._hook_masks()
+
+    def _hook_masks(self):
+        for mask in self.args[1:3]:
+            if mask is not None and mask._hook is None:
+                mask._hook = self.of_masks
+
+    def drop(self, field):
+        """Nothing is owed any more (the step ran, or the field is about to be overwritten)."""
+        if field._hook is self:
+            field._hook = None
+        for mask in self.args[1:3]:
+            if mask is not None and mask._hook is self.of_masks:
+                mask._hook = None
 
     def __call__(self, field):
         stepper, bcm, miss, omega, t = self.args
-        stepper._materialise(field, bcm, miss, omega, t)
+        self.drop(field)
+        try:
+            stepper._materialise(field, bcm, miss, omega, t)
+        except BaseException:
+            self._hook_masks()  # still owed, whichever of the three is used next (Field.handle puts the field's hook back)
+            raise
+
+
+class _MasksOfVirtual:
+    """Hook of the two masks while a field is virtual (_Materialise): using a mask uses that field first."""
+
+    def __init__(self, field):
+        import weakref
+
+        self.field = weakref.ref(field)
+
+    def __call__(self, _mask):
+        field = self.field()
+        if field is not None and isinstance(field._hook, _Materialise) and field._hook.of_masks is self:
+            field.handle
 
 
 class IncompressibleNavierStokesStepper(Stepper):
@@ -280,7 +322,7 @@ class IncompressibleNavierStokesStepper(Stepper):
     def _lazy_pair(self, f_0, f_1, bc_mask, missing_mask, omega, timestep):
         """True when this call was absorbed (deferred, or executed as the second half of a fused pair)."""
         if isinstance(f_1._hook, _Materialise):
-            f_1._hook = None  # a virtual f(t+1) in the destination is about to be overwritten: nothing to materialise
+            f_1._hook.drop(f_1)  # a virtual f(t+1) in the destination is about to be overwritten: nothing to materialise
         d = self._deferred
         if d is not None:
             f_src, f_dst, bcm, miss, om, t = d
@@ -299,7 +341,7 @@ class IncompressibleNavierStokesStepper(Stepper):
                 # the reference's protocol leaves f(t+2) in THIS call's f_1 (= f_src) and f(t+1) in its f_0 (= f_dst):
                 # exchange the buffers; f_dst now holds f(t) instead of f(t+1) until someone looks
                 f_src._h, f_dst._h = f_dst._h, f_src._h
-                f_dst._hook = _Materialise(self, bcm, miss, om, t)
+                _Materialise(self, f_dst, bcm, miss, om, t)  # (hooks f_dst and both masks: an edited mask must not reach that step)
                 return True
             self._flush_deferred()
         if not self._lazy_eligible(f_0, f_1, bc_mask, missing_mask):
@@ -322,7 +364,7 @@ class IncompressibleNavierStokesStepper(Stepper):
         """The first of n >= 1 steps overwrites f_1 entirely: a virtual f(t+1) in it (left by a fused pair of reference-style
         calls) needs no materialisation — which would allocate a third field and run an extra step for nothing."""
         if n_steps >= 1 and isinstance(f_1._hook, _Materialise):
-            f_1._hook = None
+            f_1._hook.drop(f_1)
 
     def run(self, f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep=0):
         """``n_steps`` x (step, swap) in native code; returns (f_current, f_other)."""
