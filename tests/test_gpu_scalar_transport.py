@@ -182,8 +182,9 @@ def test_walled_cases_match_the_restatement(name, build, shape, lattice, coll, p
     run_walled(build, lattice, coll, policy, shape, steps=5)
 
 
-@pytest.mark.parametrize("vec,nz", [(2, 6), (4, 8), (4, 6)])
+@pytest.mark.parametrize("vec,nz", [(2, 6), (4, 8), (4, 6), (4, 12), (4, 4)])
 def test_walled_box_with_several_cells_per_thread(vec, nz):
+    # (4, 6) falls back to one cell per thread; (4, 12) has a thread at neither row end, (4, 4) one thread holding both
     run_walled(heated_box, "D3Q19", "BGK", "FP32FP32", (7, 6, nz), steps=4, vec=vec)
 
 

@@ -14,7 +14,7 @@
 //   IN_MU,     OUT_LAMBDA  the end of a sweep: lam_0 from mu_0, no forward state
 // Every OUT_MU launch also leaves one fp64 partial sum of the cells' omega terms per block (fixed order: see block_sum_fixed).
 //
-// Addressing is k_step's (step_kernel.hpp) with one cell per thread: x is block-uniform, lanes run along z.
+// Addressing is the row front end's (row_kernel.hpp) with one cell per thread.
 #pragma once
 #include "adjoint_kernels.hpp"
 #include "step_kernel.hpp"
@@ -54,40 +54,21 @@ __device__ __forceinline__ double block_sum_fixed(double v) {
 template <class L, class T, class S, int IN, int OUT, int HASBC>
 __global__ void __launch_bounds__(ADJ_BLOCK) k_adjoint_step(const AdjointArgs<T, S> aa) {
   constexpr int Q = L::Q;
-  constexpr unsigned ES = sizeof(S);
   const StepArgs<T, S>& a = aa.f;
-  const int ny = a.ny, nz = a.nz;
-  int z = blockIdx.x * blockDim.x + threadIdx.x;
-  int y = blockIdx.y * blockDim.y + threadIdx.y;
-  const bool active = z < nz && y < ny;  // (idle threads stay for the block sum; they load cell (y, z) = (0, 0) and store nothing)
-  if (!active) {
-    z = 0;
-    y = 0;
-  }
-  const int x = blockIdx.z;  // block-uniform
-
-  // x-plane, row and column of the cell's neighbours at offset -1, 0, +1 (index offset + 1): the forward pull of direction l reads
-  // offset -c_l, the transposed streaming gathers from offset +c_l
-  int Xn[3];
-  Xn[0] = (x == 0) ? a.nx - 1 : x - 1;
-  Xn[1] = x;
-  Xn[2] = (x + 1 == a.nx) ? 0 : x + 1;
-  const size_t plane_cells = (size_t)ny * nz;
-  unsigned Yn[3], Zn[3];  // elements
-  Yn[0] = (unsigned)((y == 0) ? ny - 1 : y - 1) * (unsigned)nz;
-  Yn[1] = (unsigned)y * (unsigned)nz;
-  Yn[2] = (unsigned)((y + 1 == ny) ? 0 : y + 1) * (unsigned)nz;
-  Zn[0] = (unsigned)((z == 0) ? nz - 1 : z - 1);
-  Zn[1] = (unsigned)z;
-  Zn[2] = (unsigned)((z + 1 == nz) ? 0 : z + 1);
-  const unsigned cell = Yn[1] + Zn[1];  // own cell in its x-plane, elements (< 2^28)
+  RowCell r;
+  // (idle threads stay for the block sum; they load cell (y, z) = (0, 0) and store nothing)
+  const bool active = row_cell_of_thread<1>(a, blockIdx.x, blockIdx.y, 0, r);
+  const size_t xplane = (size_t)r.Xs[1] * r.plane_cells;  // the thread's own x plane; uniform
+  const unsigned cell = r.cell_in_plane;
 
   unsigned id = 0u, kind = K_NONE, m = 0u;
   if constexpr (HASBC != 0) {
-    id = ld(a.bc + (size_t)x * plane_cells, cell);
-    if (id != 0u) {
+    unsigned ids[1];
+    const bool any_bc = load_bc_ids<1>(a.bc + xplane, cell, ids);
+    id = ids[0];
+    if (any_bc) {
       kind = kind_of(a, id);
-      m = ld(a.miss + (size_t)x * plane_cells, opaque(cell * 4u));
+      m = ld(a.miss + xplane, opaque(cell * 4u));
     }
   }
 
@@ -95,18 +76,17 @@ __global__ void __launch_bounds__(ADJ_BLOCK) k_adjoint_step(const AdjointArgs<T,
   if constexpr (IN == ADJ_IN_LAMBDA) {
     static_for<Q>([&](auto lc) {
       constexpr int l = decltype(lc)::value;
-      lam[l] = to_compute<T, S>(ld(aa.in + (size_t)l * aa.in_stride + (size_t)x * plane_cells, cell * ES));
+      lam[l] = to_compute<T, S>(ld(aa.in + (size_t)l * aa.in_stride + xplane, cell * (unsigned)sizeof(S)));
     });
   } else {
     // ---- transposed streaming: lam_n[l] = mu[l](cell + c_l) unless that cell replaced its pull of l, + the own redirected mu ----
     unsigned gbits = 0u;
-    if constexpr (HASBC != 0) gbits = ld(aa.gmask + (size_t)x * plane_cells, cell * 4u);
+    if constexpr (HASBC != 0) gbits = ld(aa.gmask + xplane, cell * 4u);
     static_for<Q>([&](auto lc) {
       constexpr int l = decltype(lc)::value;
-      constexpr int cx = L::c(0, l), cy = L::c(1, l), cz = L::c(2, l);
-      const unsigned n = Yn[cy + 1] + Zn[cz + 1];
-      const S* row = aa.in + (size_t)l * aa.in_stride + (size_t)Xn[cx + 1] * plane_cells;  // uniform
-      T v = to_compute<T, S>(ld(row, n * ES));
+      S w[1];
+      pull_plane<L, opp<L>(l)>(aa.in + (size_t)l * aa.in_stride, r, w);  // the value at cell + c_l
+      T v = to_compute<T, S>(w[0]);
       if constexpr (HASBC != 0) {
         if ((gbits >> l) & 1u) v = T(0);  // the cell there replaced its pull of l by its rule
       }
@@ -115,11 +95,7 @@ __global__ void __launch_bounds__(ADJ_BLOCK) k_adjoint_step(const AdjointArgs<T,
     if constexpr (HASBC != 0) {
       if (kind == K_HW || kind == K_DN) {
         T own[Q];
-        const unsigned cb = opaque(cell * ES);
-        static_for<Q>([&](auto lc) {
-          constexpr int l = decltype(lc)::value;
-          own[l] = to_compute<T, S>(ld(aa.in + (size_t)l * aa.in_stride + (size_t)x * plane_cells, cb));
-        });
+        load_own_cell<L, false>(aa.in, aa.in_stride, xplane, cell, own);
         adjoint_own_terms<L, T>(kind, m, own, lam);
       }
     }
@@ -137,19 +113,15 @@ __global__ void __launch_bounds__(ADJ_BLOCK) k_adjoint_step(const AdjointArgs<T,
     T fs[Q];
     static_for<Q>([&](auto lc) {
       constexpr int l = decltype(lc)::value;
-      constexpr int cx = L::c(0, l), cy = L::c(1, l), cz = L::c(2, l);
-      const S* row = a.src + (size_t)l * a.plane_stride + (size_t)Xn[1 - cx] * plane_cells;  // uniform
-      fs[l] = to_compute<T, S>(ld(row, (Yn[1 - cy] + Zn[1 - cz]) * ES));
+      S w[1];
+      pull_plane<L, l>(a.src + (size_t)l * a.plane_stride, r, w);
+      fs[l] = to_compute<T, S>(w[0]);
     });
     if constexpr (HASBC != 0) {
       if (kind == K_EQ || kind == K_HW || kind == K_DN) {
         const T* val = opaque(a.bc_values + id * 27u);
         T pre[Q];
-        const unsigned cb = opaque(cell * ES);
-        static_for<Q>([&](auto lc) {
-          constexpr int l = decltype(lc)::value;
-          pre[l] = to_compute<T, S>(ld(a.src + (size_t)l * a.plane_stride + (size_t)x * plane_cells, cb));
-        });
+        load_own_cell<L, false>(a.src, a.plane_stride, xplane, cell, pre);
         const T none[5] = {T(0), T(0), T(0), T(0), T(0)};
         // (a constant kind per call: the rules of the kinds the adjoint does not cover fold away)
         if (kind == K_EQ)
@@ -163,14 +135,7 @@ __global__ void __launch_bounds__(ADJ_BLOCK) k_adjoint_step(const AdjointArgs<T,
     term = adjoint_local_cell<L, T>(kind, fs, lam, a.omega);
   }
 
-  if (active) {
-    static_for<Q>([&](auto lc) {
-      constexpr int l = decltype(lc)::value;
-      S* drow = aa.out + (size_t)l * aa.out_stride + (size_t)x * plane_cells;  // uniform
-      const S v[1] = {to_store<S, T>(lam[l])};
-      st_aligned<S, 1, true>(drow, cell * ES, v);
-    });
-  }
+  if (active) store_planes<true, 1, Q>(aa.out, aa.out_stride, xplane, cell, lam);
 
   if constexpr (OUT == ADJ_OUT_MU) {
     // (after the stores, so that they do not wait for the block's barriers)

@@ -1,17 +1,18 @@
 // The row kernels of the Shan-Chen step.  The interaction force at cell x needs psi = Psi(rho) of the post-streaming state at the
 // neighbours of x, whose streaming is not known inside the same launch, so one step is TWO launches on one stream:
 //   k_psi              pull + streaming rules -> rho -> psi, stored in the compute dtype (one value per cell)
-//   k_step_multiphase  pull + streaming rules again -> rho, u; the neighbours' psi by the row scheme of pull_dir; force; forced BGK;
+//   k_step_multiphase  pull + streaming rules again -> rho, u; the neighbours' psi by pull_plane; force; forced BGK;
 //                      q non-temporal stores
 // and k_multiphase_out is the second launch storing rho, the physical velocity and / or the force instead of colliding.  Per cell
 // (3 q) s + 2 s_c bytes (s, s_c: store and compute element), D3Q19 fp32: 236 B against the fluid step's 152 B.  Fusing the two would
 // mean taking psi from the previous step's density (a lagged force): another scheme, not built.
 //
-// All three share ONE front half (mp_front: addressing, lane mapping and row-end handling of k_step, the rule functions of cell.hpp),
-// so that the rho behind psi is the step's rho bit for bit.  One cell per thread.  k_step itself is untouched.
+// All three share ONE front half (mp_front: the row front end of row_kernel.hpp, the rule functions of cell.hpp), so that the rho behind
+// psi is the step's rho bit for bit.  One cell per thread.
 #pragma once
 #include "multiphase_kernels.hpp"
-#include "scalar_step_kernel.hpp"
+#include "row_kernel.hpp"
+#include "step_kernel.hpp"
 
 namespace xlb {
 
@@ -27,44 +28,6 @@ struct MultiphaseArgs {
   size_t u_stride, force_stride;
 };
 
-// where a thread's cell sits: the x planes (uniform) and the rows of its neighbourhood in elements
-struct RowCell {
-  int Xs[3];          // storage x plane for c_x = -1, 0, +1 (index c_x + 1)
-  unsigned Ye[3];     // first element of the y-neighbour rows inside an x plane (index c_y + 1)
-  int z, nz;
-  size_t plane_cells;
-  unsigned cell_in_plane;  // elements, < 2^28
-};
-
-template <class T, class S>
-__device__ __forceinline__ bool mp_cell_of_thread(const StepArgs<T, S>& a, RowCell& r) {
-  const int z = blockIdx.x * blockDim.x + threadIdx.x;
-  const int y = blockIdx.y * blockDim.y + threadIdx.y;
-  if (z >= a.nz || y >= a.ny) return false;
-  const int x = a.x_begin + blockIdx.z;  // block-uniform
-  r.Xs[0] = (x + 1 == a.nx) ? 0 : x + 1;
-  r.Xs[1] = x;
-  r.Xs[2] = (x == 0) ? a.nx - 1 : x - 1;
-  r.Ye[0] = (unsigned)((y + 1 == a.ny) ? 0 : y + 1) * (unsigned)a.nz;
-  r.Ye[1] = (unsigned)y * (unsigned)a.nz;
-  r.Ye[2] = (unsigned)((y == 0) ? a.ny - 1 : y - 1) * (unsigned)a.nz;
-  r.z = z;
-  r.nz = a.nz;
-  r.plane_cells = (size_t)a.ny * a.nz;
-  r.cell_in_plane = r.Ye[1] + (unsigned)z;
-  return true;
-}
-
-// the value arriving along direction l (from x - c_l) of one plane-major field `base` of element type E
-template <class L, class E, int l>
-__device__ __forceinline__ E mp_pull(const E* base, const RowCell& r) {
-  constexpr int cx = L::c(0, l), cy = L::c(1, l), cz = L::c(2, l);
-  const E* row = base + (size_t)r.Xs[cx + 1] * r.plane_cells;  // uniform
-  E v[1];
-  pull_dir<E, 1, cz>(row, r.Ye[cy + 1] * (unsigned)sizeof(E), (unsigned)r.z * (unsigned)sizeof(E), r.z, r.nz, false, false, v);
-  return v[0];
-}
-
 // The front half: the post-streaming populations of the cell after the streaming-step rules.  id: the cell's bc id (0 without
 // boundary conditions), m: its missing bits (0 when id == 0), fullway: a fullway bounce-back cell.
 // HASBC: 0 = no boundary conditions, 1 = halfway (constant wall velocity) and fullway bounce-back, solid cells.
@@ -73,26 +36,25 @@ __device__ __forceinline__ void mp_front(const StepArgs<T, S>& a, const RowCell&
   constexpr int Q = L::Q;
   static_for<Q>([&](auto lc) {
     constexpr int l = decltype(lc)::value;
-    f[l] = to_compute<T, S>(mp_pull<L, S, l>(a.src + (size_t)l * a.plane_stride, r));
+    S v[1];
+    pull_plane<L, l>(a.src + (size_t)l * a.plane_stride, r, v);
+    f[l] = to_compute<T, S>(v[0]);
   });
   id = 0u;
   m = 0u;
   fullway = false;
   if constexpr (HASBC != 0) {
-    id = ld(a.bc + (size_t)r.Xs[1] * r.plane_cells, r.cell_in_plane);
-    if (id != 0u) {
+    unsigned ids[1];
+    const bool any_bc = load_bc_ids<1>(a.bc + (size_t)r.Xs[1] * r.plane_cells, r.cell_in_plane, ids);
+    id = ids[0];
+    if (any_bc) {
       // rare path: the missing bits of every boundary cell (the force needs them too)
       const unsigned kind = kind_of(a, id);
       m = ld(a.miss + (size_t)r.Xs[1] * r.plane_cells, opaque(r.cell_in_plane * 4u));
       if (kind == K_HW) {
         const T* val = opaque(a.bc_values + id * 27u);
-        const unsigned cb = opaque(r.cell_in_plane * (unsigned)sizeof(S));
         T pre[Q];
-        static_for<Q>([&](auto lc) {
-          constexpr int l = decltype(lc)::value;
-          const S* own = a.src + (size_t)l * a.plane_stride + (size_t)r.Xs[1] * r.plane_cells;  // uniform
-          pre[l] = to_compute<T, S>(ld(own, cb));
-        });
+        load_own_cell<L, false>(a.src, a.plane_stride, (size_t)r.Xs[1] * r.plane_cells, r.cell_in_plane, pre);
         const T uw[5] = {T(0), T(0), T(0), T(0), T(0)};
         apply_streaming_bc<L, T>(XLBHIP_BC_HALFWAY_BB, f, pre, m, val, uw, nullptr);
       } else if (kind == K_FW) {
@@ -109,7 +71,7 @@ template <class L, class T, class S, int HASBC>
 __global__ void __launch_bounds__(256) k_psi(const MultiphaseArgs<T, S> ma) {
   const StepArgs<T, S>& a = ma.f;
   RowCell r;
-  if (!mp_cell_of_thread(a, r)) return;
+  if (!row_cell_of_thread<1>(a, blockIdx.x, blockIdx.y, 0, r)) return;
   T f[L::Q];
   unsigned id, m;
   bool fullway;
@@ -136,7 +98,9 @@ __device__ __forceinline__ void mp_force_of_cell(const MultiphaseArgs<T, S>& ma,
   nb[0] = T(0);
   static_for<L::Q - 1>([&](auto ic) {
     constexpr int i = decltype(ic)::value + 1;
-    nb[i] = mp_pull<L, T, opp<L>(i)>(ma.psi, r);
+    T v[1];
+    pull_plane<L, opp<L>(i)>(ma.psi, r, v);
+    nb[i] = v[0];
   });
   const T psi = ld(ma.psi + (size_t)r.Xs[1] * r.plane_cells, r.cell_in_plane * (unsigned)sizeof(T));
   T pw = T(0);
@@ -152,24 +116,19 @@ template <class L, class T, class S, int HASBC>
 __global__ void __launch_bounds__(256) k_step_multiphase(const MultiphaseArgs<T, S> ma) {
   const StepArgs<T, S>& a = ma.f;
   RowCell r;
-  if (!mp_cell_of_thread(a, r)) return;
+  if (!row_cell_of_thread<1>(a, blockIdx.x, blockIdx.y, 0, r)) return;
   T f[L::Q], rho, u[3], F[3];
   bool fullway;
   mp_force_of_cell<L, T, S, HASBC>(ma, r, f, fullway, rho, u, F);
   multiphase_collide_cell<L, T>(f, fullway, a.omega, rho, F, ma.model);
-  static_for<L::Q>([&](auto lc) {
-    constexpr int l = decltype(lc)::value;
-    S* drow = a.dst + (size_t)l * a.plane_stride + (size_t)r.Xs[1] * r.plane_cells;  // uniform
-    const S v[1] = {to_store<S, T>(f[l])};
-    st_aligned<S, 1, true>(drow, r.cell_in_plane * (unsigned)sizeof(S), v);
-  });
+  store_planes<true, 1, L::Q>(a.dst, a.plane_stride, (size_t)r.Xs[1] * r.plane_cells, r.cell_in_plane, f);
 }
 
 // rho, u = u_bare + F / (2 rho) and F (the lattice's d components each) of the post-streaming state
 template <class L, class T, class S, int HASBC>
 __global__ void __launch_bounds__(256) k_multiphase_out(const MultiphaseArgs<T, S> ma) {
   RowCell r;
-  if (!mp_cell_of_thread(ma.f, r)) return;
+  if (!row_cell_of_thread<1>(ma.f, blockIdx.x, blockIdx.y, 0, r)) return;
   T f[L::Q], rho, u[3], F[3];
   bool fullway;
   mp_force_of_cell<L, T, S, HASBC>(ma, r, f, fullway, rho, u, F);

@@ -7,12 +7,10 @@
 //   * SoA populations (q, x, y, z), z fastest; a thread owns VEC consecutive z cells
 //     and keeps their q populations in registers, so moments/feq/collide need no
 //     cross-lane traffic at all.
-//   * every global access is `uniform base (SGPR pair) + 32-bit byte offset (VGPR)`: x is
-//     block-uniform (blockIdx.z), so the population-plane / x-plane part of each address is
-//     scalar arithmetic and the q loads share nine per-thread (y, z) neighbour offsets.
-//   * per direction ONE load per thread: aligned for c_z == 0, shifted by one element for
-//     c_z = +-1 (dword-aligned vector load when VEC > 1; the single wrapped element at a row
-//     end is patched by an exec-masked scalar load).
+//   * mapping, address form and row-end rule are the row kernels' (row_kernel.hpp): per direction ONE load
+//     per thread, and the q loads share nine per-thread (y, z) neighbour offsets.  The thread's cell
+//     description, the pull, the own-cell loads and the store are WRITTEN OUT below, in byte offsets: in this
+//     kernel the helpers cost some instantiation a wave per SIMD or scratch (profiles/row_front_end.md).
 //   * boundary cells are handled in-register on a slow path taken only by lanes whose
 //     bc_mask byte is non-zero; the id -> kind lookup is a scalar compare chain on kernel
 //     arguments (no dependent table load), and missing bits (one u32 per cell) and own-cell
@@ -20,6 +18,7 @@
 //   * stores are aligned (vector) stores, optionally non-temporal.
 #pragma once
 #include "cell.hpp"
+#include "row_kernel.hpp"
 #include "step2_plan.hpp"
 
 #ifndef XLB_LB1
@@ -69,75 +68,6 @@ struct StepArgs {
   T omega;
 };
 
-template <class S, int N>
-struct VecOf {
-  typedef S aligned __attribute__((ext_vector_type(N), aligned(sizeof(S) * N)));
-  typedef S shifted __attribute__((ext_vector_type(N), aligned(sizeof(S))));
-};
-
-// p = uniform base, boff = per-thread byte offset (32 bit) -> global_load ... v_off, s[base]
-template <class S>
-__device__ __forceinline__ S ld(const S* base, unsigned boff) {
-  return *reinterpret_cast<const S*>(reinterpret_cast<const char*>(base) + boff);
-}
-template <class S, int VEC, bool NT = false>
-__device__ __forceinline__ void ld_aligned(const S* base, unsigned boff, S (&out)[VEC]) {
-  if constexpr (VEC == 1) {
-    if constexpr (NT)
-      out[0] = __builtin_nontemporal_load(reinterpret_cast<const S*>(reinterpret_cast<const char*>(base) + boff));
-    else
-      out[0] = ld(base, boff);
-  } else {
-    typedef typename VecOf<S, VEC>::aligned V;
-    V v;
-    if constexpr (NT)
-      v = __builtin_nontemporal_load(reinterpret_cast<const V*>(reinterpret_cast<const char*>(base) + boff));
-    else
-      v = *reinterpret_cast<const V*>(reinterpret_cast<const char*>(base) + boff);
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) out[k] = v[k];
-  }
-}
-template <class S, int VEC>
-__device__ __forceinline__ void ld_shifted(const S* base, unsigned boff, S (&out)[VEC]) {
-  typedef typename VecOf<S, VEC>::shifted V;
-  const V v = *reinterpret_cast<const V*>(reinterpret_cast<const char*>(base) + boff);
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) out[k] = v[k];
-}
-template <class S, int VEC, bool NT>
-__device__ __forceinline__ void st_aligned(S* base, unsigned boff, const S (&in)[VEC]) {
-  char* p = reinterpret_cast<char*>(base) + boff;
-  if constexpr (VEC == 1) {
-    if constexpr (NT)
-      __builtin_nontemporal_store(in[0], reinterpret_cast<S*>(p));
-    else
-      *reinterpret_cast<S*>(p) = in[0];
-  } else {
-    typedef typename VecOf<S, VEC>::aligned V;
-    V v;
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) v[k] = in[k];
-    if constexpr (NT)
-      __builtin_nontemporal_store(v, reinterpret_cast<V*>(p));
-    else
-      *reinterpret_cast<V*>(p) = v;
-  }
-}
-
-// Identity the optimiser cannot see through.  The BC branches below issue loads that are
-// textually identical across branches (own-cell populations, per-BC constants); LLVM would hoist
-// them above the branch and keep ~40 extra VGPRs live in the fluid fast path.
-__device__ __forceinline__ unsigned opaque(unsigned v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-template <class P>
-__device__ __forceinline__ const P* opaque(const P* p) {
-  asm volatile("" : "+v"(p));
-  return p;
-}
-
 // scalar compare chain only (callers guarantee n_bc <= MAX_FAST_BCS): contains NO load, so it can sit in a
 // software-pipelined loop without making the compiler's vmcnt bookkeeping fall back to vmcnt(0)
 template <class T, class S>
@@ -177,6 +107,7 @@ __global__ void __launch_bounds__(VEC == 1 ? XLB_LB1 : 256) k_step(const StepArg
     by = grp * 8u + (r % 8u);
     bx = r / 8u;
   }
+  // (restates row_cell_of_thread, in bytes)
   const int zq = bx * blockDim.x + threadIdx.x;
   const int y = by * blockDim.y + threadIdx.y;
   if (zq >= a.nzq || y >= a.ny) return;
@@ -208,7 +139,7 @@ __global__ void __launch_bounds__(VEC == 1 ? XLB_LB1 : 256) k_step(const StepArg
 
   T f[VEC][Q];
 
-  // ---- pull streaming: f[k][l] = src[l, x - cx, y - cy, z0 + k - cz]  (stream.py:57-62) ----
+  // ---- pull streaming: f[k][l] = src[l, x - cx, y - cy, z0 + k - cz]  (stream.py:57-62); restates pull_plane / pull_dir ----
   static_for<Q>([&](auto lc) {
     constexpr int l = decltype(lc)::value;
     constexpr int cx = L::c(0, l), cy = L::c(1, l), cz = L::c(2, l);
@@ -248,26 +179,10 @@ __global__ void __launch_bounds__(VEC == 1 ? XLB_LB1 : 256) k_step(const StepArg
   });
 
   // ---- boundary ids of my VEC cells ----
-  const unsigned cell_in_plane = (unsigned)y * (unsigned)nz + (unsigned)z0;  // elements, < 2^30
+  const unsigned cell_in_plane = (unsigned)y * (unsigned)nz + (unsigned)z0;  // elements (bound: row_kernel.hpp)
   unsigned ids[VEC];
   bool any_bc = false;
-  if constexpr (HASBC != 0) {
-    const uint8_t* bcp = a.bc + (size_t)Xs[1] * plane_cells;  // uniform
-    if constexpr (VEC == 4) {
-      const unsigned wrd = ld(reinterpret_cast<const unsigned*>(bcp), cell_in_plane);
-      any_bc = wrd != 0u;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ids[k] = (wrd >> (8 * k)) & 0xffu;
-    } else if constexpr (VEC == 2) {
-      const unsigned wrd = ld(reinterpret_cast<const unsigned short*>(bcp), cell_in_plane);
-      any_bc = wrd != 0u;
-      ids[0] = wrd & 0xffu;
-      ids[1] = (wrd >> 8) & 0xffu;
-    } else {
-      ids[0] = ld(bcp, cell_in_plane);
-      any_bc = ids[0] != 0u;
-    }
-  }
+  if constexpr (HASBC != 0) any_bc = load_bc_ids<VEC>(a.bc + (size_t)Xs[1] * plane_cells, cell_in_plane, ids);
 
 #pragma unroll
   for (int k = 0; k < VEC; ++k) {
@@ -276,7 +191,7 @@ __global__ void __launch_bounds__(VEC == 1 ? XLB_LB1 : 256) k_step(const StepArg
       if (any_bc && ids[k] != 0u) {
         const unsigned id = ids[k];
         const unsigned kind = kind_of(a, id);
-        const unsigned cb = (cell_in_plane + (unsigned)k) * ES;  // own cell, byte offset in the x-plane
+        const unsigned cb = (cell_in_plane + (unsigned)k) * ES;  // own cell, byte offset in the x-plane (the own-cell loads below restate load_own_cell)
         if (kind == K_EQ) {
           // bc_equilibrium.py:75-80: f = feq(rho0, u0)
           const T* val = opaque(a.bc_values + id * 27u);
@@ -383,7 +298,7 @@ __global__ void __launch_bounds__(VEC == 1 ? XLB_LB1 : 256) k_step(const StepArg
     }
   }
 
-  // ---- store (cast to store precision, nse_stepper.py:280) ----
+  // ---- store (cast to store precision, nse_stepper.py:280); restates store_planes ----
   static_for<Q>([&](auto lc) {
     constexpr int l = decltype(lc)::value;
     S* drow = a.dst + (size_t)l * a.plane_stride + (size_t)Xs[1] * plane_cells;  // uniform
