@@ -2,7 +2,7 @@
 """The reference's 3-D lid-driven cavity benchmark loop (examples/performance/mlups_3d.py:193-242) on the HIP backend,
 UNCHANGED in structure: construct the BCs and the stepper, then `f_0, f_1 = stepper(f_0, f_1, ...)` + swap per step, with a
 device synchronisation before and after the timed loop.  The backend pairs consecutive calls into two-steps-per-pass kernel
-launches behind the scenes (xlb_amd/operator/stepper/nse_stepper.py), so this loop runs at the speed of `stepper.run`.
+launches behind the scenes (xlb_amd/operator/stepper/call_pairing.py), so this loop runs at the speed of `stepper.run`.
 
     python examples/cavity_3d_reference_loop_hip.py [n=256] [steps=200]
 """

@@ -5,7 +5,7 @@ through the public API and compares every read with the model, bit for bit.
 The stepper is the part whose answer depends on its history.  Natively it keeps caches (csrc/stepper.hip, the comment block above
 xlbhip_stepper: meta words, tile order, clean flags, the edge-kind scan, the scratch field, the fields' strip buffers, the profile ring);
 in Python it defers a reference-style call, fuses it with the next one, exchanges the two fields' buffers and leaves one field holding
-f(t+1) only virtually (operator/stepper/nse_stepper.py).  A stale cache or a step that runs too late gives fluid-looking numbers.
+f(t+1) only virtually (operator/stepper/call_pairing.py).  A stale cache or a step that runs too late gives fluid-looking numbers.
 
 The model (Sim) is eager and keyed by field object: a step is orc.run(state, bc_mask, missing_mask, bcs, omega, lattice, 1) with the
 masks as they are when the call is made; stepper(a, b, ...) means b := step(a); run(a, b, ..., n) returns (cur, oth) with
@@ -291,7 +291,7 @@ class Sim:
         g = self.g if g is None else g
         return self.s.lattice == "D3Q19" and self.options["fuse2"] == 2 and setup_masks(self.s, g)[2][self.grids[g].variant].fuses
 
-    # -- restated hooks (Field.handle, nse_stepper.py _lazy_pair / _flush_deferred / _materialise)
+    # -- restated hooks (_lib.HookedBuffer.handle, call_pairing.py CallPairing.call / flush_deferred / _materialise)
     def _use(self, *objs):
         for o in objs:
             h = self.hooks.pop(o, None)
@@ -337,9 +337,9 @@ class Sim:
         self.stale[dst] = False
 
     def _call(self, k, f0, f1, omega):
-        """hip_implementation / _lazy_pair of stepper k, contents aside"""
+        """hip_implementation / CallPairing.call of stepper k, contents aside"""
         G = self.G
-        in_time = lambda d: not time_dependent(self.s) or G.t == d["t"] + 1  # noqa: E731 (nse_stepper.py pairs_in_time)
+        in_time = lambda d: not time_dependent(self.s) or G.t == d["t"] + 1  # noqa: E731 (call_pairing.py pairs_in_time)
         bm, mm = self._mask_objs()
         self._drop_virtual(f1)
         d = self.deferred[k]

@@ -181,8 +181,6 @@ def test_sequence(q):
         play(q, steppers, devs, ctx)
     finally:
         for st in steppers:  # a sequence that failed half way must not leave its deferred step to the next test's ctx.sync()
-            if st._deferred is not None:
-                st._unhook(*st._deferred[:4])
-                st._deferred = None
+            st.abandon_deferred()
         for key, value in sq.OPTION_DEFAULTS.items():
             ctx.set_option(key, value)

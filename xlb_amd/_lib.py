@@ -8,6 +8,7 @@ missing or a call fails, an exception is raised.
 
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -207,31 +208,40 @@ def lattice_info(lattice_id):
     return d.value, qq, c, w[:qq].copy(), opp[:qq].copy(), cc
 
 
-class Context:
+class DeferredWork:
+    """Who has device work deferred (no library needed: a host test derives its stand-in context from this).  Weak references to
+    objects with a ``flush_deferred()`` — operator/stepper/call_pairing.py registers itself when it defers a reference-style call."""
+
+    def __init__(self):
+        self._flushers = []
+
+    def defers_work(self, obj):
+        if not any(ref() is obj for ref in self._flushers):
+            self._flushers.append(weakref.ref(obj))
+
+    def flush_deferred(self):
+        """Enqueue whatever work operators have deferred; forget those that are gone."""
+        alive = [obj for obj in (ref() for ref in self._flushers) if obj is not None]
+        self._flushers = [weakref.ref(obj) for obj in alive]
+        for obj in alive:
+            obj.flush_deferred()
+
+
+class Context(DeferredWork):
     """Device context: HIP device + compute/communication streams (xlbhip_create)."""
 
     def __init__(self, device=0):
+        super().__init__()
         self._h = _p()
         check(load().xlbhip_create(int(device), C.byref(self._h)))
         self.device = int(device)
         self.rank, self.n_ranks = 0, 1
-        self._flushers = []  # weak references to objects with deferred device work (steppers pairing reference-style calls)
 
     @property
     def handle(self):
         if not self._h:
             raise HipBackendError("context already destroyed")
         return self._h
-
-    def flush_deferred(self):
-        """Enqueue whatever work operators have deferred (IncompressibleNavierStokesStepper pairs reference-style calls)."""
-        alive = []
-        for ref in self._flushers:
-            obj = ref()
-            if obj is not None:
-                obj._flush_deferred()
-                alive.append(ref)
-        self._flushers = alive
 
     def sync(self):
         self.flush_deferred()
@@ -352,33 +362,15 @@ def _dlpack_capsule(owner, ptr, shape, strides, dtype, device_id):
     return _PyCapsule_New(C.addressof(m), b"dltensor", C.cast(_dl_capsule_destructor, C.c_void_p))
 
 
-class Field:
-    """A device-resident field.  Host-visible shape is (cardinality, nx, ny[, nz]) C-order,
-    exactly the reference layout; the device layout is private (DESIGN.md)."""
+class HookedBuffer:
+    """The part of a field that needs no library: a buffer handle and the hook rule (a host test derives its stand-in fields from
+    this).  Whoever has deferred work that involves the field hooks it; every access goes through ``.handle``, which runs the hook
+    first.  A subclass says in ``_release`` how the buffer is given back."""
 
-    def __init__(self, ctx, cardinality, shape, dtype_code, halo=0, fill_value=0.0):
-        self.ctx = ctx
-        self.cardinality = int(cardinality)
-        self.grid_shape = tuple(int(s) for s in shape)
-        assert len(self.grid_shape) in (2, 3)
-        self.dtype_code = int(dtype_code)
-        self.halo = int(halo)
-        s3 = (1,) + self.grid_shape if len(self.grid_shape) == 2 else self.grid_shape
-        self._s3 = s3
+    def __init__(self, handle):
         self._hook = None     # called before any access through .handle (deferred work that involves this field)
         self._pinned = False  # exported through DLPack / CUDA array interface: its device memory must never be swapped
-        self._h = _p()
-        check(load().xlbhip_field_create(ctx.handle, self.cardinality, s3[0], s3[1], s3[2], self.dtype_code, self.halo,
-                                         float(fill_value or 0.0), C.byref(self._h)))
-
-    # -- reference-like attributes
-    @property
-    def shape(self):
-        return (self.cardinality,) + self.grid_shape
-
-    @property
-    def dtype(self):
-        return np.dtype(NP_OF_DTYPE[self.dtype_code])
+        self._h = handle
 
     @property
     def handle(self):
@@ -395,6 +387,63 @@ class Field:
         if not self._h:
             raise HipBackendError("field already destroyed")
         return self._h
+
+    hook = property(lambda self: self._hook)
+
+    def hook_with(self, hook):
+        self._hook = hook
+
+    def unhook(self, only=None):
+        """Nothing is owed on this field any more; with `only`, unless another hook has taken that one's place."""
+        if only is None or self._hook is only:
+            self._hook = None
+
+    def exchange_buffers(self, other):
+        """The two objects trade what they hold (a fused pair leaves its result next to the source; a virtual field adopts its temporary)."""
+        self._h, other._h = other._h, self._h
+
+    def free(self):
+        if self._hook is not None:  # what is owed runs while the buffer still exists (a freed mask: the step issued with it)
+            hook, self._hook = self._hook, None
+            try:
+                hook(self)
+            except Exception:
+                pass
+        self._release()
+
+    def __del__(self):
+        try:
+            self._hook = None  # an abandoned field owes nothing: nobody can look at it
+            self._release()
+        except Exception:
+            pass
+
+
+class Field(HookedBuffer):
+    """A device-resident field.  Host-visible shape is (cardinality, nx, ny[, nz]) C-order,
+    exactly the reference layout; the device layout is private (DESIGN.md)."""
+
+    def __init__(self, ctx, cardinality, shape, dtype_code, halo=0, fill_value=0.0):
+        super().__init__(_p())
+        self.ctx = ctx
+        self.cardinality = int(cardinality)
+        self.grid_shape = tuple(int(s) for s in shape)
+        assert len(self.grid_shape) in (2, 3)
+        self.dtype_code = int(dtype_code)
+        self.halo = int(halo)
+        s3 = (1,) + self.grid_shape if len(self.grid_shape) == 2 else self.grid_shape
+        self._s3 = s3
+        check(load().xlbhip_field_create(ctx.handle, self.cardinality, s3[0], s3[1], s3[2], self.dtype_code, self.halo,
+                                         float(fill_value or 0.0), C.byref(self._h)))
+
+    # -- reference-like attributes
+    @property
+    def shape(self):
+        return (self.cardinality,) + self.grid_shape
+
+    @property
+    def dtype(self):
+        return np.dtype(NP_OF_DTYPE[self.dtype_code])
 
     def touch(self):
         """The contents changed behind the library's back (a write through a zero-copy alias): invalidate what is cached on them."""
@@ -502,25 +551,10 @@ class Field:
         return {"cardinality": card.value, "nx": nx.value, "ny": ny.value, "nz": nz.value, "dtype": dt.value, "halo": halo.value,
                 "plane_stride": ps.value, "device_ptr": ptr.value}
 
-    def free(self):
-        if self._hook is not None:
-            hook, self._hook = self._hook, None
-            try:
-                hook(self)
-            except Exception:
-                pass
+    def _release(self):
         if self._h:
             load().xlbhip_field_destroy(self._h)
             self._h = _p()
-
-    def __del__(self):
-        try:
-            self._hook = None
-            if self._h:
-                load().xlbhip_field_destroy(self._h)
-                self._h = _p()
-        except Exception:
-            pass
 
     def __repr__(self):
         return f"HipField(shape={self.shape}, dtype={self.dtype}, halo={self.halo})"
@@ -557,15 +591,37 @@ def _hf(field):
     return field.handle
 
 
-class Stepper:
+class _Native:
+    """A native object behind the handle ``_h``: made by xlbhip_<_kind>_create(context, ..., &handle), given back by xlbhip_<_kind>_destroy."""
+
+    def __init__(self, ctx, *create_args):
+        self.ctx, self._h = ctx, _p()
+        check(getattr(load(), f"xlbhip_{self._kind}_create")(ctx.handle, *create_args, C.byref(self._h)))
+
+    def free(self):
+        if self._h:
+            getattr(load(), f"xlbhip_{self._kind}_destroy")(self._h)
+            self._h = _p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _bc_array(bc_descs):
+    """(n, BcDesc[n]) as the xlbhip_*_create functions take the boundary conditions (never a zero-length array)"""
+    return len(bc_descs), (BcDesc * max(len(bc_descs), 1))(*bc_descs)
+
+
+class Stepper(_Native):
     """Native stepper object (xlbhip_stepper_create)."""
 
+    _kind = "stepper"
+
     def __init__(self, ctx, lattice_id, collision_id, compute_code, store_code, bc_descs):
-        self.ctx = ctx
-        n = len(bc_descs)
-        arr = (BcDesc * max(n, 1))(*bc_descs)
-        self._h = _p()
-        check(load().xlbhip_stepper_create(ctx.handle, lattice_id, collision_id, compute_code, store_code, n, arr, C.byref(self._h)))
+        super().__init__(ctx, lattice_id, collision_id, compute_code, store_code, *_bc_array(bc_descs))
 
     def set_force(self, force3):
         if force3 is None:
@@ -664,29 +720,17 @@ class Stepper:
                                       int(n_steps), C.byref(ms), C.byref(where)))
         return bool(where.value), ms.value
 
-    def free(self):
-        if self._h:
-            load().xlbhip_stepper_destroy(self._h)
-            self._h = _p()
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class IBM:
+class IBM(_Native):
     """Native immersed-boundary object (xlbhip_ibm_create): the markers, their footprint and the coupling after a stepper's step."""
 
+    _kind = "ibm"
+
     def __init__(self, ctx, stepper, lattice_id, compute_code, store_code, shape3, max_iterations, tolerance, relaxation):
-        self.ctx = ctx
         self._stepper = stepper  # (kept alive: the native object calls into it)
         self.n = 0
         self.n_bodies = 0
-        self._h = _p()
-        check(load().xlbhip_ibm_create(ctx.handle, stepper._h, lattice_id, compute_code, store_code, int(shape3[0]), int(shape3[1]), int(shape3[2]),
-                                       int(max_iterations), float(tolerance), float(relaxation), C.byref(self._h)))
+        super().__init__(ctx, stepper._h, lattice_id, compute_code, store_code, *map(int, shape3[:3]), int(max_iterations), float(tolerance), float(relaxation))
 
     @staticmethod
     def _f32(a, shape):
@@ -810,29 +854,16 @@ class IBM:
         check(load().xlbhip_ibm_download_markers(self._h, self.n, *(None if x is None else x.ctypes.data for x in (p, v))))
         return p, v
 
-    def free(self):
-        if self._h:
-            load().xlbhip_ibm_destroy(self._h)
-            self._h = _p()
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class Scalar:
+class Scalar(_Native):
     """Native scalar-transport object (xlbhip_scalar_create): the tables of the coupled fluid + scalar step."""
+
+    _kind = "scalar"
 
     ADIABATIC, DIRICHLET, DO_NOTHING = 0, 1, 2  # SCALAR_* of csrc/scalar_kernels.hpp
 
     def __init__(self, ctx, lattice_id, collision_id, compute_code, store_code, bc_descs):
-        self.ctx = ctx
-        n = len(bc_descs)
-        arr = (BcDesc * max(n, 1))(*bc_descs)
-        self._h = _p()
-        check(load().xlbhip_scalar_create(ctx.handle, lattice_id, collision_id, compute_code, store_code, n, arr, C.byref(self._h)))
+        super().__init__(ctx, lattice_id, collision_id, compute_code, store_code, *_bc_array(bc_descs))
 
     def set_rules(self, rules):
         """rules: [(bc id, ADIABATIC / DIRICHLET / DO_NOTHING, value)]"""
@@ -861,27 +892,14 @@ class Scalar:
                                        float(omega_scalar), int(first_timestep), int(n_steps), C.byref(where)))
         return bool(where.value)
 
-    def free(self):
-        if self._h:
-            load().xlbhip_scalar_destroy(self._h)
-            self._h = _p()
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class Adjoint:
+class Adjoint(_Native):
     """Native adjoint object (xlbhip_adjoint_create): the boundary tables of the fused adjoint step and the device scalar dL/domega."""
 
+    _kind = "adjoint"
+
     def __init__(self, ctx, lattice_id, compute_code, store_code, bc_descs):
-        self.ctx = ctx
-        n = len(bc_descs)
-        arr = (BcDesc * max(n, 1))(*bc_descs)
-        self._h = _p()
-        check(load().xlbhip_adjoint_create(ctx.handle, lattice_id, compute_code, store_code, n, arr, C.byref(self._h)))
+        super().__init__(ctx, lattice_id, compute_code, store_code, *_bc_array(bc_descs))
 
     def step(self, f_n, lam_in, lam_out, bc_mask, missing_mask, omega):
         check(load().xlbhip_adjoint_step(self._h, _hf(f_n), _hf(lam_in), _hf(lam_out), _h(bc_mask), _h(missing_mask), float(omega)))
@@ -901,29 +919,16 @@ class Adjoint:
     def reset(self):
         check(load().xlbhip_adjoint_reset(self._h))
 
-    def free(self):
-        if self._h:
-            load().xlbhip_adjoint_destroy(self._h)
-            self._h = _p()
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class Multiphase:
+class Multiphase(_Native):
     """Native Shan-Chen object (xlbhip_multiphase_create): the boundary tables, the wall pseudopotentials and the psi field of the step."""
+
+    _kind = "multiphase"
 
     EXPONENTIAL, DENSITY, CARNAHAN_STARLING = 0, 1, 2  # PSI_* of csrc/multiphase_kernels.hpp
 
     def __init__(self, ctx, lattice_id, compute_code, store_code, bc_descs):
-        self.ctx = ctx
-        n = len(bc_descs)
-        arr = (BcDesc * max(n, 1))(*bc_descs)
-        self._h = _p()
-        check(load().xlbhip_multiphase_create(ctx.handle, lattice_id, compute_code, store_code, n, arr, C.byref(self._h)))
+        super().__init__(ctx, lattice_id, compute_code, store_code, *_bc_array(bc_descs))
 
     def set_model(self, form, g, params, force3):
         p = np.ascontiguousarray(params, dtype=np.float64)
@@ -956,34 +961,22 @@ class Multiphase:
     def macroscopic(self, f, bc_mask, missing_mask, rho, u):
         check(load().xlbhip_multiphase_macroscopic(self._h, _hf(f), _h(bc_mask), _h(missing_mask), _hf(rho), _hf(u)))
 
-    def free(self):
-        if self._h:
-            load().xlbhip_multiphase_destroy(self._h)
-            self._h = _p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
 
 def macroscopic_adjoint(ctx, lattice_id, compute_code, f, rho_bar, u_bar, lam):
     check(load().xlbhip_macroscopic_adjoint(ctx.handle, lattice_id, compute_code, _hf(f), _h(rho_bar), _h(u_bar), _hf(lam)))
 
 
-class Stats:
+class Stats(_Native):
     """Native flow-statistics object (xlbhip_stats_create): running sums [channel][bin] and the watchdog's counters."""
 
+    _kind = "stats"
+
     def __init__(self, ctx, lattice_id, compute_code, shape3, keep_mask, order, exclude_ids):
-        self.ctx = ctx
         bits = np.zeros(8, np.uint32)
         for v in exclude_ids:
             bits[int(v) >> 5] |= np.uint32(1 << (int(v) & 31))
         self.samples = 0
-        self._h = _p()
-        check(load().xlbhip_stats_create(ctx.handle, lattice_id, compute_code, int(shape3[0]), int(shape3[1]), int(shape3[2]), int(keep_mask), int(order),
-                                         bits.ctypes.data, C.byref(self._h)))
+        super().__init__(ctx, lattice_id, compute_code, int(shape3[0]), int(shape3[1]), int(shape3[2]), int(keep_mask), int(order), bits.ctypes.data)
 
     def sample(self, f, bc_mask):
         # (read-only: through .handle, which flushes work deferred on the fields, without invalidating what is cached on them)
@@ -1000,17 +993,6 @@ class Stats:
     def reset(self):
         check(load().xlbhip_stats_reset(self._h))
         self.samples = 0
-
-    def free(self):
-        if self._h:
-            load().xlbhip_stats_destroy(self._h)
-            self._h = _p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def build_masks(ctx, lattice_id, bc_ids, tag_lists, solid_lists, global_shape3, x_offset, bc_mask, missing_mask):

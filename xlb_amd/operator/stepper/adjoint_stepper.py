@@ -28,9 +28,8 @@ fp16 storage, slab-decomposed fields, IBMStepper and ScalarTransportStepper.  No
 or geometry, multi-rank sweeps, out-of-core checkpoints, an autograd wrapper (the DLPack view of a field is enough to build one)."""
 
 from ... import _lib
-from ...precision_policy import Precision
-from ..boundary_condition import DoNothingBC, EquilibriumBC, FullwayBounceBackBC, HalfwayBounceBackBC, HybridBC
-from .nse_stepper import IncompressibleNavierStokesStepper
+from ..boundary_condition import DoNothingBC, EquilibriumBC, FullwayBounceBackBC, HalfwayBounceBackBC
+from .nse_stepper import IncompressibleNavierStokesStepper, refuse_unsupported
 
 
 class AdjointStepper:
@@ -44,20 +43,14 @@ class AdjointStepper:
             raise NotImplementedError(f"AdjointStepper: collision_type {fwd.collision_type!r} is not supported; the adjoint is built for BGK")
         if fwd.force_vector is not None:
             raise NotImplementedError("AdjointStepper: a force vector is not supported")
-        pp = fwd.precision_policy
-        if pp.store_precision is Precision.FP16:
-            raise NotImplementedError(f"AdjointStepper: fp16 storage ({pp.name}) is not supported; use FP32FP32, FP64FP64 or FP64FP32")
-        grid = fwd.grid
-        if getattr(grid, "halo", 0) != 0 or getattr(grid, "n_ranks", 1) != 1:
-            raise NotImplementedError("AdjointStepper: slab-decomposed fields (ghost planes, several ranks) are not supported")
-        for bc in fwd.boundary_conditions:
-            if isinstance(bc, HybridBC):
-                raise NotImplementedError("AdjointStepper: HybridBC is not supported")
-            if getattr(bc, "profile", None) is not None or getattr(bc, "is_time_dependent", False):
-                raise NotImplementedError(f"AdjointStepper: {type(bc).__name__} with a profile (per-cell or time-dependent values) is not supported")
+        pp, grid = fwd.precision_policy, fwd.grid
+
+        def known_kinds(bc):
             if type(bc) not in (EquilibriumBC, HalfwayBounceBackBC, FullwayBounceBackBC, DoNothingBC):
                 raise NotImplementedError(f"AdjointStepper: {type(bc).__name__} is not supported (EquilibriumBC, HalfwayBounceBackBC, "
                                           "FullwayBounceBackBC and DoNothingBC only)")
+
+        refuse_unsupported("AdjointStepper", pp, grid, fwd.boundary_conditions, also=known_kinds)
         self.forward = fwd
         self.grid = grid
         self.velocity_set = fwd.velocity_set
@@ -78,14 +71,14 @@ class AdjointStepper:
 
     def adjoint_step(self, f_n, lam_next, lam_out, bc_mask, missing_mask, omega):
         """lam_out = (dS/df_n)^T lam_next; adds the step's omega term to the device scalar"""
-        self.forward._flush_deferred()
+        self.forward.flush_deferred()
         self._native().step(f_n, lam_next, lam_out, bc_mask, missing_mask, omega)
         return lam_out
 
     def backward(self, states, lam_final, lam_other, bc_mask, missing_mask, omega):
         """The adjoint steps over ``states`` = [f_0 .. f_{N-1}], last first, in native code (one fused launch per step, nothing waits
         for the device); ``lam_final`` holds lam_N, both cotangent fields are overwritten.  Returns (lam_0, the other field)."""
-        self.forward._flush_deferred()
+        self.forward.flush_deferred()
         in_b = self._native().run(list(states), lam_final, lam_other, bc_mask, missing_mask, omega)
         return (lam_other, lam_final) if in_b else (lam_final, lam_other)
 

@@ -72,9 +72,8 @@ import numpy as np
 from ... import _lib
 from ...helper.ibm_helper import IBMBody, RigidDynamics, RigidMotion, declare_bodies  # noqa: F401  (re-exported: they are this stepper's vocabulary)
 from ...compute_backend import ComputeBackend
-from ...precision_policy import Precision
 from ..operator import Operator
-from .nse_stepper import IncompressibleNavierStokesStepper
+from .nse_stepper import IncompressibleNavierStokesStepper, refuse_unsupported
 
 
 class IBMMarkers:
@@ -128,10 +127,7 @@ class IBMStepper(IncompressibleNavierStokesStepper):
         super().__init__(grid, boundary_conditions, collision_type=collision_type, backend_config={"lazy_pairs": False})
         if self.velocity_set.d != 3:
             raise NotImplementedError("IBMStepper: 2-D grids are not supported (the coupling kernels are written for D3Q19 / D3Q27)")
-        if self.precision_policy.store_precision is Precision.FP16:
-            raise NotImplementedError(f"IBMStepper: fp16 storage ({self.precision_policy.name}) is not supported; use FP32FP32, FP64FP64 or FP64FP32")
-        if getattr(grid, "halo", 0) != 0 or getattr(grid, "n_ranks", 1) != 1:
-            raise NotImplementedError("IBMStepper: slab-decomposed fields (ghost planes, several ranks) are not supported")
+        refuse_unsupported("IBMStepper", self.precision_policy, grid)
         self.use_scoped_timer = bool(use_scoped_timer)  # (accepted for the reference's signature; timing is run_timed's job here)
         self.ibm_max_iterations = int(ibm_max_iterations)
         self.ibm_tolerance = float(ibm_tolerance)

@@ -45,11 +45,10 @@ from ... import _lib
 from ...cell_type import BC_SOLID
 from ...compute_backend import ComputeBackend
 from ...helper.initializers import initialize_eq
-from ...precision_policy import Precision
-from ..boundary_condition import FullwayBounceBackBC, HalfwayBounceBackBC, HybridBC
+from ..boundary_condition import FullwayBounceBackBC, HalfwayBounceBackBC
 from ..boundary_condition.boundary_condition import BoundaryCondition
 from ..operator import Operator
-from .nse_stepper import IncompressibleNavierStokesStepper
+from .nse_stepper import IncompressibleNavierStokesStepper, refuse_unsupported
 
 CS2 = 1.0 / 3.0
 
@@ -142,18 +141,13 @@ class MultiphaseStepper(IncompressibleNavierStokesStepper):
             raise ValueError("MultiphaseStepper: pseudopotential takes ShanChenExponential, ShanChenDensity or CarnahanStarling")
         super().__init__(grid, boundary_conditions, collision_type="BGK", force_vector=force_vector, backend_config={"lazy_pairs": False})
         del self.macroscopic  # (the fluid stepper's bare-moment operator; here macroscopic() is the method below)
-        if self.precision_policy.store_precision is Precision.FP16:
-            raise NotImplementedError(f"MultiphaseStepper: fp16 storage ({self.precision_policy.name}) is not supported; use FP32FP32, FP64FP64 or FP64FP32")
-        if getattr(grid, "halo", 0) != 0 or getattr(grid, "n_ranks", 1) != 1:
-            raise NotImplementedError("MultiphaseStepper: slab-decomposed fields (ghost planes, several ranks) are not supported")
-        for bc in self.boundary_conditions:
-            if isinstance(bc, HybridBC):
-                raise NotImplementedError("MultiphaseStepper: HybridBC is not supported")
-            if getattr(bc, "profile", None) is not None or getattr(bc, "is_time_dependent", False):
-                raise NotImplementedError(f"MultiphaseStepper: {type(bc).__name__} with a profile (per-cell or time-dependent values) is not supported")
+
+        def walls_only(bc):
             if not isinstance(bc, (HalfwayBounceBackBC, FullwayBounceBackBC)):
                 raise NotImplementedError(f"MultiphaseStepper: {type(bc).__name__} is not supported (HalfwayBounceBackBC and FullwayBounceBackBC only): "
                                           "its missing directions have no agreed neighbour pseudopotential")
+
+        refuse_unsupported("MultiphaseStepper", self.precision_policy, grid, self.boundary_conditions, also=walls_only)
         self.model = pseudopotential
         self.wall_density = self._wall_table(wall_density)
         self._multiphase = None
@@ -186,13 +180,6 @@ class MultiphaseStepper(IncompressibleNavierStokesStepper):
         T = self.compute_dtype
         with np.errstate(all="ignore"):
             return {i: self.model.psi(np.array(rho_w, dtype=T))[()] for i, rho_w in self.wall_density.items()}
-
-    def _internal3(self, v):
-        if v is None:
-            return None
-        out = np.zeros(3)
-        out[3 - self.velocity_set.d :] = v
-        return out
 
     def _multiphase_native(self):
         if self._multiphase is None:

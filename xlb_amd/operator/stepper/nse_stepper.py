@@ -24,13 +24,16 @@ to single steps.  After a fused pair the field that received step t+1 in the ref
 before the next call overwrites it, it is materialised through a temporary third field — also when one of the two masks is used
 first (edited, read, freed): the step that is owed was issued with the masks as they were.  Fields exported through DLPack /
 ``__cuda_array_interface__`` are never deferred (their memory must stay put); ``backend_config={"lazy_pairs": False}``
-switches the mechanism off.
+switches the mechanism off.  call_pairing.py owns the protocol (``CallPairing``: ``call`` defers and fuses, ``flush_deferred`` runs
+the deferred step alone, ``_Materialise`` hooks a virtual field) and steps through this stepper's ``_step`` / ``_step2``.
 
 **Time-dependent walls.**  A HalfwayBounceBackBC / HybridBC with ``profile(cells, timestep)`` gets one profile table per timestep:
 the host evaluates the profile and stages the values (``xlbhip_stepper_stage_bc_profiles``: a ring of device slots, asynchronous
 copies on the compute stream) before the launch that reads them; the step from f(t) to f(t+1) uses ``profile(cells, t)``.  A
 reference-style call stages its own timestep; a deferred call at t pairs only with a call at t + 1; ``run`` stages chunks of at most
 half the ring and evaluates the next chunk while the device runs the current one."""
+
+import time
 
 import numpy as np
 
@@ -39,14 +42,32 @@ from ...compute_backend import ComputeBackend
 from ...helper.check_boundary_overlaps import check_bc_overlaps
 from ...helper.initializers import initialize_eq
 from ...helper.nse_fields import create_nse_fields
-from ..boundary_condition import ImplementationStep
+from ...precision_policy import Precision
+from ..boundary_condition import HybridBC, ImplementationStep
 from ..boundary_masker import IndicesBoundaryMasker
 from ..collision import BGK, KBC, SmagorinskyLESBGK
 from ..equilibrium import QuadraticEquilibrium
 from ..macroscopic import Macroscopic
 from ..operator import Operator
 from ..stream import Stream
+from .call_pairing import CallPairing, drop_virtual_destination, pairs_in_time  # noqa: F401 (pairs_in_time: imported from here too)
 from .stepper import Stepper
+
+
+def refuse_unsupported(name, precision_policy, grid, boundary_conditions=(), hybrid="HybridBC is not supported", also=None):
+    """What the steppers beside the plain fluid step refuse at construction, worded alike: fp16 storage, slab-decomposed fields; then
+    per boundary condition HybridBC, a profile and what the caller checks `also` (one BC at a time: the refusals keep the list's order)."""
+    if precision_policy.store_precision is Precision.FP16:
+        raise NotImplementedError(f"{name}: fp16 storage ({precision_policy.name}) is not supported; use FP32FP32, FP64FP64 or FP64FP32")
+    if getattr(grid, "halo", 0) != 0 or getattr(grid, "n_ranks", 1) != 1:
+        raise NotImplementedError(f"{name}: slab-decomposed fields (ghost planes, several ranks) are not supported")
+    for bc in boundary_conditions:
+        if isinstance(bc, HybridBC):
+            raise NotImplementedError(f"{name}: {hybrid}")
+        if getattr(bc, "profile", None) is not None or getattr(bc, "is_time_dependent", False):
+            raise NotImplementedError(f"{name}: {type(bc).__name__} with a profile (per-cell or time-dependent values) is not supported")
+        if also is not None:
+            also(bc)
 
 
 def chunk_plan(n_steps, ring_slots):
@@ -56,64 +77,6 @@ def chunk_plan(n_steps, ring_slots):
     size = max(2, (int(ring_slots) // 2) & ~1)
     n = int(n_steps)
     return [min(size, n - i) for i in range(0, n, size)]
-
-
-def pairs_in_time(t_deferred, timestep, time_dependent):
-    """May a deferred call at t_deferred be fused with a call at `timestep`?  Always without time-dependent walls (the timestep does not
-    enter the step); with them only when the call is the next timestep — the fused pair runs steps t and t + 1."""
-    return not time_dependent or int(timestep) == int(t_deferred) + 1
-
-
-class _Materialise:
-    """Hook of a field that holds f(t+1) only virtually after a fused pair (its buffer holds f(t)): see _lazy_pair.  The step that is
-    owed was issued with the masks as they were, so the two masks carry a hook of their own (_MasksOfVirtual) that leads here: whoever
-    uses a mask first — to edit it, to free it, to read it — makes the step run first.  References go one way only, field -> this hook
-    -> masks -> (weakly) field: a field abandoned while virtual is released at once, with its device memory, not by the cycle collector."""
-
-    def __init__(self, stepper, field, bcm, miss, omega, t):
-        self.args = (stepper, bcm, miss, omega, t)
-        self.of_masks = _MasksOfVirtual(field)
-        for fld in (field, bcm, miss):
-            if fld is not None and fld._hook is not None:
-                fld.handle  # (whatever else is owed on it runs first; a pair has just used all three, so normally nothing is)
-        field._hook = self
-        self._hook_masks()
-
-    def _hook_masks(self):
-        for mask in self.args[1:3]:
-            if mask is not None and mask._hook is None:
-                mask._hook = self.of_masks
-
-    def drop(self, field):
-        """Nothing is owed any more (the step ran, or the field is about to be overwritten)."""
-        if field._hook is self:
-            field._hook = None
-        for mask in self.args[1:3]:
-            if mask is not None and mask._hook is self.of_masks:
-                mask._hook = None
-
-    def __call__(self, field):
-        stepper, bcm, miss, omega, t = self.args
-        self.drop(field)
-        try:
-            stepper._materialise(field, bcm, miss, omega, t)
-        except BaseException:
-            self._hook_masks()  # still owed, whichever of the three is used next (Field.handle puts the field's hook back)
-            raise
-
-
-class _MasksOfVirtual:
-    """Hook of the two masks while a field is virtual (_Materialise): using a mask uses that field first."""
-
-    def __init__(self, field):
-        import weakref
-
-        self.field = weakref.ref(field)
-
-    def __call__(self, _mask):
-        field = self.field()
-        if field is not None and isinstance(field._hook, _Materialise) and field._hook.of_masks is self:
-            field.handle
 
 
 class IncompressibleNavierStokesStepper(Stepper):
@@ -132,8 +95,7 @@ class IncompressibleNavierStokesStepper(Stepper):
         self.force_vector = force_vector
         self._native = None
         self._td_bcs, self._td_slots = [], 0  # BCs with time-dependent wall velocities (declaration order) and the ring's slot count
-        self._deferred = None   # (f_src, f_dst, bc_mask, missing_mask, omega, timestep): a step not enqueued yet
-        self._n_fused_pairs = self._n_materialised = 0  # statistics of the pairing (tests, diagnostics)
+        self._pairing = CallPairing(self) if self.backend_config.get("lazy_pairs", True) else None
         super().__init__(grid, boundary_conditions)
         vs, pp, be = self.velocity_set, self.precision_policy, self.compute_backend
         if collision_type == "BGK":
@@ -176,10 +138,12 @@ class IncompressibleNavierStokesStepper(Stepper):
                     # cell index == storage cell index on the single-rank fields mesh BCs live on
                     self._native.set_bc_distances(*table)
             if self.force_vector is not None:
-                f3 = np.zeros(3)
-                f3[3 - self.velocity_set.d :] = self.force_vector  # internal 3-component form
-                self._native.set_force(f3)
+                self._native.set_force(self._internal3(self.force_vector))
         return self._native
+
+    def _internal3(self, v):
+        """A d-component vector (or None) in the internal 3-component form."""
+        return None if v is None else np.concatenate([np.zeros(3 - self.velocity_set.d), np.asarray(v, dtype=np.float64)])
 
     def prepare_fields(self, initializer=None):
         _, f_0, f_1, missing_mask, bc_mask = create_nse_fields(
@@ -226,9 +190,10 @@ class IncompressibleNavierStokesStepper(Stepper):
 
     @Operator.register_backend(ComputeBackend.HIP)
     def hip_implementation(self, f_0, f_1, bc_mask, missing_mask, omega, timestep):
-        if not self._lazy_pair(f_0, f_1, bc_mask, missing_mask, omega, timestep):
-            self._stage(timestep, 1)
-            self._native_stepper().step(f_0, f_1, bc_mask, missing_mask, omega, timestep)
+        if self._pairing is None:
+            drop_virtual_destination(f_1)  # (another stepper's pair may have left it virtual; this step overwrites it)
+        if self._pairing is None or not self._pairing.call(f_0, f_1, bc_mask, missing_mask, omega, timestep):
+            self._step(f_0, f_1, bc_mask, missing_mask, omega, timestep)
         return f_0, f_1
 
     # -- time-dependent wall velocities (module docstring) ---------------------------------------------------------
@@ -256,142 +221,62 @@ class IncompressibleNavierStokesStepper(Stepper):
         if self._time_dependent_bcs():
             self._native.stage_bc_profiles(int(t_first), self._td_rows(t_first, n))
 
-    # -- pairing of reference-style calls (module docstring) ------------------------------------------------------
-    def _lazy_eligible(self, f_0, f_1, bc_mask, missing_mask):
-        if not self.backend_config.get("lazy_pairs", True) or f_0.halo != 0 or f_0._pinned or f_1._pinned:
-            return False
-        # (asked every time: the answer follows the backend options — fuse2, ... — and the masks' contents; host logic only)
-        if not self._native_stepper().step2_eligible(f_0, f_1, bc_mask, missing_mask):
-            return False
-        return self._room_for_a_third_field(f_0)
+    # -- pairing of reference-style calls (module docstring): call_pairing.py owns it and steps through these --------
+    def _step(self, f_src, f_dst, bc_mask, missing_mask, omega, t):
+        """Stage timestep t's tables, then one native step."""
+        self._stage(t, 1)
+        self._native_stepper().step(f_src, f_dst, bc_mask, missing_mask, omega, t)
 
-    def _room_for_a_third_field(self, f):
-        """After a fused pair one field holds f(t+1) only virtually, and reading it takes a temporary third population field
-        (_materialise).  A run whose two fields just fit — the reference's protocol needs no more — must not fail with
-        hipErrorOutOfMemory in an innocent read: without room for that field (plus 1/16 slack) the calls are not paired.
-        hipMemGetInfo is asked at the first pairing and every 256th afterwards."""
-        self._room_calls = getattr(self, "_room_calls", 0) + 1
-        if getattr(self, "_room_ok", None) is None or self._room_calls % 256 == 0:
-            info = f.info()
-            need = info["plane_stride"] * info["cardinality"] * f.dtype.itemsize
-            free, _ = self._ctx.mem_info()
-            self._room_ok = free >= need + need // 16
-        return self._room_ok
+    def _step2(self, f_src, f_dst, bc_mask, missing_mask, omega, t):
+        """Stage the tables of t and t + 1, then one fused pass: f(t) in f_src -> f(t+2) in f_dst."""
+        self._stage(t, 2)
+        self._native_stepper().step2(f_src, f_dst, bc_mask, missing_mask, omega, t)
 
-    def _flush_deferred(self, *_):
-        """Enqueue the deferred step as a single step (some other use of its fields came first)."""
-        d, self._deferred = self._deferred, None
-        if d is None:
-            return
-        f_src, f_dst, bcm, miss, omega, t = d
-        self._unhook(f_src, f_dst, bcm, miss)
-        try:
-            self._stage(t, 1)
-            self._native_stepper().step(f_src, f_dst, bcm, miss, omega, t)
-        except BaseException:
-            # not enqueued: the step stays owed (the next use of any of its fields tries again and raises again)
-            self._deferred = d
-            for fld in (f_src, f_dst, bcm, miss):
-                if fld is not None:
-                    fld._hook = self._flush_deferred
-            raise
+    def _step2_eligible(self, f_src, f_dst, bc_mask, missing_mask):
+        return self._native_stepper().step2_eligible(f_src, f_dst, bc_mask, missing_mask)
 
-    @staticmethod
-    def _unhook(*fields):
-        for fld in fields:
-            if fld is not None:
-                fld._hook = None
+    def _temporary_field(self):
+        return self.grid.create_field(cardinality=self.velocity_set.q, dtype=self.precision_policy.store_precision)
 
-    def _materialise(self, field, bcm, miss, omega, t):
-        """`field` should hold f(t+1) but its buffer holds f(t) (a fused pair passed it by): one single step through a
-        temporary field, whose buffer the field then adopts.  (Time-dependent walls: t's table is staged again — the ring may
-        have moved on since the pair — from the same pure profile.)"""
-        # the temporary comes first: if it cannot be allocated this raises with the hook still owed (Field.handle puts it
-        # back), so the next reader raises again instead of being handed f(t) for f(t+1)
-        tmp = self.grid.create_field(cardinality=self.velocity_set.q, dtype=self.precision_policy.store_precision)
-        try:
-            self._stage(t, 1)
-            self._native_stepper().step(field, tmp, bcm, miss, omega, t)  # (field._hook is None while its hook runs)
-        except BaseException:
-            tmp.free()
-            raise
-        self._n_materialised += 1
-        field._h, tmp._h = tmp._h, field._h
-        tmp.free()
+    _deferred = property(lambda self: self._pairing.deferred if self._pairing else None)  # (read-only views: tests, diagnostics)
+    _n_fused_pairs = property(lambda self: self._pairing.n_fused_pairs if self._pairing else 0)
+    _n_materialised = property(lambda self: self._pairing.n_materialised if self._pairing else 0)
 
-    def _lazy_pair(self, f_0, f_1, bc_mask, missing_mask, omega, timestep):
-        """True when this call was absorbed (deferred, or executed as the second half of a fused pair)."""
-        if isinstance(f_1._hook, _Materialise):
-            f_1._hook.drop(f_1)  # a virtual f(t+1) in the destination is about to be overwritten: nothing to materialise
-        d = self._deferred
-        if d is not None:
-            f_src, f_dst, bcm, miss, om, t = d
-            if (f_0 is f_dst and f_1 is f_src and bc_mask is bcm and missing_mask is miss and float(omega) == om and not (f_0._pinned or f_1._pinned)
-                    and pairs_in_time(t, timestep, bool(self._time_dependent_bcs()))):
-                # the caller swapped the fields: steps t and t + 1 in one pass, f(t) in f_src's buffer -> f(t+2) in f_dst's
-                self._deferred = None
-                self._unhook(f_src, f_dst, bcm, miss)
-                if not self._native_stepper().step2_eligible(f_src, f_dst, bcm, miss):  # (an option changed in between)
-                    self._stage(t, 1)
-                    self._native_stepper().step(f_src, f_dst, bcm, miss, om, t)
-                    return False
-                self._stage(t, 2)
-                self._native_stepper().step2(f_src, f_dst, bcm, miss, om, t)
-                self._n_fused_pairs += 1
-                # the reference's protocol leaves f(t+2) in THIS call's f_1 (= f_src) and f(t+1) in its f_0 (= f_dst):
-                # exchange the buffers; f_dst now holds f(t) instead of f(t+1) until someone looks
-                f_src._h, f_dst._h = f_dst._h, f_src._h
-                _Materialise(self, f_dst, bcm, miss, om, t)  # (hooks f_dst and both masks: an edited mask must not reach that step)
-                return True
-            self._flush_deferred()
-        if not self._lazy_eligible(f_0, f_1, bc_mask, missing_mask):
-            return False
-        # defer: whoever touches either field first (or ctx.sync()) makes it run
-        if f_0._hook is not None:  # the source itself is virtual (read it properly first)
-            f_0.handle
-        self._deferred = (f_0, f_1, bc_mask, missing_mask, float(omega), timestep)
-        for fld in (f_0, f_1, bc_mask, missing_mask):  # the masks too: editing them must not overtake the deferred step
-            if fld is not None:
-                fld._hook = self._flush_deferred
-        import weakref
+    def flush_deferred(self):
+        """Enqueue a deferred reference-style call as a single step (its fields are about to be used another way)."""
+        if self._pairing is not None:
+            self._pairing.flush_deferred()
 
-        if not any(r() is self for r in self._ctx._flushers):
-            self._ctx._flushers.append(weakref.ref(self))
-        return True
+    def abandon_deferred(self):
+        """Forget a deferred reference-style call and unhook its fields: its step will never run."""
+        if self._pairing is not None:
+            self._pairing.abandon_deferred()
 
-    @staticmethod
-    def _drop_virtual_destination(f_1, n_steps):
-        """The first of n >= 1 steps overwrites f_1 entirely: a virtual f(t+1) in it (left by a fused pair of reference-style
-        calls) needs no materialisation — which would allocate a third field and run an extra step for nothing."""
-        if n_steps >= 1 and isinstance(f_1._hook, _Materialise):
-            f_1._hook.drop(f_1)
+    def _run_loop(self, f_0, f_1, n_steps):
+        """What run and run_timed begin with: the deferred call runs first, a virtual destination is dropped; then the loop that
+        interleaves host work with the device's — host-staged ghost planes, chunks of time-dependent tables — or None: the native loop."""
+        self.flush_deferred()
+        drop_virtual_destination(f_1, n_steps)
+        if f_0.halo > 0 and self._ctx.get_option("external_halo"):
+            return self._run_host_staged
+        return self._run_chunked if self._time_dependent_bcs() else None
 
     def run(self, f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep=0):
         """``n_steps`` x (step, swap) in native code; returns (f_current, f_other)."""
-        self._flush_deferred()
-        self._drop_virtual_destination(f_1, n_steps)
-        if f_0.halo > 0 and self._ctx.get_option("external_halo"):
-            return self._run_host_staged(f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep)
-        if self._time_dependent_bcs():
-            return self._run_chunked(f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep)
+        loop = self._run_loop(f_0, f_1, n_steps)
+        if loop is not None:
+            return loop(f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep)
         in_b = self._native_stepper().run(f_0, f_1, bc_mask, missing_mask, omega, first_timestep, n_steps)
         return (f_1, f_0) if in_b else (f_0, f_1)
 
     def run_timed(self, f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep=0):
         """As :meth:`run`; also returns the device time in ms measured with HIP events.  (Host-staged transports and time-dependent
         walls: the wall clock between two synchronisations — those loops interleave host work with the device's.)"""
-        self._flush_deferred()
-        self._drop_virtual_destination(f_1, n_steps)
-        host_staged = f_0.halo > 0 and self._ctx.get_option("external_halo")
-        if host_staged or self._time_dependent_bcs():
-            import time
-
+        loop = self._run_loop(f_0, f_1, n_steps)
+        if loop is not None:
             self._ctx.sync()  # no single native loop to bracket with events; wall clock instead
             t0 = time.perf_counter()
-            if host_staged:
-                out = self._run_host_staged(f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep)
-            else:
-                out = self._run_chunked(f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep)
+            out = loop(f_0, f_1, bc_mask, missing_mask, omega, n_steps, first_timestep)
             self._ctx.sync()
             return out, (time.perf_counter() - t0) * 1e3
         in_b, ms = self._native_stepper().run_timed(f_0, f_1, bc_mask, missing_mask, omega, first_timestep, n_steps)

@@ -41,12 +41,11 @@ import numpy as np
 
 from ... import _lib
 from ...compute_backend import ComputeBackend
-from ...precision_policy import Precision
-from ..boundary_condition import FullwayBounceBackBC, HybridBC
+from ..boundary_condition import FullwayBounceBackBC
 from ..boundary_condition.scalar_boundary_condition import ScalarBoundaryCondition, ScalarDirichletBC
 from ..collision import SmagorinskyLESBGK
 from ..operator import Operator
-from .nse_stepper import IncompressibleNavierStokesStepper
+from .nse_stepper import IncompressibleNavierStokesStepper, refuse_unsupported
 
 
 class ScalarTransportStepper(IncompressibleNavierStokesStepper):
@@ -54,15 +53,7 @@ class ScalarTransportStepper(IncompressibleNavierStokesStepper):
                  force_vector=None):
         super().__init__(grid, boundary_conditions, collision_type=collision_type, force_vector=force_vector, backend_config={"lazy_pairs": False})
         vs = self.velocity_set
-        if self.precision_policy.store_precision is Precision.FP16:
-            raise NotImplementedError(f"ScalarTransportStepper: fp16 storage ({self.precision_policy.name}) is not supported; use FP32FP32, FP64FP64 or FP64FP32")
-        if getattr(grid, "halo", 0) != 0 or getattr(grid, "n_ranks", 1) != 1:
-            raise NotImplementedError("ScalarTransportStepper: slab-decomposed fields (ghost planes, several ranks) are not supported")
-        for bc in self.boundary_conditions:
-            if isinstance(bc, HybridBC):
-                raise NotImplementedError("ScalarTransportStepper: HybridBC is not supported by the coupled kernel")
-            if getattr(bc, "profile", None) is not None or getattr(bc, "is_time_dependent", False):
-                raise NotImplementedError(f"ScalarTransportStepper: {type(bc).__name__} with a profile (per-cell or time-dependent values) is not supported")
+        refuse_unsupported("ScalarTransportStepper", self.precision_policy, grid, self.boundary_conditions, hybrid="HybridBC is not supported by the coupled kernel")
         self.scalar_boundary_conditions = list(scalar_boundary_conditions)
         seen = set()
         for rule in self.scalar_boundary_conditions:
@@ -84,13 +75,6 @@ class ScalarTransportStepper(IncompressibleNavierStokesStepper):
         self.scalar_q = 2 * vs.d + 1
         self.scalar_directions = np.concatenate([[vs.center_index], np.sort(vs.main_indices)]).astype(np.int64)  # fluid direction of each scalar one
         self._scalar = None
-
-    def _internal3(self, v):
-        if v is None:
-            return None
-        out = np.zeros(3)
-        out[3 - self.velocity_set.d :] = v
-        return out
 
     def _scalar_native(self):
         if self._scalar is None:
