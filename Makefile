@@ -8,7 +8,7 @@ LIB       ?= xlb_amd/lib/libxlbhip.so
 EXTRA     ?=
 HIPFLAGS  := $(EXTRA) --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fPIC -Wall -Wno-unused-function -Iinclude
 SRCS      := api.hip masker.hip stepper.hip ibm.hip stats.hip comm.cpp step_d2q9_bgk.hip step_d2q9_kbc.hip step_d3q19_bgk.hip step_d3q27_bgk.hip step_d3q27_kbc.hip step_d3q27_kbc_fast.hip \
-             step_d2q9_ext.hip step_d3q19_ext.hip step_d3q27_ext.hip step2_d3q19.hip step2_d3q19_strips.hip step2_d3q27.hip yardstick.hip \
+             step_d2q9_ext.hip step_d3q19_ext.hip step_d3q27_ext.hip step_d2q9_reg.hip step_d3q19_reg.hip step_d3q27_reg.hip step2_d3q19.hip step2_d3q19_strips.hip step2_d3q27.hip yardstick.hip \
              scalar.hip scalar_d2q9.hip scalar_d3q19.hip scalar_d3q27.hip \
              adjoint.hip adjoint_d2q9.hip adjoint_d3q19.hip adjoint_d3q27.hip \
              multiphase.hip multiphase_d2q9.hip multiphase_d3q19.hip multiphase_d3q27.hip
@@ -20,6 +20,13 @@ all: $(LIB) oracle
 # the two-step kernel packs its fp32 pairs by hand (cell.hpp: bgk_packed_pairs); hipcc's SLP vectorizer on top of that
 # scrambles the sequential moment sums into packed adds + moves (measured +2 % kernel time)
 $(OBJDIR)/step2_d3q19.o $(OBJDIR)/step2_d3q19_strips.o $(OBJDIR)/step2_d3q27.o: HIPFLAGS += -fno-slp-vectorize
+
+# the regularised units (tests/test_regularized_build.py compiles with the same flags and requires that no FP32FP32 kernel reserves
+# a private segment): the loop over the cells of a thread must unroll in the extended-boundary variants too — at VEC = 4 its body exceeds
+# the default pragma-unroll threshold, and f[4][q] would live in scratch —, and with the spiller placing spills for size the forced
+# extended-boundary kernels keep no dead stack slot for a kernel-argument tuple that is re-loaded instead of spilled (36 B otherwise)
+REGFLAGS  := -mllvm -pragma-unroll-threshold=200000 -mllvm -split-spill-mode=size
+$(OBJDIR)/step_d2q9_reg.o $(OBJDIR)/step_d3q19_reg.o $(OBJDIR)/step_d3q27_reg.o: HIPFLAGS += $(REGFLAGS)
 
 # the sample kernel's moment sums are sequential by contract; packed adds only cost it moves and registers
 $(OBJDIR)/stats.o: HIPFLAGS += -fno-slp-vectorize

@@ -57,7 +57,11 @@ enum { XLBHIP_D2Q9 = 0, XLBHIP_D3Q19 = 1, XLBHIP_D3Q27 = 2 };
 enum {
   XLBHIP_BGK = 0,
   XLBHIP_KBC = 1,
-  XLBHIP_SMAGORINSKY_LES_BGK = 2 /* xlb/operator/collision/smagorinsky_les_bgk.py:44-60 (section 8f rank 3) */
+  XLBHIP_SMAGORINSKY_LES_BGK = 2, /* xlb/operator/collision/smagorinsky_les_bgk.py:44-60 (section 8f rank 3) */
+  /* regularised BGK (not in the reference): fneq rebuilt from its second Hermite moment (Latt & Chopard 2006), and with the
+   * third-order moments that follow from it recursively (Malaspinas 2015).  Single-step kernel, FP32FP32 / FP64FP64 / FP64FP32 */
+  XLBHIP_REGULARIZED_BGK = 3,
+  XLBHIP_RECURSIVE_REGULARIZED_BGK = 4
 };
 
 /* boundary-condition kinds (in scope: SURVEY.md section 8 rows a7-a9, + DoNothing) */
@@ -190,7 +194,7 @@ int xlbhip_vorticity(xlbhip_ctx* ctx, const xlbhip_field* u, const xlbhip_field*
 int xlbhip_grid_to_point(xlbhip_ctx* ctx, const xlbhip_field* grid, int64_t n, const float* points, void* point_values);
 /* QCriterion()(u, bc_mask, norm_mu, q): postprocess/q_criterion.py:36-139; Q = (|Omega|^2 - |S|^2) / 2, same cells */
 int xlbhip_q_criterion(xlbhip_ctx* ctx, const xlbhip_field* u, const xlbhip_field* bc_mask, xlbhip_field* norm_mu, xlbhip_field* q);
-/* BGK()/KBC()(f, feq, fout, omega): bgk.py:27-32,:78-91; kbc.py:40-79 */
+/* BGK()/KBC()(f, feq, fout, omega): bgk.py:27-32,:78-91; kbc.py:40-79.  The regularised collisions take rho and u from f */
 int xlbhip_collide(xlbhip_ctx* ctx, int lattice, int collision, int compute_dtype, const xlbhip_field* f,
                    const xlbhip_field* feq, xlbhip_field* fout, double omega);
 /* bc(f_pre, f_post, bc_mask, missing_mask) -> f_post (in place): boundary_condition.py:146-180 */

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("XLBHIP_LIB") or os.path.join(_HERE, "lib", "libxlbhip
 # element types (include/xlbhip.h)
 F64, F32, F16, U8, BOOL, MISSING = 0, 1, 2, 3, 4, 5
 D2Q9, D3Q19, D3Q27 = 0, 1, 2
-BGK, KBC, SMAGORINSKY_LES_BGK = 0, 1, 2
+BGK, KBC, SMAGORINSKY_LES_BGK, REGULARIZED_BGK, RECURSIVE_REGULARIZED_BGK = 0, 1, 2, 3, 4
 BC_EQUILIBRIUM, BC_HALFWAY_BB, BC_FULLWAY_BB, BC_DO_NOTHING = 1, 2, 3, 4
 BC_ZOUHE_VELOCITY, BC_ZOUHE_PRESSURE, BC_REGULARIZED_VELOCITY, BC_REGULARIZED_PRESSURE = 5, 6, 7, 8
 BC_EXTRAPOLATION_OUTFLOW = 9

@@ -70,6 +70,11 @@ static int collide_launch(xlbhip_ctx* c, int coll, const xlbhip_field* f, const 
   } else if (coll == XLBHIP_SMAGORINSKY_LES_BGK) {
     hipLaunchKernelGGL((k_collide<L, T, XLBHIP_SMAGORINSKY_LES_BGK>), blocks_for(n), 256, 0, c->stream, view(f), view(feq), view(fo), dims(f),
                        (T)omega, cs);
+  } else if (coll == XLBHIP_REGULARIZED_BGK) {
+    hipLaunchKernelGGL((k_collide<L, T, COLL_REGULARIZED>), blocks_for(n), 256, 0, c->stream, view(f), view(feq), view(fo), dims(f), (T)omega, cs);
+  } else if (coll == XLBHIP_RECURSIVE_REGULARIZED_BGK) {
+    hipLaunchKernelGGL((k_collide<L, T, COLL_REGULARIZED | COLL_RECURSIVE>), blocks_for(n), 256, 0, c->stream, view(f), view(feq), view(fo), dims(f),
+                       (T)omega, cs);
   } else {
     if constexpr (L::ID == XLBHIP_D3Q19) {
       XLB_FAIL("Velocity set not supported: D3Q19 has no KBC (reference kbc.py:65-66)");
@@ -578,7 +583,7 @@ int xlbhip_collide(xlbhip_ctx* c, int lattice, int coll, int cdt, const xlbhip_f
   XLB_CHECK_POP(feq, lattice, "collide(feq)");
   XLB_CHECK_POP(fo, lattice, "collide(fout)");
   XLB_REQUIRE(same_grid(f, feq) && same_grid(f, fo), "collide: grids differ");
-  XLB_REQUIRE(coll == XLBHIP_BGK || coll == XLBHIP_KBC || coll == XLBHIP_SMAGORINSKY_LES_BGK, "unknown collision %d", coll);
+  XLB_REQUIRE(coll >= XLBHIP_BGK && coll <= XLBHIP_RECURSIVE_REGULARIZED_BGK, "unknown collision %d", coll);
   XLB_REQUIRE(cdt == XLBHIP_F32 || cdt == XLBHIP_F64, "bad compute dtype %d", cdt);
   touch(fo);
   return by_lattice(lattice, [&](auto L) {

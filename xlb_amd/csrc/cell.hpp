@@ -457,6 +457,22 @@ constexpr double qi(int l, int k) {
   return 0.0;
 }
 
+// Second-order Hermite projection of direction l: 4.5 w_l sum_ab (c_a c_b - delta_ab / 3) Pi_ab, the components summed in k order.
+// The regularised boundary rules (zouhe_cell, hybrid_cell) and the regularised collisions (regularized) rebuild fneq with it.
+template <class L, class T, int l>
+__device__ __forceinline__ T hermite2_dir(const T (&pi)[6]) {
+  T qp = T(0);
+  static_for<n_pi<L>()>([&](auto kc) {
+    constexpr int k = decltype(kc)::value;
+    const T t = T(qi<L>(l, k)) * pi[k];
+    if constexpr (k == 0)
+      qp = t;
+    else
+      qp = qp + t;
+  });
+  return (T(4.5) * T(L::w(l))) * qp;
+}
+
 // f: post-streaming populations of the cell (updated in place); m: missing bit-set;
 // val: prescribed velocity (val[0..2], internal 3-component form) or density (val[0]).
 template <class L, class T>
@@ -527,16 +543,7 @@ __device__ __forceinline__ void zouhe_cell(T (&f)[L::Q], unsigned m, const T* va
     second_moment<L, T>(fneq, pi);
     static_for<Q>([&](auto lc) {
       constexpr int l = decltype(lc)::value;
-      T qp = T(0);
-      static_for<n_pi<L>()>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        const T t = T(qi<L>(l, k)) * pi[k];
-        if constexpr (k == 0)
-          qp = t;
-        else
-          qp = qp + t;
-      });
-      g[l] = feq[l] + (T(9.0 / 2.0) * T(L::w(l))) * qp;
+      g[l] = feq[l] + hermite2_dir<L, T, l>(pi);
     });
   }
   static_for<Q>([&](auto lc) {
@@ -645,16 +652,7 @@ __device__ __forceinline__ void hybrid_cell(T (&f)[L::Q], const T (&pre)[L::Q], 
     second_moment<L, T>(fneq, pi);
     static_for<Q>([&](auto lc) {
       constexpr int l = decltype(lc)::value;
-      T qp = T(0);
-      static_for<n_pi<L>()>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        const T t = T(qi<L>(l, k)) * pi[k];
-        if constexpr (k == 0)
-          qp = t;
-        else
-          qp = qp + t;
-      });
-      f[l] = feq[l] + (T(4.5) * T(L::w(l))) * qp;
+      f[l] = feq[l] + hermite2_dir<L, T, l>(pi);
     });
   }
 }
@@ -688,7 +686,109 @@ __device__ __forceinline__ void smagorinsky(T (&f)[L::Q], const T (&feq)[L::Q], 
   });
 }
 
-// COLL: bits 0-1 = XLBHIP_BGK / XLBHIP_KBC / XLBHIP_SMAGORINSKY_LES_BGK, bit 2 = exact-difference forcing
+// ---- regularised BGK: fneq rebuilt from its Hermite moments (Latt & Chopard 2006; recursive third order: Malaspinas 2015) ----
+// Third-order moments follow from u and Pi: a_abc = u_a Pi_bc + u_b Pi_ac + u_c Pi_ab.  Each lattice carries the components its
+// third-order Hermite polynomials span (rank 2 / 6 / 7 on D2Q9 / D3Q19 / D3Q27; tests/test_regularized_ref.py re-derives them):
+//   a_aab = 2 u_a Pi_ab + u_b Pi_aa for a != b, in the order xxy, xxz, xyy, yyz, xzz, yzz (D2Q9: xxy, xyy); D3Q27 adds a_xyz.
+//   D3Q19: H_xyz vanishes and the six H_aab couple in the pairs (xxy, yzz), (xxz, yyz), (xyy, xzz) — Gram [[2, -1], [-1, 2]] / 27 —
+//   so it carries the pairs' sums and differences (the form of Jacob, Malaspinas & Sagaut 2018).
+template <class L>
+constexpr int n_a3() {
+  return L::ID == XLBHIP_D2Q9 ? 2 : (L::ID == XLBHIP_D3Q19 ? 6 : 7);
+}
+// user axes (alpha, beta) of the m-th a_aab: alpha-major over alpha != beta
+template <class L>
+constexpr int a3_axis(int m, bool beta) {
+  int n = 0;
+  for (int al = 0; al < L::D; ++al)
+    for (int be = 0; be < L::D; ++be) {
+      if (al == be) continue;
+      if (n == m) return beta ? be : al;
+      ++n;
+    }
+  return 0;
+}
+// slot of Pi_ab (a <= b, user axes) in second_moment's order
+template <class L>
+constexpr int pi_slot(int a, int b) {
+  int n = 0;
+  for (int i = 0; i < L::D; ++i)
+    for (int j = i; j < L::D; ++j) {
+      if (i == a && j == b) return n;
+      ++n;
+    }
+  return 0;
+}
+// 3 H_aab,l = (3 c_a^2 - 1) c_b of the m-th a_aab
+template <class L>
+constexpr int h3(int l, int m) {
+  const int ca = cu<L>(a3_axis<L>(m, false), l), cb = cu<L>(a3_axis<L>(m, true), l);
+  return (3 * ca * ca - 1) * cb;
+}
+// weight of the j-th carried third-order value in f3_l, in units of 4.5 w_l (an integer: 13.5 H_aab = 4.5 * 3 H_aab,
+// 27 H_xyz = 4.5 * 6 c_x c_y c_z; D3Q19: 13.5 (H_p + H_q) = 4.5 (3 H_p + 3 H_q), 4.5 (H_p - H_q) = 4.5 (3 H_p - 3 H_q) / 3)
+template <class L>
+constexpr int n3(int l, int j) {
+  if constexpr (L::ID == XLBHIP_D3Q19) {
+    constexpr int P[3] = {0, 1, 2}, Qm[3] = {5, 3, 4};
+    const int hp = h3<L>(l, P[j / 2]), hq = h3<L>(l, Qm[j / 2]);
+    return j % 2 == 0 ? hp + hq : (hp - hq) / 3;
+  } else {
+    if (j < L::D * (L::D - 1)) return h3<L>(l, j);
+    return 6 * cu<L>(0, l) * cu<L>(1, l) * cu<L>(2, l);
+  }
+}
+
+template <class L, class T>
+__device__ __forceinline__ void third_moment(const T (&u)[3], const T (&pi)[6], T (&a)[7]) {
+  constexpr int O = 3 - L::D, NAAB = L::D * (L::D - 1);
+  T aab[6];
+  static_for<NAAB>([&](auto mc) {
+    constexpr int m = decltype(mc)::value, al = a3_axis<L>(m, false), be = a3_axis<L>(m, true);
+    constexpr int kab = al < be ? pi_slot<L>(al, be) : pi_slot<L>(be, al), kaa = pi_slot<L>(al, al);
+    aab[m] = (T(2.0) * u[al + O]) * pi[kab] + u[be + O] * pi[kaa];
+  });
+  if constexpr (L::ID == XLBHIP_D3Q19) {
+    a[0] = aab[0] + aab[5];
+    a[1] = aab[0] - aab[5];
+    a[2] = aab[1] + aab[3];
+    a[3] = aab[1] - aab[3];
+    a[4] = aab[2] + aab[4];
+    a[5] = aab[2] - aab[4];
+  } else {
+    static_for<NAAB>([&](auto mc) { a[decltype(mc)::value] = aab[decltype(mc)::value]; });
+    if constexpr (L::ID == XLBHIP_D3Q27) a[6] = (u[0] * pi[4] + u[1] * pi[2]) + u[2] * pi[1];
+  }
+}
+
+// f' = feq + (1 - omega) (f1 [+ f3]): ORDER 2 is the projected form, ORDER 3 the recursive one.  (rho is not used: Pi is the moment of
+// fneq itself, so it and the a_abc built from it carry the density already.)
+template <class L, class T, int ORDER>
+__device__ __forceinline__ void regularized(T (&f)[L::Q], const T (&feq)[L::Q], T /*rho*/, const T (&u)[3], T omega) {
+  T fneq[L::Q];
+  static_for<L::Q>([&](auto lc) {
+    constexpr int l = decltype(lc)::value;
+    fneq[l] = f[l] - feq[l];
+  });
+  T pi[6];
+  second_moment<L, T>(fneq, pi);
+  T a[7];
+  if constexpr (ORDER == 3) third_moment<L, T>(u, pi, a);
+  const T keep = T(1.0) - omega;
+  static_for<L::Q>([&](auto lc) {
+    constexpr int l = decltype(lc)::value;
+    T r = hermite2_dir<L, T, l>(pi);
+    if constexpr (ORDER == 3) {
+      static_for<n_a3<L>()>([&](auto jc) {
+        constexpr int j = decltype(jc)::value, n = n3<L>(l, j);
+        if constexpr (n != 0) r = r + T(4.5 * L::w(l) * n) * a[j];
+      });
+    }
+    f[l] = feq[l] + keep * r;
+  });
+}
+
+// COLL: bits 0-1 = XLBHIP_BGK / XLBHIP_KBC / XLBHIP_SMAGORINSKY_LES_BGK / COLL_REGULARIZED, bit 2 = exact-difference forcing
 // fp32 BGK with the population pairs (l, opp l) evaluated by PACKED fp32 instructions (v_pk_add_f32 /
 // v_pk_mul_f32: two IEEE-rounded results per lane per issue).  On MI355X a packed instruction costs the SIMD as much
 // as its two scalar halves (the guide's "anti-lever" beside MFMAs), so this does not raise the VALU peak; what it buys
@@ -956,6 +1056,14 @@ __device__ __forceinline__ void block_sum3_add(T fx, T fy, T fz, double* force /
 }
 
 constexpr int COLL_FORCED = 4;  // (COLL_FAST = 8 is defined with kbc_fast above)
+// The regularised collisions take the base value the public ids leave free; COLL_RECURSIVE adds the third-order moments.
+// (The public ids XLBHIP_REGULARIZED_BGK = 3 and XLBHIP_RECURSIVE_REGULARIZED_BGK = 4 map to these through coll_of_public.)
+constexpr int COLL_REGULARIZED = 3;
+constexpr int COLL_RECURSIVE = 32;
+constexpr int coll_of_public(int collision) {
+  return collision == XLBHIP_REGULARIZED_BGK ? COLL_REGULARIZED
+                                             : (collision == XLBHIP_RECURSIVE_REGULARIZED_BGK ? (COLL_REGULARIZED | COLL_RECURSIVE) : collision);
+}
 
 struct CollideExtra {
   double force[3];
@@ -989,8 +1097,10 @@ __device__ __forceinline__ void collide(T (&f)[L::Q], T omega, const CollideExtr
       bgk<L, T>(f, feq, omega);
     else if constexpr (BASE == XLBHIP_KBC)
       kbc<L, T>(f, feq, omega);
-    else
+    else if constexpr (BASE == XLBHIP_SMAGORINSKY_LES_BGK)
       smagorinsky<L, T>(f, feq, omega, T(ex.smag_cs));
+    else
+      regularized<L, T, (COLL & COLL_RECURSIVE) != 0 ? 3 : 2>(f, feq, rho, u, omega);
     if constexpr (FORCED) {
       // forced_collision.py:47-49 + exact_difference_force.py:80-82
       T rho2, u2[3];

@@ -146,8 +146,14 @@ __global__ void k_collide(FieldView f, FieldView feq, FieldView fout, Dims d, T 
     bgk<L, T>(ff, fe, omega);
   else if constexpr (COLL == XLBHIP_KBC)
     kbc<L, T>(ff, fe, omega);
-  else
+  else if constexpr (COLL == XLBHIP_SMAGORINSKY_LES_BGK)
     smagorinsky<L, T>(ff, fe, omega, smag_cs);
+  else {
+    static_assert((COLL & 3) == COLL_REGULARIZED, "collision not built for the stand-alone operator");
+    T rho, u[3];
+    moments<L, T>(ff, rho, u);
+    regularized<L, T, (COLL & COLL_RECURSIVE) != 0 ? 3 : 2>(ff, fe, rho, u, omega);
+  }
   const size_t o = cell_index(fout, d, x, y, z);
   static_for<L::Q>([&](auto lc) {
     constexpr int l = decltype(lc)::value;

@@ -202,6 +202,10 @@ int step2_report_items(const Step2Launch& p, int32_t* out, int* eff_segments, in
 int launch_step_d2q9_ext(const StepLaunch& p, int coll);
 int launch_step_d3q19_ext(const StepLaunch& p, int coll);
 int launch_step_d3q27_ext(const StepLaunch& p, int coll);
+// regularised collisions (cell.hpp COLL_REGULARIZED [| COLL_RECURSIVE] [| COLL_FORCED]); the three policies of launch_step_ext
+int launch_step_d2q9_reg(const StepLaunch& p, int coll);
+int launch_step_d3q19_reg(const StepLaunch& p, int coll);
+int launch_step_d3q27_reg(const StepLaunch& p, int coll);
 int launch_step_d2q9_bgk(const StepLaunch& p);
 int launch_step_d2q9_kbc(const StepLaunch& p);
 int launch_step_d3q19_bgk(const StepLaunch& p);

@@ -89,6 +89,12 @@ namespace xlb {
 
 static int launch_any(const xlbhip_stepper* s, const StepLaunch& p) {
   XLB_REQUIRE(p.n_prof == 0 || p.prof_vals, "step launch without its profile table (timestep not staged)");
+  if (s->collision == XLBHIP_REGULARIZED_BGK || s->collision == XLBHIP_RECURSIVE_REGULARIZED_BGK) {
+    const int coll = coll_of_public(s->collision) | (s->forced ? COLL_FORCED : 0);
+    if (s->lattice == XLBHIP_D2Q9) return launch_step_d2q9_reg(p, coll);
+    if (s->lattice == XLBHIP_D3Q19) return launch_step_d3q19_reg(p, coll);
+    return launch_step_d3q27_reg(p, coll);
+  }
   if (s->forced || s->collision == XLBHIP_SMAGORINSKY_LES_BGK) {
     const int coll = s->collision | (s->forced ? COLL_FORCED : 0);
     if (s->lattice == XLBHIP_D2Q9) return launch_step_d2q9_ext(p, coll);
@@ -536,7 +542,7 @@ int xlbhip_stepper_create(xlbhip_ctx* c, int lattice, int collision, int cdt, in
                           xlbhip_stepper** out) {
   XLB_REQUIRE(c && out, "null argument");
   XLB_REQUIRE(lattice_q(lattice) > 0, "unknown lattice %d", lattice);
-  XLB_REQUIRE(collision == XLBHIP_BGK || collision == XLBHIP_KBC || collision == XLBHIP_SMAGORINSKY_LES_BGK, "unknown collision %d", collision);
+  XLB_REQUIRE(collision >= XLBHIP_BGK && collision <= XLBHIP_RECURSIVE_REGULARIZED_BGK, "unknown collision %d", collision);
   XLB_REQUIRE(!(collision == XLBHIP_KBC && lattice == XLBHIP_D3Q19), "Velocity set not supported: D3Q19 has no KBC (reference kbc.py:65-66)");
   XLB_REQUIRE(cdt == XLBHIP_F32 || cdt == XLBHIP_F64, "bad compute dtype %d", cdt);
   XLB_REQUIRE(is_float(sdt) && dtype_size(sdt) <= dtype_size(cdt), "bad store dtype %d for compute dtype %d", sdt, cdt);

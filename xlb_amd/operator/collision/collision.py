@@ -1,5 +1,6 @@
 """Collision operators BGK and KBC as stand-alone whole-field operators
-(reference xlb/operator/collision/bgk.py:27-32,:78-91 and kbc.py:40-79)."""
+(reference xlb/operator/collision/bgk.py:27-32,:78-91 and kbc.py:40-79), Smagorinsky LES BGK, and the
+regularised BGK collisions, which the reference does not have."""
 
 from ... import _lib
 from ...compute_backend import ComputeBackend
@@ -60,4 +61,28 @@ class SmagorinskyLESBGK(Collision):
     @Operator.register_backend(ComputeBackend.HIP)
     def hip_implementation(self, f, feq, fout, omega):
         self._ctx.set_option("smagorinsky_coef_e6", round(self.smagorinsky_coef * 1e6))
+        return self._launch(f, feq, fout, omega)
+
+
+class RegularizedBGK(Collision):
+    """Regularised BGK, projected form (Latt and Chopard 2006): fout = feq + (1 - omega) f1, where f1 is the projection of
+    f - feq on the second-order Hermite polynomials — the part that carries the stress.  Everything else in f - feq (the ghost
+    modes that make BGK blow up as omega -> 2) is dropped at every step.  All three lattices; the viscosity is BGK's."""
+
+    hip_collision_id = _lib.REGULARIZED_BGK
+
+    @Operator.register_backend(ComputeBackend.HIP)
+    def hip_implementation(self, f, feq, fout, omega):
+        return self._launch(f, feq, fout, omega)
+
+
+class RecursiveRegularizedBGK(Collision):
+    """Regularised BGK, recursive form (Malaspinas 2015): the projected form plus the third-order Hermite moments that follow
+    from u and the stress, a_abc = u_a Pi_bc + u_b Pi_ac + u_c Pi_ab, on the components each lattice carries (D3Q19: the three
+    coupled pairs of Jacob, Malaspinas and Sagaut 2018).  rho and u are f's own moments."""
+
+    hip_collision_id = _lib.RECURSIVE_REGULARIZED_BGK
+
+    @Operator.register_backend(ComputeBackend.HIP)
+    def hip_implementation(self, f, feq, fout, omega):
         return self._launch(f, feq, fout, omega)

@@ -73,7 +73,7 @@ from ... import _lib
 from ...helper.ibm_helper import IBMBody, RigidDynamics, RigidMotion, declare_bodies  # noqa: F401  (re-exported: they are this stepper's vocabulary)
 from ...compute_backend import ComputeBackend
 from ..operator import Operator
-from .nse_stepper import IncompressibleNavierStokesStepper, refuse_unsupported
+from .nse_stepper import IncompressibleNavierStokesStepper, refuse_regularized, refuse_unsupported
 
 
 class IBMMarkers:
@@ -123,6 +123,7 @@ class LagrangianForces:
 class IBMStepper(IncompressibleNavierStokesStepper):
     def __init__(self, grid, boundary_conditions=[], collision_type="BGK", use_scoped_timer=False, ibm_max_iterations=4, ibm_tolerance=1e-5,
                  ibm_relaxation=1.0):
+        refuse_regularized("IBMStepper", collision_type)
         # the pairing of reference-style calls is off: every call runs its step at once
         super().__init__(grid, boundary_conditions, collision_type=collision_type, backend_config={"lazy_pairs": False})
         if self.velocity_set.d != 3:

@@ -45,7 +45,7 @@ from ...helper.nse_fields import create_nse_fields
 from ...precision_policy import Precision
 from ..boundary_condition import HybridBC, ImplementationStep
 from ..boundary_masker import IndicesBoundaryMasker
-from ..collision import BGK, KBC, SmagorinskyLESBGK
+from ..collision import BGK, KBC, RecursiveRegularizedBGK, RegularizedBGK, SmagorinskyLESBGK
 from ..equilibrium import QuadraticEquilibrium
 from ..macroscopic import Macroscopic
 from ..operator import Operator
@@ -68,6 +68,16 @@ def refuse_unsupported(name, precision_policy, grid, boundary_conditions=(), hyb
             raise NotImplementedError(f"{name}: {type(bc).__name__} with a profile (per-cell or time-dependent values) is not supported")
         if also is not None:
             also(bc)
+
+
+REGULARIZED_COLLISIONS = ("RegularizedBGK", "RecursiveRegularizedBGK")
+
+
+def refuse_regularized(name, collision_type):
+    """The steppers with a coupled kernel of their own have no regularised form of it."""
+    if collision_type in REGULARIZED_COLLISIONS:
+        raise NotImplementedError(f"{name}: collision_type {collision_type!r} is not supported; the coupled step is built for BGK, KBC and "
+                                  "SmagorinskyLESBGK")
 
 
 def chunk_plan(n_steps, ring_slots):
@@ -104,8 +114,13 @@ class IncompressibleNavierStokesStepper(Stepper):
             self.collision = KBC(vs, pp, be)
         elif collision_type == "SmagorinskyLESBGK":
             self.collision = SmagorinskyLESBGK(vs, pp, be)
+        elif collision_type in REGULARIZED_COLLISIONS:
+            # single-step kernel, three precision policies, one rank (slab grids are untested with it: refused)
+            refuse_unsupported(f"collision_type {collision_type!r}", pp, grid)
+            self.collision = (RegularizedBGK if collision_type == "RegularizedBGK" else RecursiveRegularizedBGK)(vs, pp, be)
         else:
-            raise NotImplementedError(f"collision_type {collision_type!r} is not available on the HIP backend (BGK, KBC, SmagorinskyLESBGK)")
+            raise NotImplementedError(f"collision_type {collision_type!r} is not available on the HIP backend "
+                                      "(BGK, KBC, SmagorinskyLESBGK, RegularizedBGK, RecursiveRegularizedBGK)")
         if force_vector is not None and force_vector.shape != (vs.d,):
             raise AssertionError("Check the dimensions of the input force!")  # forced_collision.py:41
         self.stream = Stream(vs, pp, be)

@@ -45,12 +45,13 @@ from ..boundary_condition import FullwayBounceBackBC
 from ..boundary_condition.scalar_boundary_condition import ScalarBoundaryCondition, ScalarDirichletBC
 from ..collision import SmagorinskyLESBGK
 from ..operator import Operator
-from .nse_stepper import IncompressibleNavierStokesStepper, refuse_unsupported
+from .nse_stepper import IncompressibleNavierStokesStepper, refuse_regularized, refuse_unsupported
 
 
 class ScalarTransportStepper(IncompressibleNavierStokesStepper):
     def __init__(self, grid, boundary_conditions=[], scalar_boundary_conditions=[], collision_type="BGK", buoyancy=None, scalar_reference=0.0,
                  force_vector=None):
+        refuse_regularized("ScalarTransportStepper", collision_type)
         super().__init__(grid, boundary_conditions, collision_type=collision_type, force_vector=force_vector, backend_config={"lazy_pairs": False})
         vs = self.velocity_set
         refuse_unsupported("ScalarTransportStepper", self.precision_policy, grid, self.boundary_conditions, hybrid="HybridBC is not supported by the coupled kernel")
