@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 from oracle import xlb_numpy as orc
+from xlb_amd import _lib
+from xlb_amd.default_config import get_context
 from xlb_amd.grid import grid_factory
 from xlb_amd.operator.boundary_condition import (DoNothingBC, EquilibriumBC, ExtrapolationOutflowBC, FullwayBounceBackBC, HalfwayBounceBackBC, HybridBC,
                                                  RegularizedBC, ZouHeBC)
@@ -313,3 +315,6 @@ def test_refusals_at_construction():
         init_hip("D3Q19", policy)
         with pytest.raises(NotImplementedError, match="fp16"):
             AdjointStepper(IncompressibleNavierStokesStepper(grid=grid_factory(shape)))
+    # below that Python refusal: the adjoint kernels are built for three policies, and the create says so
+    with pytest.raises(_lib.HipBackendError, match="built for FP32FP32, FP64FP64 and FP64FP32 only"):
+        _lib.Adjoint(get_context(), _lib.D3Q19, _lib.F32, _lib.F16, [])

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 
 from oracle import xlb_numpy as orc
+from xlb_amd import _lib
+from xlb_amd.default_config import get_context
 from xlb_amd.grid import grid_factory
 from xlb_amd.operator.boundary_condition import FullwayBounceBackBC, HalfwayBounceBackBC
 from xlb_amd.operator.stepper import CarnahanStarling, MultiphaseStepper, ShanChenDensity, ShanChenExponential
@@ -233,6 +235,9 @@ def test_the_native_layer_refuses_what_the_kernels_cannot_take():
     with pytest.raises(Exception, match="different fields"):
         stepper.run(f_0, f_0, bc_mask, missing_mask, 1.0, 1)
     assert np.array_equal(f_1.numpy(), before)  # nothing was launched
+    # below the Python refusal of fp16 storage: the kernels are built for three policies, and the create says so
+    with pytest.raises(_lib.HipBackendError, match="built for FP32FP32, FP64FP64 and FP64FP32 only"):
+        _lib.Multiphase(get_context(), _lib.D3Q19, _lib.F32, _lib.F16, [])
 
 
 # ---- refusals at construction ----------------------------------------------------------------------------------------------------------

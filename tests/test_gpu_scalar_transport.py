@@ -305,3 +305,6 @@ def test_the_native_layer_refuses_what_the_kernel_cannot_take():
     with pytest.raises(_lib.HipBackendError, match="different fields"):
         _lib.Scalar.run(stepper._scalar_native(), f_0, f_1, g_0, g_0, bc_mask, missing_mask, 1.0, 1.0, 0, 1)
     assert np.array_equal(f_1.numpy(), before[0]) and np.array_equal(g_1.numpy(), before[1])  # nothing was launched
+    # below the Python refusal of fp16 storage: the coupled kernels are built for three policies, and the create says so
+    with pytest.raises(_lib.HipBackendError, match="built for FP32FP32, FP64FP64 and FP64FP32 only"):
+        _lib.Scalar(get_context(), _lib.D3Q19, _lib.BGK, _lib.F32, _lib.F16, [])

@@ -1,17 +1,12 @@
 // libxlbhip: the discrete adjoint of the fused BGK step.  The object owns the boundary tables (a BcTables like a stepper's,
 // stepper_tables.hpp), the carried-state scratch field of a single adjoint step, the per-block partial sums and the device scalar dL/domega;
 // a step enqueues its kernels on the context's compute stream, and only omega_gradient waits for the device.
-#include <memory>
-
 #include "adjoint_launch.hpp"
 #include "stepper_tables.hpp"
 
 using namespace xlb;
 
-struct xlbhip_adjoint {
-  xlbhip_ctx* ctx = nullptr;
-  int lattice = 0, cdt = 0, sdt = 0;
-  BcTables bc;
+struct xlbhip_adjoint : RowStepper {
   DeviceBuf mu;          // the carried state between the two launches of a single step (store dtype, q planes)
   size_t mu_elems = 0;
   DeviceBuf partial;     // fp64 [blocks], then [chunks of blocks]: the two levels below the device scalar
@@ -46,14 +41,8 @@ static int check_adjoint_fields(const xlbhip_adjoint* s, const xlbhip_field* f_n
                                 const xlbhip_field* miss) {
   XLB_REQUIRE(s && lin && lout, "null argument");
   XLB_REQUIRE(lin != lout && lin->data != lout->data, "lam_in and lam_out must be different fields");
-  const int q = lattice_q(s->lattice);
-  for (const xlbhip_field* f : {f_n, lin, lout}) {
-    if (!f) continue;
-    XLB_REQUIRE(f->card == q, "adjoint step: state and cotangent fields must have cardinality %d", q);
-    XLB_REQUIRE(f->dtype == s->sdt, "adjoint step: state and cotangent fields must have the store dtype %d", s->sdt);
-    XLB_REQUIRE(f->halo == 0, "adjoint step: fields without ghost planes only (single rank)");
-    XLB_REQUIRE(same_grid(f, lin), "the fields of an adjoint step must share one grid");
-  }
+  // (f_n may be null: a launch that leaves lam reads no forward state; every field's stride goes to the kernel, so they may differ)
+  if (int rc = check_row_fields("adjoint step", "state and cotangent fields", lattice_q(s->lattice), s->sdt, {f_n, lin, lout}, false)) return rc;
   return check_single_rank_grid("adjoint step", "kernel", s->lattice, s->bc.n_bc, lin, bcm, miss);
 }
 
@@ -109,13 +98,7 @@ static int adjoint_launch_once(xlbhip_adjoint* s, const xlbhip_field* f_n, const
   q.out_mode = out_mode;
   q.partial = s->partial.get<double>();
   q.gmask = s->gmask.get<const uint32_t>();
-  int rc;
-  if (s->lattice == XLBHIP_D2Q9)
-    rc = launch_adjoint_d2q9(q);
-  else if (s->lattice == XLBHIP_D3Q19)
-    rc = launch_adjoint_d3q19(q);
-  else
-    rc = launch_adjoint_d3q27(q);
+  const int rc = launch_for_lattice(s->lattice, launch_adjoint_d2q9, launch_adjoint_d3q19, launch_adjoint_d3q27, q);
   if (rc || out_mode != ADJ_OUT_MU) return rc;
   // the step's omega terms: per-block partials -> per-chunk sums -> the device scalar (a chunk per block; one block at the end)
   const unsigned n = (unsigned)adjoint_blocks(p.nx, p.ny, p.nz), chunks = (n + ADJ_CHUNK - 1) / ADJ_CHUNK;
@@ -137,37 +120,19 @@ static int adjoint_launch_once(xlbhip_adjoint* s, const xlbhip_field* f_n, const
 extern "C" {
 
 int xlbhip_adjoint_create(xlbhip_ctx* c, int lattice, int cdt, int sdt, int n_bc, const xlbhip_bc_desc* bcs, xlbhip_adjoint** out) {
-  XLB_REQUIRE(c && out, "null argument");
-  XLB_REQUIRE(lattice_q(lattice) > 0, "unknown lattice %d", lattice);
-  XLB_REQUIRE((cdt == XLBHIP_F32 && sdt == XLBHIP_F32) || (cdt == XLBHIP_F64 && (sdt == XLBHIP_F64 || sdt == XLBHIP_F32)),
-              "the adjoint step is built for FP32FP32, FP64FP64 and FP64FP32 only (got compute=%d store=%d)", cdt, sdt);
-  XLB_REQUIRE(n_bc == 0 || bcs, "null bc list");
-  BcImage image;
   const auto refusal = [](int kind) {
     return bc_adjoint_accepts(kind) ? nullptr
                                     : "adjoint step: bc kind %d is not supported (equilibrium, halfway and fullway bounce-back and do-nothing only)";
   };
-  if (int rc = bc_image(lattice, n_bc, bcs, refusal, image)) return rc;
-  XLB_HIP(hipSetDevice(c->device));
-  auto s = std::make_unique<xlbhip_adjoint>();
-  s->ctx = c;
-  s->lattice = lattice;
-  s->cdt = cdt;
-  s->sdt = sdt;
-  if (int rc = s->bc.upload(cdt, image)) return rc;
-  XLB_HIP(s->domega.alloc(sizeof(double)));
-  XLB_HIP(hipMemset(s->domega.get(), 0, sizeof(double)));
-  *out = s.release();
-  return 0;
+  const auto own = [](xlbhip_adjoint& s) {
+    XLB_HIP(s.domega.alloc(sizeof(double)));
+    XLB_HIP(hipMemset(s.domega.get(), 0, sizeof(double)));
+    return 0;
+  };
+  return create_row_stepper(c, lattice, cdt, sdt, n_bc, bcs, ADJOINT_POLICY_SUBJECT, refusal, own, out);
 }
 
-int xlbhip_adjoint_destroy(xlbhip_adjoint* s) {
-  if (!s) return 0;
-  (void)hipSetDevice(s->ctx->device);
-  (void)hipStreamSynchronize(s->ctx->stream);
-  delete s;
-  return 0;
-}
+int xlbhip_adjoint_destroy(xlbhip_adjoint* s) { return destroy_drained(s); }
 
 int xlbhip_adjoint_step(xlbhip_adjoint* s, const xlbhip_field* f_n, const xlbhip_field* lam_in, xlbhip_field* lam_out, const xlbhip_field* bc_mask,
                         const xlbhip_field* missing_mask, double omega) {

@@ -1,5 +1,6 @@
 // Type-erased launch descriptor of the fused adjoint step and the per-lattice dispatcher that each adjoint_<lattice>.hip
-// instantiates (the scheme of step_launch.hpp; the forward part's arguments are step_args', the block is launch_shape.hpp's).
+// instantiates.  From step_launch.hpp: the forward part's arguments (step_args), the policies (by_three_policies) and the launch
+// (launch_rows); the block is launch_shape.hpp's.
 #pragma once
 #include "adjoint_step_kernel.hpp"
 #include "common.hpp"
@@ -25,6 +26,9 @@ inline size_t adjoint_blocks(int nx, int ny, int nz) {
   return (size_t)sh.gx * sh.gy * sh.gz;
 }
 
+// in whose name by_three_policies refuses a policy (the launch and xlbhip_adjoint_create)
+constexpr const char* ADJOINT_POLICY_SUBJECT = "the adjoint step is";
+
 template <class L, class T, class S, int IN, int OUT, int HASBC>
 int launch_adjoint_typed(const AdjointLaunch& q) {
   const StepLaunch& p = q.f;
@@ -36,12 +40,7 @@ int launch_adjoint_typed(const AdjointLaunch& q) {
   aa.out_stride = q.out_stride;
   aa.partial = q.partial;
   aa.gmask = q.gmask;
-  const RowBlockShape sh = adjoint_geometry(p.nx, p.ny, p.nz);
-  const dim3 block(sh.tz, sh.ty, 1), grid(sh.gx, sh.gy, sh.gz);
-  XLB_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "grid too large: ny/ty=%u nx=%u", grid.y, grid.z);
-  hipLaunchKernelGGL((k_adjoint_step<L, T, S, IN, OUT, HASBC>), grid, block, 0, p.stream, aa);
-  XLB_HIP(hipGetLastError());
-  return 0;
+  return launch_rows(k_adjoint_step<L, T, S, IN, OUT, HASBC>, adjoint_geometry(p.nx, p.ny, p.nz), p.stream, aa);
 }
 
 template <class L, class T, class S, int HASBC>
@@ -59,11 +58,8 @@ int launch_adjoint_policy(const AdjointLaunch& q) {
 
 template <class L>
 int launch_adjoint_lattice(const AdjointLaunch& q) {
-  const int c = q.f.compute_dtype, s = q.f.store_dtype;
-  if (c == XLBHIP_F32 && s == XLBHIP_F32) return launch_adjoint_policy<L, float, float>(q);
-  if (c == XLBHIP_F64 && s == XLBHIP_F64) return launch_adjoint_policy<L, double, double>(q);
-  if (c == XLBHIP_F64 && s == XLBHIP_F32) return launch_adjoint_policy<L, double, float>(q);
-  XLB_FAIL("the adjoint step is built for FP32FP32, FP64FP64 and FP64FP32 only (got compute=%d store=%d)", c, s);
+  return by_three_policies(ADJOINT_POLICY_SUBJECT, q.f.compute_dtype, q.f.store_dtype,
+                           [&](auto T, auto S) { return launch_adjoint_policy<L, decltype(T), decltype(S)>(q); });
 }
 
 // defined one per translation unit (adjoint_<lattice>.hip)

@@ -11,6 +11,7 @@
 #include "ibm_kernels.hpp"
 #include "ibm_motion_kernels.hpp"
 #include "ibm_state.hpp"
+#include "stepper_tables.hpp"
 
 using namespace xlb;
 
@@ -268,11 +269,7 @@ int xlbhip_ibm_create(xlbhip_ctx* c, xlbhip_stepper* stepper, int lattice, int c
 }
 
 int xlbhip_ibm_destroy(xlbhip_ibm* b) {
-  if (!b) return 0;
-  (void)hipSetDevice(b->ctx->device);
-  (void)hipStreamSynchronize(b->ctx->stream);  // copies may still read the pinned buffers
-  delete b;
-  return 0;
+  return destroy_drained(b);  // (the drain: copies may still read the pinned buffers)
 }
 
 int xlbhip_ibm_set_markers(xlbhip_ibm* b, int64_t n, const float* positions, const float* areas, const float* velocities) {
@@ -339,14 +336,9 @@ int xlbhip_ibm_run(xlbhip_ibm* b, xlbhip_field* f_a, xlbhip_field* f_b, const xl
                    int64_t first_timestep, int64_t n_steps, int* result_in_b) {
   XLB_REQUIRE(b && result_in_b && n_steps >= 0, "bad argument");
   if (int rc = b->bodies.require_poses(first_timestep, n_steps)) return rc;  // (before anything is enqueued)
-  xlbhip_field* cur = f_a;
-  xlbhip_field* oth = f_b;
-  for (int64_t i = 0; i < n_steps; ++i) {
-    if (int rc = xlbhip_ibm_step(b, cur, oth, bc_mask, missing_mask, omega, first_timestep + i)) return rc;
-    std::swap(cur, oth);
-  }
-  *result_in_b = cur == f_b ? 1 : 0;
-  return 0;
+  return run_alternating(n_steps, result_in_b, [&](int64_t i, bool odd) {
+    return xlbhip_ibm_step(b, odd ? f_b : f_a, odd ? f_a : f_b, bc_mask, missing_mask, omega, first_timestep + i);
+  });
 }
 
 int xlbhip_ibm_forces(xlbhip_ibm* b, int64_t n, double* forces) {

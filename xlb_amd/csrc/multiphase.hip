@@ -2,7 +2,6 @@
 // stepper_tables.hpp), the wall pseudopotentials by bc id and the psi field (one value per cell in the compute dtype, allocated at
 // first use); a step enqueues k_psi and k_step_multiphase on the context's compute stream, and nothing here waits for the device.
 #include <cmath>
-#include <memory>
 #include <vector>
 
 #include "multiphase_launch.hpp"
@@ -10,10 +9,7 @@
 
 using namespace xlb;
 
-struct xlbhip_multiphase {
-  xlbhip_ctx* ctx = nullptr;
-  int lattice = 0, cdt = 0, sdt = 0;
-  BcTables bc;
+struct xlbhip_multiphase : RowStepper {
   DeviceBuf psi_wall;  // [256] compute dtype: Psi(rho_w) by bc id
   DeviceBuf psi;       // [psi_cells] compute dtype
   size_t psi_cells = 0;
@@ -25,11 +21,10 @@ struct xlbhip_multiphase {
 
 namespace xlb {
 
-static int check_multiphase_grid(const xlbhip_multiphase* s, const xlbhip_field* f, const xlbhip_field* bcm, const xlbhip_field* miss) {
-  const int q = lattice_q(s->lattice);
-  XLB_REQUIRE(f->card == q, "population fields must have cardinality %d", q);
-  XLB_REQUIRE(f->dtype == s->sdt, "population fields must have the store dtype %d", s->sdt);
-  XLB_REQUIRE(f->halo == 0, "multiphase: fields without ghost planes only (single rank)");
+// the population field f, with f_other (or nullptr) its double-buffering partner, and the masks
+static int check_multiphase_grid(const xlbhip_multiphase* s, const xlbhip_field* f, const xlbhip_field* f_other, const xlbhip_field* bcm,
+                                 const xlbhip_field* miss) {
+  if (int rc = check_row_fields("multiphase", "population fields", lattice_q(s->lattice), s->sdt, {f, f_other}, true)) return rc;
   return check_single_rank_grid("multiphase", "step kernel", s->lattice, s->bc.n_bc, f, bcm, miss);
 }
 
@@ -68,9 +63,7 @@ static MultiphaseLaunch multiphase_launch(const xlbhip_multiphase* s, const xlbh
 }
 
 static int multiphase_dispatch(const xlbhip_multiphase* s, const MultiphaseLaunch& q, MultiphaseKernel which) {
-  if (s->lattice == XLBHIP_D2Q9) return launch_multiphase_d2q9(q, which);
-  if (s->lattice == XLBHIP_D3Q19) return launch_multiphase_d3q19(q, which);
-  return launch_multiphase_d3q27(q, which);
+  return launch_for_lattice(s->lattice, launch_multiphase_d2q9, launch_multiphase_d3q19, launch_multiphase_d3q27, q, which);
 }
 
 // one step f(t) -> f(t + 1): psi of the post-streaming state, then the forced step that reads it
@@ -86,9 +79,7 @@ static int check_multiphase_step(xlbhip_multiphase* s, const xlbhip_field* fa, c
                                  double omega) {
   XLB_REQUIRE(s && fa && fb, "null argument");
   XLB_REQUIRE(fa != fb, "f_0 and f_1 must be different fields (double buffering)");
-  if (int rc = check_multiphase_grid(s, fa, bcm, miss)) return rc;
-  XLB_REQUIRE(fb->card == fa->card && fb->dtype == fa->dtype && fb->halo == 0 && same_grid(fb, fa) && fb->plane_stride == fa->plane_stride,
-              "f_0 / f_1 layouts differ");
+  if (int rc = check_multiphase_grid(s, fa, fb, bcm, miss)) return rc;
   if (int rc = check_relaxation("omega", omega)) return rc;
   XLB_HIP(hipSetDevice(s->ctx->device));
   return ensure_psi(s, fa);
@@ -98,7 +89,7 @@ static int check_multiphase_step(xlbhip_multiphase* s, const xlbhip_field* fa, c
 static int multiphase_outputs(xlbhip_multiphase* s, const xlbhip_field* f, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, xlbhip_field* rho,
                               xlbhip_field* u, xlbhip_field* force) {
   XLB_REQUIRE(s && f, "null argument");
-  if (int rc = check_multiphase_grid(s, f, bc_mask, missing_mask)) return rc;
+  if (int rc = check_multiphase_grid(s, f, nullptr, bc_mask, missing_mask)) return rc;
   const int d = lattice_d(s->lattice);
   if (int rc = check_multiphase_output(s, "rho", rho, 1, f)) return rc;
   if (int rc = check_multiphase_output(s, "u", u, d, f)) return rc;
@@ -122,38 +113,19 @@ static int multiphase_outputs(xlbhip_multiphase* s, const xlbhip_field* f, const
 extern "C" {
 
 int xlbhip_multiphase_create(xlbhip_ctx* c, int lattice, int cdt, int sdt, int n_bc, const xlbhip_bc_desc* bcs, xlbhip_multiphase** out) {
-  XLB_REQUIRE(c && out, "null argument");
-  XLB_REQUIRE(lattice_q(lattice) > 0, "unknown lattice %d", lattice);
-  XLB_REQUIRE((cdt == XLBHIP_F32 && sdt == XLBHIP_F32) || (cdt == XLBHIP_F64 && (sdt == XLBHIP_F64 || sdt == XLBHIP_F32)),
-              "the multiphase step is built for FP32FP32, FP64FP64 and FP64FP32 only (got compute=%d store=%d)", cdt, sdt);
-  XLB_REQUIRE(n_bc == 0 || bcs, "null bc list");
-  BcImage image;
   const auto refusal = [](int kind) {
     return bc_multiphase_accepts(kind) ? nullptr
                                        : "multiphase: bc kind %d is not supported (halfway bounce-back with a constant wall velocity and fullway "
                                          "bounce-back only: the missing directions of other kinds have no neighbour pseudopotential)";
   };
-  if (int rc = bc_image(lattice, n_bc, bcs, refusal, image)) return rc;
-  for (int i = 0; i < n_bc; ++i) XLB_REQUIRE(bcs[i].id != (int)BC_ID_SOLID, "multiphase: bc id 255 is the solid cells' id");
-  XLB_HIP(hipSetDevice(c->device));
-  auto s = std::make_unique<xlbhip_multiphase>();
-  s->ctx = c;
-  s->lattice = lattice;
-  s->cdt = cdt;
-  s->sdt = sdt;
-  if (int rc = s->bc.upload(cdt, image)) return rc;
-  if (int rc = upload_values(cdt, std::vector<double>(256, 0.0), s->psi_wall)) return rc;
-  *out = s.release();
-  return 0;
+  const auto own = [&](xlbhip_multiphase& s) {
+    for (int i = 0; i < n_bc; ++i) XLB_REQUIRE(bcs[i].id != (int)BC_ID_SOLID, "multiphase: bc id 255 is the solid cells' id");
+    return upload_values(cdt, std::vector<double>(256, 0.0), s.psi_wall);
+  };
+  return create_row_stepper(c, lattice, cdt, sdt, n_bc, bcs, MULTIPHASE_POLICY_SUBJECT, refusal, own, out);
 }
 
-int xlbhip_multiphase_destroy(xlbhip_multiphase* s) {
-  if (!s) return 0;
-  (void)hipSetDevice(s->ctx->device);
-  (void)hipStreamSynchronize(s->ctx->stream);
-  delete s;
-  return 0;
-}
+int xlbhip_multiphase_destroy(xlbhip_multiphase* s) { return destroy_drained(s); }
 
 int xlbhip_multiphase_set_model(xlbhip_multiphase* s, int form, double g, int n_params, const double* params, const double* force) {
   XLB_REQUIRE(s, "null argument");
@@ -202,18 +174,14 @@ int xlbhip_multiphase_run(xlbhip_multiphase* s, xlbhip_field* f_a, xlbhip_field*
   (void)first_timestep;
   XLB_REQUIRE(result_in_b && n_steps >= 0, "bad argument");
   if (int rc = check_multiphase_step(s, f_a, f_b, bc_mask, missing_mask, omega)) return rc;
-  xlbhip_field *fc = f_a, *fo = f_b;
-  for (int64_t i = 0; i < n_steps; ++i) {
-    if (int rc = multiphase_step_once(s, fc, fo, bc_mask, missing_mask, omega)) return rc;
-    std::swap(fc, fo);
-  }
-  *result_in_b = fc == f_b ? 1 : 0;
-  return 0;
+  return run_alternating(n_steps, result_in_b, [&](int64_t, bool odd) {
+    return odd ? multiphase_step_once(s, f_b, f_a, bc_mask, missing_mask, omega) : multiphase_step_once(s, f_a, f_b, bc_mask, missing_mask, omega);
+  });
 }
 
 int xlbhip_multiphase_psi(xlbhip_multiphase* s, const xlbhip_field* f, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, xlbhip_field* psi) {
   XLB_REQUIRE(s && f && psi, "null argument");
-  if (int rc = check_multiphase_grid(s, f, bc_mask, missing_mask)) return rc;
+  if (int rc = check_multiphase_grid(s, f, nullptr, bc_mask, missing_mask)) return rc;
   if (int rc = check_multiphase_output(s, "psi", psi, 1, f)) return rc;
   XLB_HIP(hipSetDevice(s->ctx->device));
   touch(psi);

@@ -1,6 +1,6 @@
 // Type-erased launch descriptor of the Shan-Chen step's kernels and the per-lattice dispatcher that each multiphase_<lattice>.hip
-// instantiates (the scheme of scalar_launch.hpp; the fluid's arguments are step_args', the block is launch_shape.hpp's).  One cell per
-// thread: there are no `vec` variants.
+// instantiates.  From step_launch.hpp: the fluid's arguments (step_args), the policies (by_three_policies) and the launch (launch_rows);
+// the block is launch_shape.hpp's.  One cell per thread: there are no `vec` variants.
 #pragma once
 #include "common.hpp"
 #include "multiphase_step_kernel.hpp"
@@ -22,6 +22,9 @@ struct MultiphaseLaunch {
   size_t u_stride, force_stride;
 };
 
+// in whose name by_three_policies refuses a policy (the launch and xlbhip_multiphase_create)
+constexpr const char* MULTIPHASE_POLICY_SUBJECT = "the multiphase step is";
+
 template <class L, class T, class S, int HASBC>
 int launch_multiphase_typed(const MultiphaseLaunch& q, MultiphaseKernel which) {
   const StepLaunch& p = q.f;
@@ -38,17 +41,10 @@ int launch_multiphase_typed(const MultiphaseLaunch& q, MultiphaseKernel which) {
   ma.out_force = static_cast<T*>(q.out_force);
   ma.u_stride = q.u_stride;
   ma.force_stride = q.force_stride;
-  const RowBlockShape sh = row_block_shape(p.nz, p.ny, p.nx, 256, 0);
-  const dim3 block(sh.tz, sh.ty, 1), grid(sh.gx, sh.gy, sh.gz);
-  XLB_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "grid too large: ny/ty=%u nx=%u", grid.y, grid.z);
-  if (which == MultiphaseKernel::psi)
-    hipLaunchKernelGGL((k_psi<L, T, S, HASBC>), grid, block, 0, p.stream, ma);
-  else if (which == MultiphaseKernel::step)
-    hipLaunchKernelGGL((k_step_multiphase<L, T, S, HASBC>), grid, block, 0, p.stream, ma);
-  else
-    hipLaunchKernelGGL((k_multiphase_out<L, T, S, HASBC>), grid, block, 0, p.stream, ma);
-  XLB_HIP(hipGetLastError());
-  return 0;
+  void (*const kernel)(MultiphaseArgs<T, S>) = which == MultiphaseKernel::psi    ? k_psi<L, T, S, HASBC>
+                                               : which == MultiphaseKernel::step ? k_step_multiphase<L, T, S, HASBC>
+                                                                                 : k_multiphase_out<L, T, S, HASBC>;
+  return launch_rows(kernel, row_block_shape(p.nz, p.ny, p.nx, 256, 0), p.stream, ma);
 }
 
 template <class L, class T, class S>
@@ -58,11 +54,8 @@ int launch_multiphase_policy(const MultiphaseLaunch& q, MultiphaseKernel which) 
 
 template <class L>
 int launch_multiphase_lattice(const MultiphaseLaunch& q, MultiphaseKernel which) {
-  const int c = q.f.compute_dtype, s = q.f.store_dtype;
-  if (c == XLBHIP_F32 && s == XLBHIP_F32) return launch_multiphase_policy<L, float, float>(q, which);
-  if (c == XLBHIP_F64 && s == XLBHIP_F64) return launch_multiphase_policy<L, double, double>(q, which);
-  if (c == XLBHIP_F64 && s == XLBHIP_F32) return launch_multiphase_policy<L, double, float>(q, which);
-  XLB_FAIL("the multiphase step is built for FP32FP32, FP64FP64 and FP64FP32 only (got compute=%d store=%d)", c, s);
+  return by_three_policies(MULTIPHASE_POLICY_SUBJECT, q.f.compute_dtype, q.f.store_dtype,
+                           [&](auto T, auto S) { return launch_multiphase_policy<L, decltype(T), decltype(S)>(q, which); });
 }
 
 // defined one per translation unit (multiphase_<lattice>.hip)

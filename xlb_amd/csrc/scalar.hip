@@ -2,7 +2,6 @@
 // stepper_tables.hpp; and the scalar's rule and value by bc id); a step enqueues the coupled kernel and the fluid's outflow pass on the
 // context's compute stream, and nothing here waits for the device.
 #include <cmath>
-#include <memory>
 #include <vector>
 
 #include "scalar_launch.hpp"
@@ -10,10 +9,8 @@
 
 using namespace xlb;
 
-struct xlbhip_scalar {
-  xlbhip_ctx* ctx = nullptr;
-  int lattice = 0, collision = 0, cdt = 0, sdt = 0;
-  BcTables bc;         // the fluid's
+struct xlbhip_scalar : RowStepper {  // (bc: the fluid's)
+  int collision = 0;
   DeviceBuf sc_rule;   // uint8 [256] SCALAR_*
   DeviceBuf sc_value;  // [256] compute dtype
   bool forced = false;
@@ -34,15 +31,9 @@ static int check_scalar_fields(const xlbhip_scalar* s, const xlbhip_field* fa, c
                                const xlbhip_field* bcm, const xlbhip_field* miss) {
   XLB_REQUIRE(s && fa && fb && ga && gb, "null argument");
   XLB_REQUIRE(fa != fb && ga != gb, "f_0 / f_1 and g_0 / g_1 must be different fields (double buffering)");
-  const int q = lattice_q(s->lattice), qs = scalar_q(s->lattice);
-  XLB_REQUIRE(fa->card == q && fb->card == q, "population fields must have cardinality %d", q);
-  XLB_REQUIRE(ga->card == qs && gb->card == qs, "scalar population fields must have cardinality %d", qs);
-  for (const xlbhip_field* f : {fa, fb, ga, gb}) {
-    XLB_REQUIRE(f->dtype == s->sdt, "population fields must have the store dtype %d", s->sdt);
-    XLB_REQUIRE(f->halo == 0, "scalar transport: fields without ghost planes only (single rank)");
-    XLB_REQUIRE(same_grid(f, fa), "the fields of a scalar-transport step must share one grid");
-  }
-  XLB_REQUIRE(fa->plane_stride == fb->plane_stride && ga->plane_stride == gb->plane_stride, "f_0 / f_1 or g_0 / g_1 layouts differ");
+  if (int rc = check_row_fields("scalar transport", "population fields", lattice_q(s->lattice), s->sdt, {fa, fb}, true)) return rc;
+  if (int rc = check_row_fields("scalar transport", "scalar population fields", scalar_q(s->lattice), s->sdt, {ga, gb}, true)) return rc;
+  XLB_REQUIRE(same_grid(ga, fa), "scalar transport: the fields of a step must share one grid");
   return check_single_rank_grid("scalar transport", "step kernel", s->lattice, s->bc.n_bc, fa, bcm, miss);
 }
 
@@ -75,14 +66,7 @@ static int scalar_step_once(xlbhip_scalar* s, const xlbhip_field* fs, xlbhip_fie
   q.cp = s->cp;
   q.omega_s = omega_s;
   const int coll = s->collision | (s->forced ? COLL_FORCED : 0);
-  int rc;
-  if (s->lattice == XLBHIP_D2Q9)
-    rc = launch_scalar_d2q9(q, coll);
-  else if (s->lattice == XLBHIP_D3Q19)
-    rc = launch_scalar_d3q19(q, coll);
-  else
-    rc = launch_scalar_d3q27(q, coll);
-  if (rc) return rc;
+  if (int rc = launch_for_lattice(s->lattice, launch_scalar_d2q9, launch_scalar_d3q19, launch_scalar_d3q27, q, coll)) return rc;
   return outflow_aux(c, s->lattice, s->cdt, s->bc, CellTables(), fs, fd, bcm, miss);
 }
 
@@ -91,38 +75,19 @@ static int scalar_step_once(xlbhip_scalar* s, const xlbhip_field* fs, xlbhip_fie
 extern "C" {
 
 int xlbhip_scalar_create(xlbhip_ctx* c, int lattice, int collision, int cdt, int sdt, int n_bc, const xlbhip_bc_desc* bcs, xlbhip_scalar** out) {
-  XLB_REQUIRE(c && out, "null argument");
-  XLB_REQUIRE(lattice_q(lattice) > 0, "unknown lattice %d", lattice);
   XLB_REQUIRE(collision == XLBHIP_BGK || collision == XLBHIP_KBC || collision == XLBHIP_SMAGORINSKY_LES_BGK, "unknown collision %d", collision);
   XLB_REQUIRE(!(collision == XLBHIP_KBC && lattice == XLBHIP_D3Q19), "Velocity set not supported: D3Q19 has no KBC (reference kbc.py:65-66)");
-  XLB_REQUIRE((cdt == XLBHIP_F32 && sdt == XLBHIP_F32) || (cdt == XLBHIP_F64 && (sdt == XLBHIP_F64 || sdt == XLBHIP_F32)),
-              "scalar transport is built for FP32FP32, FP64FP64 and FP64FP32 only (got compute=%d store=%d)", cdt, sdt);
-  XLB_REQUIRE(n_bc == 0 || bcs, "null bc list");
-  BcImage image;
   const auto refusal = [](int kind) {
     return bc_scalar_accepts(kind) ? nullptr : "scalar transport: bc kind %d (HybridBC, profile walls) is not supported by the coupled step";
   };
-  if (int rc = bc_image(lattice, n_bc, bcs, refusal, image)) return rc;
-  XLB_HIP(hipSetDevice(c->device));
-  auto s = std::make_unique<xlbhip_scalar>();
-  s->ctx = c;
-  s->lattice = lattice;
-  s->collision = collision;
-  s->cdt = cdt;
-  s->sdt = sdt;
-  if (int rc = s->bc.upload(cdt, image)) return rc;
-  if (int rc = upload_rules(s.get(), std::vector<uint8_t>(256, SCALAR_ADIABATIC), std::vector<double>(256, 0.0))) return rc;
-  *out = s.release();
-  return 0;
+  const auto own = [&](xlbhip_scalar& s) {
+    s.collision = collision;
+    return upload_rules(&s, std::vector<uint8_t>(256, SCALAR_ADIABATIC), std::vector<double>(256, 0.0));
+  };
+  return create_row_stepper(c, lattice, cdt, sdt, n_bc, bcs, SCALAR_POLICY_SUBJECT, refusal, own, out);
 }
 
-int xlbhip_scalar_destroy(xlbhip_scalar* s) {
-  if (!s) return 0;
-  (void)hipSetDevice(s->ctx->device);
-  (void)hipStreamSynchronize(s->ctx->stream);
-  delete s;
-  return 0;
-}
+int xlbhip_scalar_destroy(xlbhip_scalar* s) { return destroy_drained(s); }
 
 int xlbhip_scalar_set_rules(xlbhip_scalar* s, int n, const int32_t* bc_ids, const int32_t* rules, const double* values) {
   XLB_REQUIRE(s && n >= 0 && (n == 0 || (bc_ids && rules && values)), "bad argument");
@@ -210,14 +175,10 @@ int xlbhip_scalar_run(xlbhip_scalar* s, xlbhip_field* f_a, xlbhip_field* f_b, xl
   if (int rc = check_scalar_fields(s, f_a, f_b, g_a, g_b, bc_mask, missing_mask)) return rc;
   if (int rc = check_omegas(omega, omega_scalar)) return rc;
   XLB_HIP(hipSetDevice(s->ctx->device));
-  xlbhip_field *fc = f_a, *fo = f_b, *gc = g_a, *go = g_b;
-  for (int64_t i = 0; i < n_steps; ++i) {
-    if (int rc = scalar_step_once(s, fc, fo, gc, go, bc_mask, missing_mask, omega, omega_scalar)) return rc;
-    std::swap(fc, fo);
-    std::swap(gc, go);
-  }
-  *result_in_b = fc == f_b ? 1 : 0;
-  return 0;
+  return run_alternating(n_steps, result_in_b, [&](int64_t, bool odd) {
+    return odd ? scalar_step_once(s, f_b, f_a, g_b, g_a, bc_mask, missing_mask, omega, omega_scalar)
+               : scalar_step_once(s, f_a, f_b, g_a, g_b, bc_mask, missing_mask, omega, omega_scalar);
+  });
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // Type-erased launch descriptor of the coupled fluid + scalar step and the per-lattice dispatcher that each scalar_<lattice>.hip
-// instantiates (the scheme of step_launch.hpp; the fluid's arguments are step_args', the block is launch_shape.hpp's).
+// instantiates.  From step_launch.hpp: the fluid's arguments (step_args), the policies (by_three_policies) and the launch (launch_rows);
+// the block is launch_shape.hpp's.
 #pragma once
 #include "common.hpp"
 #include "scalar_step_kernel.hpp"
@@ -18,6 +19,9 @@ struct ScalarLaunch {
   double omega_s;
 };
 
+// in whose name by_three_policies refuses a policy (the launch and xlbhip_scalar_create)
+constexpr const char* SCALAR_POLICY_SUBJECT = "scalar transport is";
+
 template <class L, class T, class S, int VEC, int COLL, int HASBC>
 int launch_scalar_typed(const ScalarLaunch& q) {
   const StepLaunch& p = q.f;
@@ -30,12 +34,7 @@ int launch_scalar_typed(const ScalarLaunch& q) {
   sa.sc_value = static_cast<const T*>(q.sc_value);
   sa.cp = q.cp;
   sa.omega_s = static_cast<T>(q.omega_s);
-  const RowBlockShape sh = row_block_shape(sa.f.nzq, p.ny, p.nx, 256, 0);
-  const dim3 block(sh.tz, sh.ty, 1), grid(sh.gx, sh.gy, sh.gz);
-  XLB_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "grid too large: ny/ty=%u nx=%u", grid.y, grid.z);
-  hipLaunchKernelGGL((k_step_scalar<L, T, S, VEC, COLL, HASBC>), grid, block, 0, p.stream, sa);
-  XLB_HIP(hipGetLastError());
-  return 0;
+  return launch_rows(k_step_scalar<L, T, S, VEC, COLL, HASBC>, row_block_shape(sa.f.nzq, p.ny, p.nx, 256, 0), p.stream, sa);
 }
 
 template <class L, class T, class S, int COLL>
@@ -51,11 +50,8 @@ int launch_scalar_policy(const ScalarLaunch& q) {
 
 template <class L, int COLL>
 int launch_scalar_coll(const ScalarLaunch& q) {
-  const int c = q.f.compute_dtype, s = q.f.store_dtype;
-  if (c == XLBHIP_F32 && s == XLBHIP_F32) return launch_scalar_policy<L, float, float, COLL>(q);
-  if (c == XLBHIP_F64 && s == XLBHIP_F64) return launch_scalar_policy<L, double, double, COLL>(q);
-  if (c == XLBHIP_F64 && s == XLBHIP_F32) return launch_scalar_policy<L, double, float, COLL>(q);
-  XLB_FAIL("scalar transport is built for FP32FP32, FP64FP64 and FP64FP32 only (got compute=%d store=%d)", c, s);
+  return by_three_policies(SCALAR_POLICY_SUBJECT, q.f.compute_dtype, q.f.store_dtype,
+                           [&](auto T, auto S) { return launch_scalar_policy<L, decltype(T), decltype(S), COLL>(q); });
 }
 
 // coll: XLBHIP_BGK / KBC / SMAGORINSKY_LES_BGK, | COLL_FORCED with a force vector or buoyancy

@@ -1,16 +1,6 @@
-// Instantiates the fused step kernel for D3Q27 with the regularised collisions (projected and recursive,
-// each with and without exact-difference forcing): cell.hpp regularized.
+// Instantiates the fused step kernel for D3Q27 with the regularised collisions (step_launch.hpp: launch_step_reg_lattice).
 #include "step_launch.hpp"
 
 namespace xlb {
-int launch_step_d3q27_reg(const StepLaunch& p, int coll) {
-  constexpr int RR = COLL_REGULARIZED | COLL_RECURSIVE;
-  switch (coll) {
-    case COLL_REGULARIZED: return launch_step_ext<D3Q27, COLL_REGULARIZED>(p);
-    case COLL_REGULARIZED | COLL_FORCED: return launch_step_ext<D3Q27, COLL_REGULARIZED | COLL_FORCED>(p);
-    case RR: return launch_step_ext<D3Q27, RR>(p);
-    case RR | COLL_FORCED: return launch_step_ext<D3Q27, RR | COLL_FORCED>(p);
-  }
-  XLB_FAIL("collision variant %d not built for D3Q27", coll);
-}
+int launch_step_d3q27_reg(const StepLaunch& p, int coll) { return launch_step_reg_lattice<D3Q27>(p, coll); }
 }  // namespace xlb

@@ -1,6 +1,8 @@
 // Type-erased launch descriptor + the per-(lattice, collision) dispatcher that each
-// step_*.hip translation unit instantiates.  step_args is the one copy StepLaunch -> StepArgs of every launcher of a StepLaunch (this
-// file's, scalar_launch.hpp, adjoint_launch.hpp, step2_launch.hpp); the block shape of the row kernels is launch_shape.hpp's.
+// step_*.hip translation unit instantiates.  What every launcher of a StepLaunch shares (this file's, scalar_launch.hpp,
+// adjoint_launch.hpp, multiphase_launch.hpp; step2_launch.hpp takes step_args) is defined once here: step_args, the one copy
+// StepLaunch -> StepArgs; by_three_policies, the precision policies of every kernel family but the plain ones; launch_rows, the launch
+// of a row kernel on a block shape of launch_shape.hpp; launch_for_lattice, the choice among a family's three per-lattice units.
 #pragma once
 #include "common.hpp"
 #include "launch_shape.hpp"
@@ -101,6 +103,40 @@ StepArgs<T, S> step_args(const StepLaunch& p, int vec) {
   return a;
 }
 
+// The precision policies every kernel family but the plain BGK / KBC steps is built for (to bound build time): FP32FP32, FP64FP64
+// and FP64FP32
+inline bool three_policies(int compute_dtype, int store_dtype) {
+  return (compute_dtype == XLBHIP_F32 && store_dtype == XLBHIP_F32) ||
+         (compute_dtype == XLBHIP_F64 && (store_dtype == XLBHIP_F64 || store_dtype == XLBHIP_F32));
+}
+
+// f(T{}, S{}) with (T, S) the compute and store types of one of the three policies; any other pair is refused in the name of
+// `subject` ("scalar transport is", "... collisions are")
+template <class F>
+int by_three_policies(const char* subject, int compute_dtype, int store_dtype, F&& f) {
+  XLB_REQUIRE(three_policies(compute_dtype, store_dtype), "%s built for FP32FP32, FP64FP64 and FP64FP32 only (got compute=%d store=%d)", subject,
+              compute_dtype, store_dtype);
+  if (store_dtype == XLBHIP_F64) return f(double{}, double{});
+  return compute_dtype == XLBHIP_F64 ? f(double{}, float{}) : f(float{}, float{});
+}
+
+// One launch of a row kernel (k_step, k_step_scalar, k_adjoint_step, the multiphase kernels) on `stream`: block and grid of `sh`,
+// with the grid's y and z inside what the device takes
+template <class Args>
+int launch_rows(void (*kernel)(Args), const RowBlockShape& sh, hipStream_t stream, const Args& a) {
+  const dim3 block(sh.tz, sh.ty, 1), grid(sh.gx, sh.gy, sh.gz);
+  XLB_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "grid too large: ny/ty=%u x_count=%u", grid.y, grid.z);
+  hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
+  XLB_HIP(hipGetLastError());
+  return 0;
+}
+
+// The entry point of `lattice` among the three of a kernel family (each is defined in a translation unit of its own), called with `a`
+template <class Entry, class... A>
+int launch_for_lattice(int lattice, Entry* d2q9, Entry* d3q19, Entry* d3q27, const A&... a) {
+  return (lattice == XLBHIP_D2Q9 ? d2q9 : lattice == XLBHIP_D3Q19 ? d3q19 : d3q27)(a...);
+}
+
 template <class L, class T, class S, int VEC, int COLL, int HASBC, int FLAGS>
 int launch_typed(const StepLaunch& p) {
   StepArgs<T, S> a = step_args<T, S>(p, VEC);
@@ -115,13 +151,9 @@ int launch_typed(const StepLaunch& p) {
   a.extra.force[2] = p.force[2];
   const int threads = p.block_threads > 0 ? p.block_threads : 256;
   const RowBlockShape sh = row_block_shape(a.nzq, p.ny, p.x_count, threads, p.block_tz);
-  const dim3 block(sh.tz, sh.ty, 1), grid(sh.gx, sh.gy, sh.gz);
   XLB_REQUIRE(threads <= (VEC == 1 ? XLB_LB1 : 256), "block_threads %d exceeds the kernel's launch bound", threads);
-  a.xcd_swizzle = (p.xcd_swizzle && grid.x > 1 && grid.y % 8 == 0) ? 1 : 0;
-  XLB_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "grid too large: ny/ty=%u x_count=%u", grid.y, grid.z);
-  hipLaunchKernelGGL((k_step<L, T, S, VEC, COLL, HASBC, FLAGS>), grid, block, 0, p.stream, a);
-  XLB_HIP(hipGetLastError());
-  return 0;
+  a.xcd_swizzle = (p.xcd_swizzle && sh.gx > 1 && sh.gy % 8 == 0) ? 1 : 0;
+  return launch_rows(k_step<L, T, S, VEC, COLL, HASBC, FLAGS>, sh, p.stream, a);
 }
 
 template <class L, class T, class S, int VEC, int COLL, int HASBC>
@@ -167,14 +199,40 @@ int launch_step(const StepLaunch& p) {
   XLB_FAIL("unsupported precision policy compute=%d store=%d", c, s);
 }
 
-// Extended collisions (Smagorinsky LES, exact-difference forcing): three policies only, to bound build time
+// Extended and regularised collisions: three policies only, to bound build time
 template <class L, int COLL>
 int launch_step_ext(const StepLaunch& p) {
-  const int c = p.compute_dtype, s = p.store_dtype;
-  if (c == XLBHIP_F32 && s == XLBHIP_F32) return launch_policy<L, float, float, COLL>(p);
-  if (c == XLBHIP_F64 && s == XLBHIP_F64) return launch_policy<L, double, double, COLL>(p);
-  if (c == XLBHIP_F64 && s == XLBHIP_F32) return launch_policy<L, double, float, COLL>(p);
-  XLB_FAIL("SmagorinskyLESBGK / forced collisions are built for FP32FP32, FP64FP64 and FP64FP32 only (got compute=%d store=%d)", c, s);
+  return by_three_policies("SmagorinskyLESBGK / forced collisions are", p.compute_dtype, p.store_dtype,
+                           [&](auto T, auto S) { return launch_policy<L, decltype(T), decltype(S), COLL>(p); });
+}
+
+// The variants of a step_<lattice>_ext.hip unit.  coll: XLBHIP_SMAGORINSKY_LES_BGK [| COLL_FORCED], or XLBHIP_BGK / XLBHIP_KBC |
+// COLL_FORCED (Smagorinsky LES, exact-difference forcing: SURVEY.md section 8f rank 3)
+template <class L>
+int launch_step_ext_lattice(const StepLaunch& p, int coll) {
+  switch (coll) {
+    case XLBHIP_SMAGORINSKY_LES_BGK: return launch_step_ext<L, XLBHIP_SMAGORINSKY_LES_BGK>(p);
+    case XLBHIP_SMAGORINSKY_LES_BGK | COLL_FORCED: return launch_step_ext<L, XLBHIP_SMAGORINSKY_LES_BGK | COLL_FORCED>(p);
+    case XLBHIP_BGK | COLL_FORCED: return launch_step_ext<L, XLBHIP_BGK | COLL_FORCED>(p);
+  }
+  if constexpr (L::ID != XLBHIP_D3Q19) {
+    if (coll == (XLBHIP_KBC | COLL_FORCED)) return launch_step_ext<L, XLBHIP_KBC | COLL_FORCED>(p);
+  }
+  XLB_FAIL("collision variant %d not built for D%dQ%d", coll, L::D, L::Q);
+}
+
+// The variants of a step_<lattice>_reg.hip unit.  coll: COLL_REGULARIZED [| COLL_RECURSIVE] [| COLL_FORCED] (cell.hpp regularized:
+// projected and recursive, each with and without exact-difference forcing)
+template <class L>
+int launch_step_reg_lattice(const StepLaunch& p, int coll) {
+  constexpr int RR = COLL_REGULARIZED | COLL_RECURSIVE;
+  switch (coll) {
+    case COLL_REGULARIZED: return launch_step_ext<L, COLL_REGULARIZED>(p);
+    case COLL_REGULARIZED | COLL_FORCED: return launch_step_ext<L, COLL_REGULARIZED | COLL_FORCED>(p);
+    case RR: return launch_step_ext<L, RR>(p);
+    case RR | COLL_FORCED: return launch_step_ext<L, RR | COLL_FORCED>(p);
+  }
+  XLB_FAIL("collision variant %d not built for D%dQ%d", coll, L::D, L::Q);
 }
 
 // fp64-compute policies only (the fast KBC variant: cell.hpp kbc_fast)
@@ -199,10 +257,10 @@ int launch_step2_d3q27_kbc(const Step2Launch& p);
 int step2_build_clean(const Step2Launch& p, uint8_t* out);
 int step2_items(const Step2Launch& p);
 int step2_report_items(const Step2Launch& p, int32_t* out, int* eff_segments, int* eff_cap);  // out: device memory, 3 words per item
+// (the definitions are launch_step_ext_lattice<L> and launch_step_reg_lattice<L>)
 int launch_step_d2q9_ext(const StepLaunch& p, int coll);
 int launch_step_d3q19_ext(const StepLaunch& p, int coll);
 int launch_step_d3q27_ext(const StepLaunch& p, int coll);
-// regularised collisions (cell.hpp COLL_REGULARIZED [| COLL_RECURSIVE] [| COLL_FORCED]); the three policies of launch_step_ext
 int launch_step_d2q9_reg(const StepLaunch& p, int coll);
 int launch_step_d3q19_reg(const StepLaunch& p, int coll);
 int launch_step_d3q27_reg(const StepLaunch& p, int coll);

@@ -69,10 +69,8 @@ struct Step2Caches {
 //   scratch field   re-created when the population fields' shape or dtype differs (can_fuse2)
 //   strip buffers   (the fields' own, common.hpp) valid iff strips_version == version && strips_oz == the launch's tile_oz
 //   profile ring    dropped whenever the profile table's layout changes (ProfileTables::rebuild)
-struct xlbhip_stepper {
-  xlbhip_ctx* ctx = nullptr;
-  int lattice = 0, collision = 0, cdt = 0, sdt = 0;
-  BcTables bc;
+struct xlbhip_stepper : RowStepper {
+  int collision = 0;
   Step2Caches pairs;
   ProfileTables prof;  // per-cell prescribed values and per-timestep wall velocities (profile_tables.hpp)
   bool forced = false;
@@ -91,15 +89,11 @@ static int launch_any(const xlbhip_stepper* s, const StepLaunch& p) {
   XLB_REQUIRE(p.n_prof == 0 || p.prof_vals, "step launch without its profile table (timestep not staged)");
   if (s->collision == XLBHIP_REGULARIZED_BGK || s->collision == XLBHIP_RECURSIVE_REGULARIZED_BGK) {
     const int coll = coll_of_public(s->collision) | (s->forced ? COLL_FORCED : 0);
-    if (s->lattice == XLBHIP_D2Q9) return launch_step_d2q9_reg(p, coll);
-    if (s->lattice == XLBHIP_D3Q19) return launch_step_d3q19_reg(p, coll);
-    return launch_step_d3q27_reg(p, coll);
+    return launch_for_lattice(s->lattice, launch_step_d2q9_reg, launch_step_d3q19_reg, launch_step_d3q27_reg, p, coll);
   }
   if (s->forced || s->collision == XLBHIP_SMAGORINSKY_LES_BGK) {
     const int coll = s->collision | (s->forced ? COLL_FORCED : 0);
-    if (s->lattice == XLBHIP_D2Q9) return launch_step_d2q9_ext(p, coll);
-    if (s->lattice == XLBHIP_D3Q19) return launch_step_d3q19_ext(p, coll);
-    return launch_step_d3q27_ext(p, coll);
+    return launch_for_lattice(s->lattice, launch_step_d2q9_ext, launch_step_d3q19_ext, launch_step_d3q27_ext, p, coll);
   }
   if (s->lattice == XLBHIP_D2Q9) return s->collision == XLBHIP_BGK ? launch_step_d2q9_bgk(p) : launch_step_d2q9_kbc(p);
   if (s->lattice == XLBHIP_D3Q19) return launch_step_d3q19_bgk(p);
@@ -540,27 +534,18 @@ extern "C" {
 
 int xlbhip_stepper_create(xlbhip_ctx* c, int lattice, int collision, int cdt, int sdt, int n_bc, const xlbhip_bc_desc* bcs,
                           xlbhip_stepper** out) {
-  XLB_REQUIRE(c && out, "null argument");
-  XLB_REQUIRE(lattice_q(lattice) > 0, "unknown lattice %d", lattice);
   XLB_REQUIRE(collision >= XLBHIP_BGK && collision <= XLBHIP_RECURSIVE_REGULARIZED_BGK, "unknown collision %d", collision);
   XLB_REQUIRE(!(collision == XLBHIP_KBC && lattice == XLBHIP_D3Q19), "Velocity set not supported: D3Q19 has no KBC (reference kbc.py:65-66)");
   XLB_REQUIRE(cdt == XLBHIP_F32 || cdt == XLBHIP_F64, "bad compute dtype %d", cdt);
   XLB_REQUIRE(is_float(sdt) && dtype_size(sdt) <= dtype_size(cdt), "bad store dtype %d for compute dtype %d", sdt, cdt);
-  XLB_REQUIRE(n_bc == 0 || bcs, "null bc list");
-  BcImage image;
-  if (int rc = bc_image(lattice, n_bc, bcs, [&](int kind) { return bc_stepper_refusal(lattice_q(lattice), kind); }, image)) return rc;
-  XLB_HIP(hipSetDevice(c->device));
-  auto s = std::make_unique<xlbhip_stepper>();  // (a failure below releases it and the tables uploaded so far)
-  s->ctx = c;
-  s->lattice = lattice;
-  s->collision = collision;
-  s->cdt = cdt;
-  s->sdt = sdt;
-  s->prof.ctx = c;
-  s->prof.cdt = cdt;
-  if (int rc = s->bc.upload(cdt, image)) return rc;
-  *out = s.release();
-  return 0;
+  const auto refusal = [&](int kind) { return bc_stepper_refusal(lattice_q(lattice), kind); };
+  const auto own = [&](xlbhip_stepper& s) {
+    s.collision = collision;
+    s.prof.ctx = c;
+    s.prof.cdt = cdt;
+    return 0;
+  };
+  return create_row_stepper(c, lattice, cdt, sdt, n_bc, bcs, nullptr, refusal, own, out);  // (all five policies: checked above)
 }
 
 }  // extern "C"
@@ -681,14 +666,11 @@ int xlbhip_stepper_set_smagorinsky(xlbhip_stepper* s, double coef) {
 }
 
 int xlbhip_stepper_destroy(xlbhip_stepper* s) {
-  if (!s) return 0;
-  (void)hipSetDevice(s->ctx->device);
-  (void)hipStreamSynchronize(s->ctx->stream);
-  s->prof.release();  // (explicitly here, after the drain: copies may still read the pinned rows)
-  s->pairs.forget_meta(s->ctx);
-  if (s->pairs.scratch) xlbhip_field_destroy(s->pairs.scratch);
-  delete s;  // (the device tables go with their owners)
-  return 0;
+  return destroy_drained(s, [&] {
+    s->prof.release();  // (explicitly here, after the drain: copies may still read the pinned rows)
+    s->pairs.forget_meta(s->ctx);
+    if (s->pairs.scratch) xlbhip_field_destroy(s->pairs.scratch);
+  });  // (the device tables go with their owners)
 }
 
 int xlbhip_step(xlbhip_stepper* s, const xlbhip_field* src, xlbhip_field* dst, const xlbhip_field* bcm, const xlbhip_field* miss,

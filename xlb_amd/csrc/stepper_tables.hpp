@@ -1,7 +1,11 @@
-// The device side of a stepper's boundary conditions, shared by stepper.hip, scalar.hip and adjoint.hip: BcTables owns the uploaded
-// tables and keeps the packed words, the flags and the host kinds of the image they came from (bc_tables.hpp parses the descriptors);
-// bc_launch fills the part of a StepLaunch the three steppers fill alike; outflow_aux is the pass after a step.
+// What the native objects that launch row kernels share (stepper.hip, scalar.hip, adjoint.hip, multiphase.hip).  The device side of
+// their boundary conditions: BcTables owns the uploaded tables and keeps the packed words, the flags and the host kinds of the image
+// they came from (bc_tables.hpp parses the descriptors); bc_launch fills the part of a StepLaunch they fill alike; outflow_aux is the
+// pass after a step.  Their life: RowStepper is what each carries, create_row_stepper the shared part of its create, destroy_drained
+// its destroy, run_alternating its run loop (ibm.hip takes the last two as well), check_row_fields what a step asks of its fields.
 #pragma once
+#include <initializer_list>
+#include <memory>
 #include <string>
 
 #include "api_internal.hpp"
@@ -30,6 +34,80 @@ template <class Refusal>
 static int bc_image(int lattice, int n_bc, const xlbhip_bc_desc* bcs, Refusal&& refusal, BcImage& out) {
   const std::string err = bc_parse(lattice_q(lattice), n_bc, bcs, refusal, out);
   XLB_REQUIRE(err.empty(), "%s", err.c_str());
+  return 0;
+}
+
+// What the four native objects that launch row kernels carry (the fluid stepper, scalar transport, the adjoint, the multiphase step)
+struct RowStepper {
+  xlbhip_ctx* ctx = nullptr;
+  int lattice = 0, cdt = 0, sdt = 0;
+  BcTables bc;
+};
+
+// The shared part of their xlbhip_*_create: the argument checks, the image of the descriptors (`refusal`: bc_image), the object on
+// the context's device with its boundary tables uploaded, then own(object) for the caller's own tables, and only then *out.
+// policy_subject: in whose name any policy but the three of by_three_policies is refused, or nullptr (the caller checked its dtypes).
+template <class Obj, class Refusal, class Own>
+static int create_row_stepper(xlbhip_ctx* c, int lattice, int cdt, int sdt, int n_bc, const xlbhip_bc_desc* bcs, const char* policy_subject,
+                              Refusal&& refusal, Own&& own, Obj** out) {
+  XLB_REQUIRE(c && out, "null argument");
+  XLB_REQUIRE(lattice_q(lattice) > 0, "unknown lattice %d", lattice);
+  if (policy_subject)  // (the launchers' dispatcher with nothing to launch: its refusal is the check, in the launchers' words)
+    if (int rc = by_three_policies(policy_subject, cdt, sdt, [](auto, auto) { return 0; })) return rc;
+  XLB_REQUIRE(n_bc == 0 || bcs, "null bc list");
+  BcImage image;
+  if (int rc = bc_image(lattice, n_bc, bcs, refusal, image)) return rc;
+  XLB_HIP(hipSetDevice(c->device));
+  auto s = std::make_unique<Obj>();  // (a failure below releases it and the tables uploaded so far)
+  s->ctx = c;
+  s->lattice = lattice;
+  s->cdt = cdt;
+  s->sdt = sdt;
+  if (int rc = s->bc.upload(cdt, image)) return rc;
+  if (int rc = own(*s)) return rc;
+  *out = s.release();
+  return 0;
+}
+
+// xlbhip_*_destroy of an object whose launches run on its context's compute stream: they may still read what it owns, so the stream
+// drains first; then release() for what has to go before the members do, then the object
+template <class Obj, class Release>
+static int destroy_drained(Obj* s, Release&& release) {
+  if (!s) return 0;
+  (void)hipSetDevice(s->ctx->device);
+  (void)hipStreamSynchronize(s->ctx->stream);
+  release();
+  delete s;
+  return 0;
+}
+template <class Obj>
+static int destroy_drained(Obj* s) {
+  return destroy_drained(s, [] {});
+}
+
+// xlbhip_*_run of a double-buffered step: step(i, odd) for i = 0 .. n_steps - 1, where an even step goes a -> b and an odd one
+// b -> a; *result_in_b says where the last one left the result
+template <class Step>
+static int run_alternating(int64_t n_steps, int* result_in_b, Step&& step) {
+  for (int64_t i = 0; i < n_steps; ++i)
+    if (int rc = step(i, (i & 1) != 0)) return rc;
+  *result_in_b = (int)(n_steps & 1);
+  return 0;
+}
+
+// What a single-rank row-kernel step asks of a family of its fields (null entries are skipped): `card` planes in the store dtype,
+// no ghost planes, one grid and, where the kernel takes one stride for all of them (one_stride), one plane stride
+static int check_row_fields(const char* who, const char* fields_name, int card, int sdt, std::initializer_list<const xlbhip_field*> fields, bool one_stride) {
+  const xlbhip_field* first = nullptr;
+  for (const xlbhip_field* f : fields) {
+    if (!f) continue;
+    if (!first) first = f;
+    XLB_REQUIRE(f->card == card, "%s: %s must have cardinality %d", who, fields_name, card);
+    XLB_REQUIRE(f->dtype == sdt, "%s: %s must have the store dtype %d", who, fields_name, sdt);
+    XLB_REQUIRE(f->halo == 0, "%s: fields without ghost planes only (single rank)", who);
+    XLB_REQUIRE(same_grid(f, first), "%s: the fields of a step must share one grid", who);
+    XLB_REQUIRE(!one_stride || f->plane_stride == first->plane_stride, "%s: the layouts of the %s differ", who, fields_name);
+  }
   return 0;
 }
 
