@@ -37,7 +37,7 @@ HYBRID_KINDS = (KIND_HYBRID_BB_REGULARIZED, KIND_HYBRID_BB_GRADS, KIND_HYBRID_NE
 
 
 def seg_tri_t(v, p, dvec, max_t):
-    """Moeller-Trumbore in fp32, the operation order of ops_kernels.hpp: seg_tri_t.  Returns t (np.float32) or None."""
+    """Moeller-Trumbore in fp32, the operation order of masker_kernels.hpp: seg_tri_t.  Returns t (np.float32) or None."""
     v = v.astype(F)
     e1, e2 = v[1] - v[0], v[2] - v[0]
     dx, dy, dz = (F(x) for x in dvec)

@@ -840,7 +840,7 @@ def mesh_mask_aabb(shape, lat, bc_id, vertices, bc_mask, missing_mask):
 
 
 def _seg_tri_hit(v, p, dvec, max_t):
-    """Moeller-Trumbore, fp32, the operation order of ops_kernels.hpp: seg_tri_hit"""
+    """Moeller-Trumbore, fp32, the operation order of masker_kernels.hpp: seg_tri_t"""
     F = np.float32
     v = v.astype(F)
     e1, e2 = v[1] - v[0], v[2] - v[0]

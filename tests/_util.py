@@ -116,6 +116,13 @@ def mesh_zoo():
     }
 
 
+# the zoo meshes small enough for the oracle's per-triangle loops (12 - 24 triangles), and the cases (mesh, lattice, method,
+# close_voxels) on which kernels and oracle must agree bit for bit: on the GPU and in the host-compiled emulation
+ORACLE_MESHES = ["box", "box_low_faces", "box_high_faces", "plate", "two_boxes", "box_zero_area", "integer_box"]
+ORACLE_CASES = [(name, "D3Q27", m, h) for name in ORACLE_MESHES for m, h in (("AABB", 0), ("RAY", 0), ("WINDING", 0), ("AABB_CLOSE", 2))]
+ORACLE_CASES += [(name, "D3Q19", m, h) for name in ("box_low_faces", "integer_box") for m, h in (("AABB", 0), ("RAY", 0), ("WINDING", 0), ("AABB_CLOSE", 1))]
+
+
 def icosphere(center, radius, subdivisions=2):
     """triangle soup (3 n, 3) of a sphere, counter-clockwise seen from outside, built procedurally (no STL reader here)"""
     t = (1.0 + 5.0**0.5) / 2.0

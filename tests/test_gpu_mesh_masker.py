@@ -11,7 +11,7 @@ from xlb_amd.operator.boundary_condition import FullwayBounceBackBC, HalfwayBoun
 from xlb_amd.operator.boundary_masker import BC_SOLID, MeshMaskerAABB, MeshVoxelizationMethod
 from xlb_amd.operator.stepper import IncompressibleNavierStokesStepper
 
-from _util import icosphere, init_hip
+from _util import icosphere, init_hip, mesh_zoo
 
 pytestmark = pytest.mark.gpu
 
@@ -126,3 +126,22 @@ def test_stepper_routes_ray_method():
     assert (bm_w.numpy() == 255).sum() > 20
     with pytest.raises(AssertionError, match="Unsupported voxelization method"):
         MeshVoxelizationMethod("OCTREE")
+
+
+@pytest.mark.parametrize("lattice", ["D3Q19", "D3Q27"])
+def test_aabb_and_ray_entry_points_vs_oracle(lattice):
+    """xlbhip_mesh_mask_aabb and xlbhip_mesh_mask_ray, which the Python maskers do not call (they go through xlbhip_mesh_mask), called
+    directly on fresh fields: the oracle's arrays bit for bit."""
+    from xlb_amd import _lib
+
+    vs, pp = init_hip(lattice)
+    lat = orc.Lattice(lattice)
+    verts, shape = mesh_zoo()["box"]  # 12 triangles in 18 x 16 x 14
+    verts = np.ascontiguousarray(verts, np.float32)
+    ctx = MeshMaskerAABB()._ctx
+    for entry, oracle in (("xlbhip_mesh_mask_aabb", orc.mesh_mask_aabb), ("xlbhip_mesh_mask_ray", orc.mesh_mask_ray)):
+        grid, f_0, f_1, missing_mask, bc_mask = create_nse_fields(shape)
+        _lib.check(getattr(_lib.load(), entry)(ctx.handle, vs.hip_id, 3, len(verts) // 3, verts.ctypes.data, bc_mask.handle, missing_mask.handle))
+        e_bc, e_mm = oracle(shape, lat, 3, verts, np.zeros((1,) + shape, np.uint8), np.zeros((lat.q,) + shape, bool))
+        assert (e_bc == 3).sum() > 100
+        assert np.array_equal(bc_mask.numpy(), e_bc) and np.array_equal(missing_mask.numpy(), e_mm.astype(np.uint8)), entry

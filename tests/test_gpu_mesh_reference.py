@@ -1,4 +1,4 @@
-"""The four mesh voxelisers of the HIP backend (k_mesh_* in csrc/ops_kernels.hpp) and the wall distances they hand to HybridBC
+"""The four mesh voxelisers of the HIP backend (k_mesh_* in csrc/masker_kernels.hpp) and the wall distances they hand to HybridBC
 against the fp64 reference of tests/_mesh_ref.py, on a zoo of meshes chosen for what one easy sphere never runs: more triangles
 than one 256-thread block (the tix >= n_tri guard, atomicMin / atomicOr between blocks), the clamps at the domain faces and tags
 dropped outside the box, the padded grid of AABB_CLOSE next to a face, close_voxels 1 and 3, links that cross two surfaces (the
@@ -20,20 +20,17 @@ from xlb_amd.helper import create_nse_fields
 from xlb_amd.operator.boundary_condition import HybridBC
 from xlb_amd.operator.boundary_masker import BC_SOLID, MeshVoxelizationMethod, mesh_masker_for
 
-from _util import init_hip, mesh_zoo, remap_ids
+from _util import ORACLE_CASES, init_hip, mesh_zoo, remap_ids
 
 pytestmark = pytest.mark.gpu
 
 ZOO = mesh_zoo()
 REFERENCE_MESHES = ["sphere2", "torus", "box", "box_low_faces", "box_high_faces", "plate", "two_boxes", "sphere2_inward", "box_zero_area"]
-ORACLE_MESHES = ["box", "box_low_faces", "box_high_faces", "plate", "two_boxes", "box_zero_area", "integer_box"]  # 12 - 24 triangles
 METHODS = [("AABB", 0, False), ("RAY", 0, False), ("RAY", 0, True), ("WINDING", 0, False), ("WINDING", 0, True), ("AABB_CLOSE", 2, False),
            ("AABB_CLOSE", 2, True)]
 CASES = [(name, lattice) + m for name in REFERENCE_MESHES for lattice in ("D3Q19", "D3Q27") for m in METHODS]
 CASES += [(name, lattice, "AABB_CLOSE", h, d) for name in ("box", "box_low_faces", "box_high_faces") for lattice in ("D3Q19", "D3Q27") for h in (1, 3)
           for d in (False, True)]
-ORACLE_CASES = [(name, "D3Q27", m, h) for name in ORACLE_MESHES for m, h in (("AABB", 0), ("RAY", 0), ("WINDING", 0), ("AABB_CLOSE", 2))]
-ORACLE_CASES += [(name, "D3Q19", m, h) for name in ("box_low_faces", "integer_box") for m, h in (("AABB", 0), ("RAY", 0), ("WINDING", 0), ("AABB_CLOSE", 1))]
 ORACLE_ID = 3
 
 
