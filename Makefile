@@ -11,7 +11,8 @@ SRCS      := api.hip masker.hip stepper.hip ibm.hip stats.hip comm.cpp step_d2q9
              step_d2q9_ext.hip step_d3q19_ext.hip step_d3q27_ext.hip step_d2q9_reg.hip step_d3q19_reg.hip step_d3q27_reg.hip step2_d3q19.hip step2_d3q19_strips.hip step2_d3q27.hip yardstick.hip \
              scalar.hip scalar_d2q9.hip scalar_d3q19.hip scalar_d3q27.hip \
              adjoint.hip adjoint_d2q9.hip adjoint_d3q19.hip adjoint_d3q27.hip \
-             multiphase.hip multiphase_d2q9.hip multiphase_d3q19.hip multiphase_d3q27.hip
+             multiphase.hip multiphase_d2q9.hip multiphase_d3q19.hip multiphase_d3q27.hip \
+             multicomponent.hip multicomponent_d2q9.hip multicomponent_d3q19.hip multicomponent_d3q27.hip
 OBJS      := $(addprefix $(OBJDIR)/,$(addsuffix .o,$(basename $(SRCS))))
 HDRS      := $(wildcard $(CSRC)/*.hpp) include/xlbhip.h
 

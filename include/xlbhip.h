@@ -39,6 +39,7 @@ typedef struct xlbhip_stats xlbhip_stats;
 typedef struct xlbhip_scalar xlbhip_scalar;
 typedef struct xlbhip_adjoint xlbhip_adjoint;
 typedef struct xlbhip_multiphase xlbhip_multiphase;
+typedef struct xlbhip_multicomponent xlbhip_multicomponent;
 
 /* element types of a field; mirrors Precision in xlb/precision_policy.py:13-54 */
 enum {
@@ -599,6 +600,46 @@ int xlbhip_multiphase_psi(xlbhip_multiphase* m, const xlbhip_field* f, const xlb
 int xlbhip_multiphase_force(xlbhip_multiphase* m, const xlbhip_field* f, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, xlbhip_field* force);
 int xlbhip_multiphase_macroscopic(xlbhip_multiphase* m, const xlbhip_field* f, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, xlbhip_field* rho,
                                   xlbhip_field* u);
+
+/* ---- Shan-Chen flow of two immiscible components A and B ------------------------------------------------------------------------------
+ * (no counterpart in the reference; Shan and Chen, Phys. Rev. E 47, 1815 (1993); Shan and Doolen, J. Stat. Phys. 81, 379 (1995); walls
+ * after Martys and Chen, Phys. Rev. E 53, 743 (1996); applied through the exact-difference forcing the reference has for a constant
+ * force, xlb/operator/force/exact_difference_force.py; pinned by the NumPy restatement tests/_multicomponent_ref.py)
+ * Each component s has its populations f^s on the same lattice and its relaxation rate omega_s.  One step on the post-streaming
+ * populations (pull, then the streaming-step boundary rules, per component): rho_s, u_s = moments; psi_s = rho_s;
+ * u' = (omega_A rho_A u_A + omega_B rho_B u_B) / (omega_A rho_A + omega_B rho_B); S^s_a = sum_{i >= 1} (w_i psi_s(x + c_i)) c_ai with the
+ * lattice's weights; F^A = (-psi_A) (G_AA S^A + G_AB S^B), F^B = (-psi_B) (G_AB S^A + G_BB S^B); each component collides by BGK towards
+ * feq(rho_s, u') with the exact-difference acceleration force + F^s / rho_s.  A neighbour behind a missing direction counts with the wall
+ * densities of the cell's own bc id; fullway bounce-back cells and solid cells (bc id 255) carry their wall densities and feel no force.
+ * The bulk pressure is cs^2 (rho_A + rho_B) + cs^2 (G_AA rho_A^2 / 2 + G_AB rho_A rho_B + G_BB rho_B^2 / 2).  Two launches per step (both
+ * densities, then the step that reads the neighbours'); the density fields are the object's.  Fields without ghost planes, FP32FP32 /
+ * FP64FP64 / FP64FP32.  bcs: as for xlbhip_stepper_create, kinds 2 and 3 only, and a halfway wall at rest (all values zero: the
+ * moving-wall constant assumes density 1). */
+int xlbhip_multicomponent_create(xlbhip_ctx* ctx, int lattice, int compute_dtype, int store_dtype, int n_bc, const xlbhip_bc_desc* bcs,
+                                 xlbhip_multicomponent** out);
+int xlbhip_multicomponent_destroy(xlbhip_multicomponent* m);
+/* force: 3 doubles (internal 3-component form) or NULL, the constant acceleration added to F^s / rho_s of both components */
+int xlbhip_multicomponent_set_model(xlbhip_multicomponent* m, double g_aa, double g_ab, double g_bb, const double* force);
+/* The wall densities: rho_w_a[i], rho_w_b[i] for bc id bc_ids[i] (one of this object's BCs, or 255 for solid cells), rounded to the
+ * compute dtype.  Every other id has 0 for both.  Replaces all values set before. */
+int xlbhip_multicomponent_set_wall_density(xlbhip_multicomponent* m, int n, const int32_t* bc_ids, const double* rho_w_a, const double* rho_w_b);
+/* one step (f^A, f^B)(t) -> (t + 1); omega_a, omega_b in (0, 2] */
+int xlbhip_multicomponent_step(xlbhip_multicomponent* m, const xlbhip_field* fa_src, xlbhip_field* fa_dst, const xlbhip_field* fb_src, xlbhip_field* fb_dst,
+                               const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, double omega_a, double omega_b, int64_t timestep);
+/* n_steps x (step, swap of both pairs) enqueued without a host wait; *result_in_1: the result is in fa_1 and fb_1 */
+int xlbhip_multicomponent_run(xlbhip_multicomponent* m, xlbhip_field* fa_0, xlbhip_field* fa_1, xlbhip_field* fb_0, xlbhip_field* fb_1,
+                              const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, double omega_a, double omega_b, int64_t first_timestep,
+                              int64_t n_steps, int* result_in_1);
+/* Outputs of the post-streaming state of the stored fields fa, fb, in the compute dtype.  densities: psi_A, psi_B as the force reads them
+ * (cardinality 1 each; the wall densities at wall cells).  force: F^A and F^B without the force vector (cardinality d each; zero at wall
+ * cells).  macroscopic: rho_A, rho_B (the moments, cardinality 1 each) and the barycentric velocity
+ * u = (rho_A u_A + rho_B u_B + (F^A + F^B) / 2) / (rho_A + rho_B) (cardinality d). */
+int xlbhip_multicomponent_densities(xlbhip_multicomponent* m, const xlbhip_field* fa, const xlbhip_field* fb, const xlbhip_field* bc_mask,
+                                    const xlbhip_field* missing_mask, xlbhip_field* rho_a, xlbhip_field* rho_b);
+int xlbhip_multicomponent_force(xlbhip_multicomponent* m, const xlbhip_field* fa, const xlbhip_field* fb, const xlbhip_field* bc_mask,
+                                const xlbhip_field* missing_mask, xlbhip_field* force_a, xlbhip_field* force_b);
+int xlbhip_multicomponent_macroscopic(xlbhip_multicomponent* m, const xlbhip_field* fa, const xlbhip_field* fb, const xlbhip_field* bc_mask,
+                                      const xlbhip_field* missing_mask, xlbhip_field* rho_a, xlbhip_field* rho_b, xlbhip_field* u);
 
 #ifdef __cplusplus
 }

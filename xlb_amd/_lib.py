@@ -158,6 +158,15 @@ SIGNATURES = {
     "xlbhip_multiphase_psi": [_p, _p, _p, _p, _p],
     "xlbhip_multiphase_force": [_p, _p, _p, _p, _p],
     "xlbhip_multiphase_macroscopic": [_p, _p, _p, _p, _p, _p],
+    "xlbhip_multicomponent_create": [_p, _i, _i, _i, _i, C.POINTER(BcDesc), _pp],
+    "xlbhip_multicomponent_destroy": [_p],
+    "xlbhip_multicomponent_set_model": [_p, _d, _d, _d, _p],
+    "xlbhip_multicomponent_set_wall_density": [_p, _i, _p, _p, _p],
+    "xlbhip_multicomponent_step": [_p, _p, _p, _p, _p, _p, _p, _d, _d, _i64],
+    "xlbhip_multicomponent_run": [_p, _p, _p, _p, _p, _p, _p, _d, _d, _i64, _i64, C.POINTER(C.c_int)],
+    "xlbhip_multicomponent_densities": [_p, _p, _p, _p, _p, _p, _p],
+    "xlbhip_multicomponent_force": [_p, _p, _p, _p, _p, _p, _p],
+    "xlbhip_multicomponent_macroscopic": [_p, _p, _p, _p, _p, _p, _p, _p],
 }
 
 _lib = None
@@ -960,6 +969,47 @@ class Multiphase(_Native):
 
     def macroscopic(self, f, bc_mask, missing_mask, rho, u):
         check(load().xlbhip_multiphase_macroscopic(self._h, _hf(f), _h(bc_mask), _h(missing_mask), _hf(rho), _hf(u)))
+
+
+class Multicomponent(_Native):
+    """Native two-component Shan-Chen object (xlbhip_multicomponent_create): the boundary tables, the wall densities and the two density
+    fields of the step."""
+
+    _kind = "multicomponent"
+
+    def __init__(self, ctx, lattice_id, compute_code, store_code, bc_descs):
+        super().__init__(ctx, lattice_id, compute_code, store_code, *_bc_array(bc_descs))
+
+    def set_model(self, g_aa, g_ab, g_bb, force3):
+        f = None if force3 is None else np.ascontiguousarray(force3, dtype=np.float64)
+        check(load().xlbhip_multicomponent_set_model(self._h, float(g_aa), float(g_ab), float(g_bb), None if f is None else f.ctypes.data))
+
+    def set_wall_density(self, walls):
+        """walls: [(bc id, rho_w of A, rho_w of B)]"""
+        ids = np.array([w[0] for w in walls], dtype=np.int32)
+        rho_a = np.array([w[1] for w in walls], dtype=np.float64)
+        rho_b = np.array([w[2] for w in walls], dtype=np.float64)
+        check(load().xlbhip_multicomponent_set_wall_density(self._h, len(walls), ids.ctypes.data, rho_a.ctypes.data, rho_b.ctypes.data))
+
+    def step(self, fa_src, fa_dst, fb_src, fb_dst, bc_mask, missing_mask, omega_a, omega_b, timestep):
+        check(load().xlbhip_multicomponent_step(self._h, _hf(fa_src), _hf(fa_dst), _hf(fb_src), _hf(fb_dst), _h(bc_mask), _h(missing_mask), float(omega_a),
+                                                float(omega_b), int(timestep)))
+
+    def run(self, fa_0, fa_1, fb_0, fb_1, bc_mask, missing_mask, omega_a, omega_b, first_timestep, n_steps):
+        """n steps; returns True when the result is in fa_1 and fb_1."""
+        where = C.c_int()
+        check(load().xlbhip_multicomponent_run(self._h, _hf(fa_0), _hf(fa_1), _hf(fb_0), _hf(fb_1), _h(bc_mask), _h(missing_mask), float(omega_a),
+                                               float(omega_b), int(first_timestep), int(n_steps), C.byref(where)))
+        return bool(where.value)
+
+    def densities(self, fa, fb, bc_mask, missing_mask, rho_a, rho_b):
+        check(load().xlbhip_multicomponent_densities(self._h, _hf(fa), _hf(fb), _h(bc_mask), _h(missing_mask), _hf(rho_a), _hf(rho_b)))
+
+    def force(self, fa, fb, bc_mask, missing_mask, force_a, force_b):
+        check(load().xlbhip_multicomponent_force(self._h, _hf(fa), _hf(fb), _h(bc_mask), _h(missing_mask), _hf(force_a), _hf(force_b)))
+
+    def macroscopic(self, fa, fb, bc_mask, missing_mask, rho_a, rho_b, u):
+        check(load().xlbhip_multicomponent_macroscopic(self._h, _hf(fa), _hf(fb), _h(bc_mask), _h(missing_mask), _hf(rho_a), _hf(rho_b), _hf(u)))
 
 
 def macroscopic_adjoint(ctx, lattice_id, compute_code, f, rho_bar, u_bar, lam):

@@ -1,5 +1,6 @@
 """Steppers of the HIP backend: the fused incompressible Navier-Stokes step, the same with an immersed boundary, the same
-with a transported scalar, the discrete adjoint of the plain BGK step, and the Shan-Chen liquid-vapour step."""
+with a transported scalar, the discrete adjoint of the plain BGK step, the Shan-Chen liquid-vapour step and the Shan-Chen step of two
+immiscible components."""
 
 from .stepper import Stepper as Stepper
 from .nse_stepper import IncompressibleNavierStokesStepper as IncompressibleNavierStokesStepper
@@ -12,3 +13,4 @@ from .multiphase_stepper import (
     ShanChenDensity as ShanChenDensity,
     CarnahanStarling as CarnahanStarling,
 )
+from .multicomponent_stepper import MulticomponentStepper as MulticomponentStepper, ShanChenMixture as ShanChenMixture
