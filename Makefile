@@ -12,7 +12,8 @@ SRCS      := api.hip masker.hip stepper.hip ibm.hip stats.hip comm.cpp step_d2q9
              scalar.hip scalar_d2q9.hip scalar_d3q19.hip scalar_d3q27.hip \
              adjoint.hip adjoint_d2q9.hip adjoint_d3q19.hip adjoint_d3q27.hip \
              multiphase.hip multiphase_d2q9.hip multiphase_d3q19.hip multiphase_d3q27.hip \
-             multicomponent.hip multicomponent_d2q9.hip multicomponent_d3q19.hip multicomponent_d3q27.hip
+             multicomponent.hip multicomponent_d2q9.hip multicomponent_d3q19.hip multicomponent_d3q27.hip \
+             porous.hip porous_d2q9.hip porous_d3q19.hip porous_d3q27.hip
 OBJS      := $(addprefix $(OBJDIR)/,$(addsuffix .o,$(basename $(SRCS))))
 HDRS      := $(wildcard $(CSRC)/*.hpp) include/xlbhip.h
 

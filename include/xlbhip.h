@@ -565,6 +565,35 @@ int xlbhip_adjoint_reset(xlbhip_adjoint* a);
 int xlbhip_macroscopic_adjoint(xlbhip_ctx* ctx, int lattice, int compute_dtype, const xlbhip_field* f, const xlbhip_field* rho_bar, const xlbhip_field* u_bar,
                                xlbhip_field* lam);
 
+/* ---- porous BGK step and its discrete adjoint -----------------------------------------------------------------------------------
+ * (geometry as a continuous field: a per-cell solidity alpha in [0, 1], after Pingen, Evgrafov and Maute, Struct. Multidisc. Optim. 34,
+ * 507 (2007); pinned by the NumPy restatement tests/_porous_ref.py)  The step is the fused BGK step with the equilibrium taken at the
+ * damped velocity (1 - alpha) u; alpha == 0 is the plain BGK step bit for bit.  Values outside [0, 1] are the caller's business and are
+ * not checked.  Scope as the adjoint's: BGK without a force; fields without ghost planes; FP32FP32 / FP64FP64 / FP64FP32; bc kinds 1..4.
+ * The solidity field has one value per cell in the COMPUTE dtype; it is bound by ADDRESS: destroying the field while it is bound and
+ * then stepping or reading the gradient is undefined (the library cannot tell), so bind another field first or keep it alive.  The adjoint
+ * step is xlbhip_adjoint_step's with the porous transpose; beside dL/domega it accumulates dL/dalpha in an fp64 field of the object,
+ * each cell by its own thread, in the order of the steps. */
+typedef struct xlbhip_porous xlbhip_porous;
+int xlbhip_porous_create(xlbhip_ctx* ctx, int lattice, int compute_dtype, int store_dtype, int n_bc, const xlbhip_bc_desc* bcs, xlbhip_porous** out);
+int xlbhip_porous_destroy(xlbhip_porous* p);
+/* binds alpha; a field whose grid (nx, ny, nz) differs from the last one's starts a new (zero) gradient field */
+int xlbhip_porous_set_solidity(xlbhip_porous* p, const xlbhip_field* alpha);
+int xlbhip_porous_step(xlbhip_porous* p, const xlbhip_field* f_src, xlbhip_field* f_dst, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask,
+                       double omega, int64_t timestep);
+int xlbhip_porous_run(xlbhip_porous* p, xlbhip_field* f_a, xlbhip_field* f_b, const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, double omega,
+                      int64_t first_timestep, int64_t n_steps, int* result_in_b);
+/* as xlbhip_adjoint_step / xlbhip_adjoint_run, at the bound alpha */
+int xlbhip_porous_adjoint_step(xlbhip_porous* p, const xlbhip_field* f_n, const xlbhip_field* lam_in, xlbhip_field* lam_out, const xlbhip_field* bc_mask,
+                               const xlbhip_field* missing_mask, double omega);
+int xlbhip_porous_adjoint_run(xlbhip_porous* p, int64_t n_states, const xlbhip_field* const* states, xlbhip_field* lam_a, xlbhip_field* lam_b,
+                              const xlbhip_field* bc_mask, const xlbhip_field* missing_mask, double omega, int* result_in_b);
+/* zeroes dL/domega and dL/dalpha (enqueued) / dL/domega (waits for the compute stream) / copies dL/dalpha into `out`, an fp64 field of
+ * one value per cell on alpha's grid (enqueued) */
+int xlbhip_porous_adjoint_reset(xlbhip_porous* p);
+int xlbhip_porous_omega_gradient(xlbhip_porous* p, double* out);
+int xlbhip_porous_solidity_gradient(xlbhip_porous* p, xlbhip_field* out);
+
 /* ---- Shan-Chen pseudopotential flow (single component, liquid-vapour) ----------------------------------------------------------
  * (no counterpart in the reference; the interaction force is Shan and Chen's, Phys. Rev. E 47, 1815 (1993), applied through the
  * exact-difference forcing the reference has for a constant force, xlb/operator/force/exact_difference_force.py; the Carnahan-Starling

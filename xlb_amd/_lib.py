@@ -149,6 +149,16 @@ SIGNATURES = {
     "xlbhip_adjoint_omega_gradient": [_p, C.POINTER(_d)],
     "xlbhip_adjoint_reset": [_p],
     "xlbhip_macroscopic_adjoint": [_p, _i, _i, _p, _p, _p, _p],
+    "xlbhip_porous_create": [_p, _i, _i, _i, _i, C.POINTER(BcDesc), _pp],
+    "xlbhip_porous_destroy": [_p],
+    "xlbhip_porous_set_solidity": [_p, _p],
+    "xlbhip_porous_step": [_p, _p, _p, _p, _p, _d, _i64],
+    "xlbhip_porous_run": [_p, _p, _p, _p, _p, _d, _i64, _i64, C.POINTER(C.c_int)],
+    "xlbhip_porous_adjoint_step": [_p, _p, _p, _p, _p, _p, _d],
+    "xlbhip_porous_adjoint_run": [_p, _i64, _pp, _p, _p, _p, _p, _d, C.POINTER(C.c_int)],
+    "xlbhip_porous_adjoint_reset": [_p],
+    "xlbhip_porous_omega_gradient": [_p, C.POINTER(_d)],
+    "xlbhip_porous_solidity_gradient": [_p, _p],
     "xlbhip_multiphase_create": [_p, _i, _i, _i, _i, C.POINTER(BcDesc), _pp],
     "xlbhip_multiphase_destroy": [_p],
     "xlbhip_multiphase_set_model": [_p, _i, _d, _i, _p, _p],
@@ -927,6 +937,53 @@ class Adjoint(_Native):
 
     def reset(self):
         check(load().xlbhip_adjoint_reset(self._h))
+
+
+class Porous(_Native):
+    """Native porous object (xlbhip_porous_create): the boundary tables of the porous step and of its adjoint step, the binding of the
+    solidity field, the device scalar dL/domega and the fp64 field dL/dalpha.  ``step`` / ``run`` are the forward step's, ``adjoint_step``
+    / ``adjoint_run`` have the interface of ``Adjoint.step`` / ``Adjoint.run``."""
+
+    _kind = "porous"
+
+    def __init__(self, ctx, lattice_id, compute_code, store_code, bc_descs):
+        super().__init__(ctx, lattice_id, compute_code, store_code, *_bc_array(bc_descs))
+        self._alpha = None
+
+    def set_solidity(self, alpha):
+        check(load().xlbhip_porous_set_solidity(self._h, _h(alpha)))
+        self._alpha = alpha  # (bound by reference: it outlives the binding)
+
+    def step(self, f_src, f_dst, bc_mask, missing_mask, omega, timestep):
+        check(load().xlbhip_porous_step(self._h, _hf(f_src), _hf(f_dst), _h(bc_mask), _h(missing_mask), float(omega), int(timestep)))
+
+    def run(self, f_a, f_b, bc_mask, missing_mask, omega, first_timestep, n_steps):
+        where = C.c_int()
+        check(load().xlbhip_porous_run(self._h, _hf(f_a), _hf(f_b), _h(bc_mask), _h(missing_mask), float(omega), int(first_timestep), int(n_steps),
+                                       C.byref(where)))
+        return bool(where.value)
+
+    def adjoint_step(self, f_n, lam_in, lam_out, bc_mask, missing_mask, omega):
+        check(load().xlbhip_porous_adjoint_step(self._h, _hf(f_n), _hf(lam_in), _hf(lam_out), _h(bc_mask), _h(missing_mask), float(omega)))
+
+    def adjoint_run(self, states, lam_a, lam_b, bc_mask, missing_mask, omega):
+        where = C.c_int()
+        arr = (C.c_void_p * max(len(states), 1))(*[_hf(f) for f in states])
+        check(load().xlbhip_porous_adjoint_run(self._h, len(states), arr, _hf(lam_a), _hf(lam_b), _h(bc_mask), _h(missing_mask), float(omega),
+                                               C.byref(where)))
+        return bool(where.value)
+
+    def omega_gradient(self):
+        out = _d()
+        check(load().xlbhip_porous_omega_gradient(self._h, C.byref(out)))
+        return out.value
+
+    def solidity_gradient(self, out):
+        check(load().xlbhip_porous_solidity_gradient(self._h, _hf(out)))
+        return out
+
+    def reset(self):
+        check(load().xlbhip_porous_adjoint_reset(self._h))
 
 
 class Multiphase(_Native):

@@ -25,11 +25,19 @@ Scope: BGK; D2Q9, D3Q19, D3Q27; FP32FP32, FP64FP64, FP64FP32; periodic edges, Eq
 velocity or none), FullwayBounceBackBC, DoNothingBC; single rank.  Limits (NotImplementedError at construction): KBC and
 SmagorinskyLESBGK, a force vector, ZouHeBC / RegularizedBC / ExtrapolationOutflowBC, HybridBC, profile tables and time-dependent walls,
 fp16 storage, slab-decomposed fields, IBMStepper and ScalarTransportStepper.  Not covered: gradients with respect to boundary values
-or geometry, multi-rank sweeps, out-of-core checkpoints, an autograd wrapper (the DLPack view of a field is enough to build one)."""
+or to geometry other than a PorousStepper's solidity (below), multi-rank sweeps, out-of-core checkpoints, an autograd wrapper (the DLPack
+view of a field is enough to build one).
+
+**Geometry.**  ``AdjointStepper(PorousStepper(...))`` is the adjoint of the porous step (porous_stepper.py) at the solidity field bound to
+the forward stepper.  ``adjoint_step``, ``backward``, ``gradient`` and ``MacroscopicAdjoint`` work as above; every adjoint step also adds
+each cell's term -omega sum_d B_d u_d to an fp64 field dL/dalpha on the device (the cell's own thread, in the order of the steps), which
+``solidity_gradient()`` returns and ``reset()`` clears, and ``gradient`` returns three values: (lam_0, dL/domega, dL/dalpha)."""
 
 from ... import _lib
 from ..boundary_condition import DoNothingBC, EquilibriumBC, FullwayBounceBackBC, HalfwayBounceBackBC
+from ...precision_policy import Precision
 from .nse_stepper import IncompressibleNavierStokesStepper, refuse_unsupported
+from .porous_stepper import PorousStepper
 
 
 class AdjointStepper:
@@ -37,8 +45,9 @@ class AdjointStepper:
         fwd = forward_stepper
         if not isinstance(fwd, IncompressibleNavierStokesStepper):
             raise TypeError("AdjointStepper wraps an IncompressibleNavierStokesStepper")
-        if type(fwd) is not IncompressibleNavierStokesStepper:
-            raise NotImplementedError(f"AdjointStepper: the adjoint of {type(fwd).__name__} is not supported (the plain fluid stepper only)")
+        if type(fwd) not in (IncompressibleNavierStokesStepper, PorousStepper):
+            raise NotImplementedError(f"AdjointStepper: the adjoint of {type(fwd).__name__} is not supported (the plain fluid stepper and "
+                                      "PorousStepper only)")
         if fwd.collision_type != "BGK":
             raise NotImplementedError(f"AdjointStepper: collision_type {fwd.collision_type!r} is not supported; the adjoint is built for BGK")
         if fwd.force_vector is not None:
@@ -56,9 +65,15 @@ class AdjointStepper:
         self.velocity_set = fwd.velocity_set
         self.precision_policy = pp
         self._ctx = fwd._ctx
+        self.porous = type(fwd) is PorousStepper
         self._adjoint = None
 
     def _native(self):
+        if self.porous:
+            native = self.forward._bound()  # (refuses without a solidity field; the forward stepper's object: tables, alpha, gradients)
+            if self._adjoint is None:
+                self._adjoint = _PorousAdjoint(native)
+            return self._adjoint
         if self._adjoint is None:
             fwd = self.forward
             descs = [bc._hip_descriptor() for bc in fwd.boundary_conditions]
@@ -86,7 +101,15 @@ class AdjointStepper:
         """dL/domega of every adjoint step since the last reset (waits for the device)"""
         return self._native().omega_gradient()
 
+    def solidity_gradient(self):
+        """dL/dalpha of every adjoint step since the last reset, as a new fp64 field of one value per cell (a PorousStepper forward only;
+        enqueued: reading the field waits for the device)"""
+        if not self.porous:
+            raise NotImplementedError("AdjointStepper.solidity_gradient: the forward stepper is not a PorousStepper")
+        return self._native().solidity_gradient(self.grid.create_field(cardinality=1, dtype=Precision.FP64))
+
     def reset(self):
+        """Clears dL/domega (and dL/dalpha of a porous forward stepper)"""
         self._native().reset()
 
     @staticmethod
@@ -104,9 +127,10 @@ class AdjointStepper:
                 "forward_steps": n, "recomputed_steps": n - len(checkpoints)}
 
     def gradient(self, f_init, bc_mask, missing_mask, omega, n_steps, cotangent, checkpoint_every=8):
-        """(lam_0 = dL/df_init, dL/domega) of L(f_N), f_N = S^N(f_init; omega).  ``cotangent(f_final)`` returns lam_N = dL/df_N as a
-        field of the store dtype (it may read f_final, which is overwritten afterwards); the sweep takes that field over: lam_0 comes back
-        in it or in a second one made here, and the other of the two is freed.  f_init is left as it is."""
+        """(lam_0 = dL/df_init, dL/domega[, dL/dalpha: a porous forward stepper]) of L(f_N), f_N = S^N(f_init; omega).
+        ``cotangent(f_final)`` returns lam_N = dL/df_N as a field of the store dtype (it may read f_final, which is overwritten
+        afterwards); the sweep takes that field over: lam_0 comes back in it or in a second one made here, and the other of the two is
+        freed.  f_init is left as it is."""
         plan = self.checkpoint_plan(n_steps, checkpoint_every)
         fwd, store = self.forward, self.precision_policy.store_precision
         new = lambda: self.grid.create_field(cardinality=self.velocity_set.q, dtype=store)  # noqa: E731
@@ -147,8 +171,16 @@ class AdjointStepper:
                     self._ctx.sync()  # (the sweep still reads the checkpoint)
                     ckpt.pop(seg["start"]).free()
             d_omega = self.omega_gradient()
-            return lam, d_omega
+            return (lam, d_omega, self.solidity_gradient()) if self.porous else (lam, d_omega)
         finally:
             self._ctx.sync()
             for f in scratch + [f for t, f in ckpt.items() if t != 0] + ([lam_other] if lam_other is not None else []):
                 f.free()
+
+
+class _PorousAdjoint:
+    """The adjoint half of a native porous object (_lib.Porous) under the names of _lib.Adjoint"""
+
+    def __init__(self, native):
+        self.step, self.run = native.adjoint_step, native.adjoint_run
+        self.omega_gradient, self.solidity_gradient, self.reset = native.omega_gradient, native.solidity_gradient, native.reset
